@@ -19,6 +19,11 @@ recalled upstream AIR) are timed beside it as `recalled_upstream_air`.  SIPP_BEN
 A secondary object `io_sharded` times ONE larger instance cut into `world` ranges of obligations (level L-D, strong scaling,
 no collective either).
 
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) sets up, runs W untimed and K timed steps and prints the headline:
+`value`, `ms_per_step` and what describes them.  Everything else -- the verifiers on the proofs, the per-kernel HIP-event
+times and rooflines, the queued (`pipelined`) figure, the side legs, the other AIR variant, `io_sharded`, `outer_plonk`
+and the CPU baseline -- runs only with `--full`.  `--dump-outputs DIR` writes the three proofs of the last timed step.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -41,6 +46,16 @@ PMC_FILE = "r06_pmc.json"   # rocprofv3 PMC passes of this same command (scripts
 def load_ios(n):
     d = np.load(os.path.join(ROOT, "tests", "golden", "sipp_n%d_ios.npz" % n))
     return [d["g1"], d["g2"], d["fq12"]]
+
+
+def dump_outputs(out_dir, proofs):
+    """the three flat proofs (u64 words) a caller of the timed path receives, as DIR/proof_<name>.npy: float64 arrays of
+    shape (words, 2) holding the low and high 32 bits of every word, exactly (a u64 does not fit a float64's mantissa)"""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, pf in zip(("g1", "g2", "fq12"), proofs):
+        w = np.asarray(pf, dtype=np.uint64)
+        np.save(os.path.join(out_dir, "proof_%s.npy" % name),
+                np.stack([w & np.uint64(0xFFFFFFFF), w >> np.uint64(32)], axis=1).astype(np.float64))
 
 
 def cpu_baseline(ios, shapes, kinds, budget_s=150.0):
@@ -426,7 +441,14 @@ def main():
                     help="instances proved concurrently for the secondary `pipelined` figure (1 = skip); default 5 on one "
                          "rank, 1 (skipped) when launched with more: 8 ranks x 5 slots x 3 worker threads would put 120 host "
                          "threads on one node for a secondary figure")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: verify the proofs, per-kernel times and rooflines, the queued figure, the side "
+                         "legs, io_sharded, outer_plonk and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the three proofs of the last one as DIR/proof_{g1,g2,fq12}.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # invoked bare (`python bench.py --gpus N`): start the N ranks ourselves, exactly as the driver's launcher would.  Nothing
         # in this process has touched the GPU (torch is not even imported yet), the ranks are fresh children, rank 0's one JSON
@@ -502,21 +524,26 @@ def main():
             c.profile_reset()
         proof_ms[:] = [0.0, 0.0, 0.0]
 
-    prepare_checker(rank, barrier)
-    # W untimed warm-up steps, then exactly K steps between barrier + synchronize, max over ranks
+    if args.full:
+        prepare_checker(rank, barrier)
+    # W untimed warm-up steps, then exactly K steps between barrier + synchronize, max over ranks (--full: with the per-kernel
+    # HIP-event brackets on)
     elapsed, proofs = dist_util.timed_steps(step, args.steps, args.warmup, sync=device_sync, device=red_device,
-                                            before_timing=start_profiling)
+                                            before_timing=start_profiling if args.full else None)
     proofs = [p.copy() for p in proofs]           # the instance's output buffers are reused by the later legs
-    # every rank pushes the proofs of its LAST timed step through the oracle's verifier (outside the timed region)
-    lib_verify_ms = []
-    verified_main = all_ranks_true(verify_proofs(proofs, lib_verify_ms), red_device)
-    prof = {}
-    for c in inst.distinct_ctxs():
-        for k, v in c.profile_report().items():
-            e = prof.setdefault(k, {"calls": 0, "ms": 0.0})
-            e["calls"] += v["calls"]
-            e["ms"] += v["ms"]
-        c.profile(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, proofs)
+    if args.full:
+        # every rank pushes the proofs of its LAST timed step through the oracle's verifier (outside the timed region)
+        lib_verify_ms = []
+        verified_main = all_ranks_true(verify_proofs(proofs, lib_verify_ms), red_device)
+        prof = {}
+        for c in inst.distinct_ctxs():
+            for k, v in c.profile_report().items():
+                e = prof.setdefault(k, {"calls": 0, "ms": 0.0})
+                e["calls"] += v["calls"]
+                e["ms"] += v["ms"]
+            c.profile(False)
 
     def dist_util_max(x):
         return dist_util.max_over_ranks(x, device=red_device)
@@ -525,7 +552,7 @@ def main():
     # (3 streams each).  One instance leaves issue slots idle in its latency-bound phases (chains, Fiat-Shamir round
     # trips, FRI tail); a server with a queue of proofs fills them.  `value` above stays the single-instance number.
     pipelined = None
-    if args.inflight > 1 and not serial and sum(ws) * (args.inflight + 1) < (240 << 30):
+    if args.full and args.inflight > 1 and not serial and sum(ws) * (args.inflight + 1) < (240 << 30):
         # sipp_instances_prove: `inflight` slots of three ctxs take the instances of a queue from a shared counter
         queue = sipp_amd.InstanceQueue([a.shape[0] for a in ios], in_flight=args.inflight, device=local_rank, priorities=prios,
                                        hardened=hardened)
@@ -546,7 +573,7 @@ def main():
     # one extra step with the three proofs run one after the other (outside the timed region): per-kernel times without the
     # other proofs' kernels competing for the SIMDs
     kernel_ms_serial = None
-    if rank == 0 and not serial:
+    if args.full and rank == 0 and not serial:
         for c in inst.distinct_ctxs():
             c.profile(True)
             c.profile_reset()
@@ -561,6 +588,32 @@ def main():
     if rank == 0:
         ms_per_step = 1e3 * elapsed / args.steps
         value = dist_util.whole_job_rate(args.n, world, elapsed / args.steps)
+        out = {
+            "metric": "SIPP proof-gen wall-clock + pairings-aggregated/sec, n=%d (the 3 STARK sub-proofs, %s; outer plonky2 proof not included)"
+                      % (args.n, "hardened G1/G2 AIRs" if hardened else "plain G1/G2 AIRs: forgeable for crafted statements, see hardened_instance"),
+            "value": value, "unit": "pairings/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "u64", "data": "synthetic",
+            # what carried the barrier and the max-over-ranks reduction of the timed region
+            "timing_reduction": ("%s:%s" % (dist.get_backend(), red_device)) if dist.is_initialized() else "single process",
+            "config": {"workload": "n=%d SIPP instance per GPU: G1ExpStark %d IO (N=2^%d, W+P+Q=%d), G2ExpStark %d IO "
+                                   "(N=2^%d, %d), Fq12ExpStark %d IO (N=2^%d, %d); IO records on host -> 3 flat proofs "
+                                   "on host, the 3 sub-proofs on 3 concurrent HIP streams" % (args.n, ios[0].shape[0], shapes[0][0], sum(shapes[0][1:]),
+                                               ios[1].shape[0], shapes[1][0], sum(shapes[1][1:]),
+                                               ios[2].shape[0], shapes[2][0], sum(shapes[2][1:])),
+                       "stark_config": "rate_bits=1 cap_height=4 pow_bits=16 arity=16 queries=84 challenges=2 pow_rule=duplex",
+                       "air_revision": air_revision(),
+                       "air_variant": ("hardened G1 / G2 exponentiation AIRs (API kinds 4 / 5: canonical x3, x-inequality witness, R = +-P proved; "
+                                       "+14 % columns) + Fq12ExpStark (kind 2)") if hardened else
+                                      "plain G1 / G2 exponentiation AIRs (kinds 0 / 1: incomplete chord rows as recalled from upstream) + Fq12ExpStark",
+                       "kinds": kinds,
+                       "columns": {"G1ExpStark": {"log_n": shapes[0][0], "W": shapes[0][1], "P": shapes[0][2], "Q": shapes[0][3]},
+                                   "G2ExpStark": {"log_n": shapes[1][0], "W": shapes[1][1], "P": shapes[1][2], "Q": shapes[1][3]},
+                                   "Fq12ExpStark": {"log_n": shapes[2][0], "W": shapes[2][1], "P": shapes[2][2], "Q": shapes[2][3]}},
+                       "parallelism": "%d independent SIPP instance(s), one per GPU, no collective" % world},
+            "proof_words": [int(len(p)) for p in proofs],
+        }
+    if rank == 0 and args.full:
         # dominant kernel: Poseidon leaf hashing, ONE STATE PER LANE (poseidon_leaves_kernel: every tree of more than 2^16 leaves).
         # Algorithmic bytes per launch: every LDE cell of the batch is read once (8 B), one 32-B digest per leaf is written.  The
         # thin trees' two-lane kernel (the Fq12 STARK) is a different kernel and has its own entry; batches of <= 4 columns are
@@ -654,34 +707,12 @@ def main():
                 cal = 1024.0 * al["eff_clock_ghz"] / al.get("cycles_per_inst", 4.0)
                 valu_instance.update({"peak_calibrated": cal, "frac_of_calibrated": ach / cal, "eff_clock_ghz": al["eff_clock_ghz"],
                                       "cycles_per_inst": al.get("cycles_per_inst", 4.0)})
-        out = {
-            "metric": "SIPP proof-gen wall-clock + pairings-aggregated/sec, n=%d (the 3 STARK sub-proofs, %s; outer plonky2 proof not included)"
-                      % (args.n, "hardened G1/G2 AIRs" if hardened else "plain G1/G2 AIRs: forgeable for crafted statements, see hardened_instance"),
-            "value": value, "unit": "pairings/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "u64", "data": "synthetic",
+        out.update({
             # the three proofs of the last timed step, on every rank, through oracle/stark.c's verifier after the timed region
             "verified": verified_main,
             # ... and through the library's own verifier first (sipp_stark_verify: host C++, one core; ms per proof, G1 / G2 / Fq12)
             "library_verifier": {"ms_per_proof": lib_verify_ms, "entry_point": "sipp_stark_verify (verify_stark_proof of the generators / data.verify)"},
             **({"verify_errors": VERIFY_ERRORS[:3]} if VERIFY_ERRORS else {}),
-            # what carried the barrier and the max-over-ranks reduction of the timed region
-            "timing_reduction": ("%s:%s" % (dist.get_backend(), red_device)) if dist.is_initialized() else "single process",
-            "config": {"workload": "n=%d SIPP instance per GPU: G1ExpStark %d IO (N=2^%d, W+P+Q=%d), G2ExpStark %d IO "
-                                   "(N=2^%d, %d), Fq12ExpStark %d IO (N=2^%d, %d); IO records on host -> 3 flat proofs "
-                                   "on host, the 3 sub-proofs on 3 concurrent HIP streams" % (args.n, ios[0].shape[0], shapes[0][0], sum(shapes[0][1:]),
-                                               ios[1].shape[0], shapes[1][0], sum(shapes[1][1:]),
-                                               ios[2].shape[0], shapes[2][0], sum(shapes[2][1:])),
-                       "stark_config": "rate_bits=1 cap_height=4 pow_bits=16 arity=16 queries=84 challenges=2 pow_rule=duplex",
-                       "air_revision": air_revision(),
-                       "air_variant": ("hardened G1 / G2 exponentiation AIRs (API kinds 4 / 5: canonical x3, x-inequality witness, R = +-P proved; "
-                                       "+14 % columns) + Fq12ExpStark (kind 2)") if hardened else
-                                      "plain G1 / G2 exponentiation AIRs (kinds 0 / 1: incomplete chord rows as recalled from upstream) + Fq12ExpStark",
-                       "kinds": kinds,
-                       "columns": {"G1ExpStark": {"log_n": shapes[0][0], "W": shapes[0][1], "P": shapes[0][2], "Q": shapes[0][3]},
-                                   "G2ExpStark": {"log_n": shapes[1][0], "W": shapes[1][1], "P": shapes[1][2], "Q": shapes[1][3]},
-                                   "Fq12ExpStark": {"log_n": shapes[2][0], "W": shapes[2][1], "P": shapes[2][2], "Q": shapes[2][3]}},
-                       "parallelism": "%d independent SIPP instance(s), one per GPU, no collective" % world},
             "roofline": {"bound": "hbm", "kernel": "poseidon_leaves", "achieved": achieved, "peak": HBM_PEAK_GBS,
                          "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
                          "traffic_source": ("profiles/%s (static: separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this "
@@ -718,10 +749,9 @@ def main():
                     / (sum(prof.get(k, {"ms": 0})["ms"] for k in NTT_KERNELS) * 1e-3)
                     if sum(prof.get(k, {"ms": 0})["ms"] for k in NTT_KERNELS) > 0 else None),
             },
-            "proof_words": [int(len(p)) for p in proofs],
             "proof_ms_per_step": [round(x / args.steps, 2) for x in proof_ms] if serial else None,
             "pipelined": pipelined,
-        }
+        })
         if pipelined and valu_instance and valu_instance.get("peak_calibrated"):
             # five instances queued: the same instruction count over the queued time per instance
             pipelined["valu_frac_of_calibrated"] = (valu_instance["insts_per_instance"] / (pipelined["ms_per_instance"] * 1e-3) / 1e9
@@ -849,7 +879,7 @@ def main():
     inst.close()
     io_sharded = None
     shard_sizes = os.environ.get("SIPP_BENCH_IO_SHARD_N", "1024,4096")
-    if shard_sizes not in ("", "0") and not serial:
+    if args.full and shard_sizes not in ("", "0") and not serial:
         io_sharded = {}
         for n_s in [int(x) for x in shard_sizes.split(",")]:
             mine = sipp_amd.shard_ios(load_ios(n_s), world, rank)
@@ -883,7 +913,7 @@ def main():
                                         # what this sharding costs the verifier side (sipp_amd/proof_cost.py, counted from the proofs'
                                         # shapes): 3 * world proofs instead of 3 for the recursive verifier behind verifier_circuit.rs:133-147
                                         "verifier_price": price_vs_world1([a.shape[0] for a in load_ios(n_s)], world, hardened)}
-    if rank == 0:
+    if rank == 0 and args.full:
         out["io_sharded"] = io_sharded
         # secondary, one rank only: the outer plonky2 prover at the reference's circuit configuration (SIPP_BENCH_OUTER_PLONK=0 skips,
         # SIPP_BENCH_OUTER_PLONK=<log2 rows> sizes it; default 2^18)
@@ -893,6 +923,7 @@ def main():
                 out["outer_plonk"] = outer_plonk_leg(local_rank, int(op_bits))
             except Exception as e:                  # noqa: BLE001 -- never allowed to break the main line
                 out["outer_plonk"] = {"error": repr(e)}
+    if rank == 0:
         print(json.dumps(out))
     if dist.is_initialized():
         dist.destroy_process_group()

@@ -27,12 +27,12 @@ line = json.load(open("%s/bench_line.json" % src))
 json.dump(line, open(dst + "_bench_line.json", "w"))
 f, nf = counters("pmc_f")
 w, nw = counters("pmc_w")
-instances = 3      # the PMC passes run bench.py --steps 1 --warmup 1 plus the serial step bench.py appends
+instances = 3      # the PMC passes run bench.py --steps 1 --warmup 1 plus the serial step bench.py --full appends
 NTT = ("ntt_pass_kernel", "lde_column_kernel", "lde_gather_kernel", "lde_mid_kernel", "bitrev_tiled_kernel", "bitrev_cols_kernel",
        "tree_gather_kernel", "tree_mid_kernel", "tree_pass_kernel", "tree_pass_dma_kernel", "tree_fwd_dma_kernel")
 alg = line["roofline_ntt"]["algorithmic_bytes_per_step"]
 traffic = sum(2.0 * f[k]["FETCH_SIZE"] + w[k]["WRITE_SIZE"] for k in NTT) * 1024.0 / instances
-out = {"command": "rocprofv3 --kernel-trace --pmc FETCH_SIZE (and, separately, --pmc WRITE_SIZE) -- python3 bench.py --n %s --steps 1 --warmup 1 --no-cpu-baseline --inflight 1"
+out = {"command": "rocprofv3 --kernel-trace --pmc FETCH_SIZE (and, separately, --pmc WRITE_SIZE) -- python3 bench.py --full --n %s --steps 1 --warmup 1 --no-cpu-baseline --inflight 1"
                   % re.search(r"n(\d+)$", src).group(1),
        "instances_profiled": instances, "fetch_correction": 2.0,
        "kernels": {k: {"launches": nf.get(k, 0), "FETCH_SIZE_kb_sum": f[k]["FETCH_SIZE"], "WRITE_SIZE_kb_sum": w[k]["WRITE_SIZE"],

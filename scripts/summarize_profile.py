@@ -70,7 +70,7 @@ shutil.copy("%s/bench_line.json" % src, dst + "_bench_n128_bench_line.json")
 f, nf = counters("pmc_f")
 w, nw = counters("pmc_w")
 v, nv = counters("pmc_v")
-steps_profiled = 4   # --steps 2 --warmup 1, plus the serial step bench.py appends for kernel_ms_serial
+steps_profiled = 4   # --steps 2 --warmup 1, plus the serial step bench.py --full appends for kernel_ms_serial
 tot = sum(x["SQ_INSTS_VALU"] for x in v.values())
 
 
@@ -119,7 +119,7 @@ except Exception as ex:            # noqa: BLE001
 out = {
     # the AIR variant of the profiled instance (bench.py uses these counters only for a line of the same kinds)
     "kinds": line["config"]["kinds"],
-    "command": "rocprofv3 --kernel-trace --pmc FETCH_SIZE (and, separately, --pmc WRITE_SIZE, --pmc SQ_INSTS_VALU) --output-format csv -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --inflight 1",
+    "command": "rocprofv3 --kernel-trace --pmc FETCH_SIZE (and, separately, --pmc WRITE_SIZE, --pmc SQ_INSTS_VALU) --output-format csv -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --inflight 1",
     "calibration": "scripts/ubench/fetch_calib.hip: 1 GiB read with the leaf kernel's 8-B-per-lane column pattern reports FETCH_SIZE = 524,293.5 KB (exactly 1/2, as MI355X_MICROARCH.md section HBM says for wide coalesced reads); 1 GiB written reports WRITE_SIZE = 1,048,576 KB (exact)",
     "fetch_correction": 2.0,
     "instances_profiled": steps_profiled,
@@ -128,7 +128,7 @@ out = {
     "valu_insts_per_instance": tot / steps_profiled,
     # which code these counters belong to: bench.py refuses them for any other (sipp_amd/build.py source_hash)
     "source_sha256": open("%s/source_sha256.txt" % src).read().strip(),
-    "valu_pass_command": "rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_VALU2 SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_INST_ANY GRBM_GUI_ACTIVE -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --inflight 1",
+    "valu_pass_command": "rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_VALU2 SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_INST_ANY GRBM_GUI_ACTIVE -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --inflight 1",
     # every kernel alone on the chip (counter collection serialises the dispatches)
     "leaf_one_alone": alone(vd, "poseidon_leaves_kernel"),
     "leaf_pair_alone": alone(vd, "poseidon_leaves_pair_kernel"),
@@ -145,7 +145,7 @@ out["ntt"] = {"kernels": {k: {"launches": nf.get(k, 0), "FETCH_SIZE_kb_sum": f[k
               "traffic_bytes_per_instance": sum(2.0 * f[k]["FETCH_SIZE"] + w[k]["WRITE_SIZE"] for k in NTT) * 1024.0 / steps_profiled,
               "note": "all NTT / LDE kernels of one n = 128 instance (4 instances profiled: 1 warm-up + 2 timed steps + the serial step); FETCH_SIZE x2"}
 out["merkle"] = {k: nf.get(k, 0) // steps_profiled for k in ("merkle_subtree_kernel",) if nf.get(k, 0)}
-json.dump({"command": "rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --inflight 1",
+json.dump({"command": "rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --inflight 1",
            "instances_profiled": steps_profiled, "valu_insts_per_instance": tot / steps_profiled,
            "per_kernel": {k: {"SQ_INSTS_VALU_per_instance": x["SQ_INSTS_VALU"] / steps_profiled, "share": x["SQ_INSTS_VALU"] / tot,
                               "launches_per_instance": nv[k] / steps_profiled}

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Concurrency analysis of a rocprofv3 kernel trace of bench.py: for the last timed step, how much wall-clock has
 0 / 1 / 2 / 3 streams busy, and which kernels run while fewer than all three streams are busy.
-usage: timeline.py <run_kernel_trace.csv> [step index, default -3: bench.py appends a serial step and the native chain after the timed steps]"""
+usage: timeline.py <run_kernel_trace.csv> [step index, default -3: bench.py --full appends a serial step and the native chain after the timed steps]"""
 import collections, csv, re, sys
 
 rows = []
@@ -23,7 +23,7 @@ for m in marks:
     cuts.append(i)
 steps = [rows[a:b] for a, b in zip(cuts, cuts[1:] + [len(rows)])]
 print("steps found:", len(steps), [len(s) for s in steps])
-# bench.py appends a serial step and the native chain after the timed steps: analyse the last step that looks like a timed
+# bench.py --full appends a serial step and the native chain after the timed steps: analyse the last step that looks like a timed
 # one (the most common launch count), or the index given on the command line
 if len(sys.argv) > 2:
     st = steps[int(sys.argv[2])]

@@ -34,7 +34,7 @@ def _run_bench(extra_env, nproc, args, timeout=900):
 @pytest.mark.timeout(1200)
 def test_bench_two_ranks_rehearsal_prints_one_whole_job_line():
     out = _run_bench({"SIPP_BENCH_REHEARSAL": "1", "SIPP_BENCH_IO_SHARD_N": "128"}, 2,
-                     ["--gpus", "2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--inflight", "1"])
+                     ["--gpus", "2", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--inflight", "1"])
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout[-3000:]
@@ -62,7 +62,7 @@ def test_bench_four_ranks_rehearsal_shards_the_n1024_instance():
     test_world8_shards_of_the_large_configs and the 8-rank tiling / timing contract runs on the CPU in tests/test_dist_cpu.py).
     No --inflight flag: the default must switch the queue leg off for world > 1."""
     out = _run_bench({"SIPP_BENCH_REHEARSAL": "1", "SIPP_BENCH_IO_SHARD_N": "1024"}, 4,
-                     ["--gpus", "4", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"], timeout=1400)
+                     ["--gpus", "4", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"], timeout=1400)
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout[-3000:]
@@ -160,7 +160,7 @@ def test_bare_bench_starts_its_own_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     env.update(SIPP_BENCH_REHEARSAL="1", SIPP_BENCH_IO_SHARD_N="128", SIPP_BENCH_OTHER_AIR="0", SIPP_BENCH_MAP_G2="0")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                          "--no-cpu-baseline"], capture_output=True, text=True, timeout=1100, cwd=ROOT, env=env)
+                          "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=1100, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout[-3000:]
@@ -179,7 +179,7 @@ def test_bench_timing_contract_over_rccl_with_one_rank():
     env.update(SIPP_BENCH_SINGLE_RANK_GROUP="1", SIPP_BENCH_IO_SHARD_N="128", SIPP_BENCH_OTHER_AIR="0", SIPP_BENCH_MAP_G2="0", SIPP_BENCH_OUTER_PLONK="0",
                HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-                          "--no-cpu-baseline", "--inflight", "1"], capture_output=True, text=True, timeout=800, cwd=ROOT, env=env)
+                          "--full", "--no-cpu-baseline", "--inflight", "1"], capture_output=True, text=True, timeout=800, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
     r = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
     assert r["n_gpus"] == 1 and r["timing_reduction"] == "nccl:cuda"
