@@ -86,7 +86,7 @@ static inline uint64_t gl_root_of_unity(unsigned k) {
 }
 
 static inline uint64_t gl_from_i64(int64_t v) {
-    return v >= 0 ? (uint64_t)v % GL_P : GL_P - ((uint64_t)(-v) % GL_P);
+    return v >= 0 ? (uint64_t)v % GL_P : GL_P - ((0 - (uint64_t)v) % GL_P);   /* -v overflows for INT64_MIN */
 }
 
 /* ---- quadratic extension: a = c0 + c1 * X, X^2 = 7 ---- */

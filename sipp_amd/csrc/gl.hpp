@@ -152,8 +152,8 @@ GL_HD uint64_t root_of_unity(unsigned k) {
     return r;
 }
 
-// signed small integer -> field
-GL_HD uint64_t from_i64(int64_t v) { return v >= 0 ? (uint64_t)v : P - (uint64_t)(-v); }
+// signed integer -> field; the magnitude of a negative v is taken in uint64_t (-v overflows for INT64_MIN)
+GL_HD uint64_t from_i64(int64_t v) { return v >= 0 ? (uint64_t)v : P - (0 - (uint64_t)v); }
 
 #if defined(__HIPCC__)
 #define GL_D __device__ __forceinline__

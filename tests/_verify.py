@@ -77,3 +77,46 @@ def lib_fri_verify(proof, caps, ncols, n_salt, batches, log_n, ofp, och):
                                     C.byref(ch), C.byref(reason))
     assert rc in (0, -9), rc
     return reason.value, bytes(ch)
+
+
+def py_plonk_replay(pf, circ, p, ofp, digest, pis):
+    """the second reading (oracle/py/plonky2_generic.py) on a "SIPPPLK3" proof: the transcript from the proof's caps, the gate constraints
+    at zeta from the OPENED constants and wires (evaluate_gate_constraints), the permutation terms, and per challenge whether the
+    verifier's identity vanishing(zeta) = Z_H(zeta) quotient(zeta) holds"""
+    from oracle.py import plonky2_generic as g2
+    pf = [int(v) for v in pf]
+    R, D, C = p.num_routed_wires, p.max_degree, p.num_challenges
+    K, W, log_n = circ["num_constants"], circ["num_wires"], pf[1]
+    pih = g2.hash_no_pad([int(x) for x in pis])
+    cap_words = 4 << ofp.cap_height
+    wcap, zcap, qcap = (pf[16 + k * cap_words:16 + (k + 1) * cap_words] for k in range(3))
+    ch = g2.Challenger()
+    ch.observe_many([int(x) for x in digest])
+    ch.observe_many(pih)
+    ch.observe_cap([wcap[4 * k:4 * k + 4] for k in range(1 << ofp.cap_height)])
+    betas, gammas = ch.get_n(C), ch.get_n(C)
+    ch.observe_cap([zcap[4 * k:4 * k + 4] for k in range(1 << ofp.cap_height)])
+    alphas = ch.get_n(C)
+    ch.observe_cap([qcap[4 * k:4 * k + 4] for k in range(1 << ofp.cap_height)])
+    zeta = ch.get_ext()
+    npd = _oracle.plonk_num_prods(p)
+    op = pf[16 + 3 * cap_words + 8:]
+    take = iter(range(0, 10 ** 9, 2))
+    ext_at = lambda: (lambda k: g2.Ext(op[k], op[k + 1]))(next(take))
+    c_o = [ext_at() for _ in range(K)]
+    sg_o = [ext_at() for _ in range(R)]
+    w_o = [ext_at() for _ in range(W)]
+    zs_o = [ext_at() for _ in range(C)]
+    pp_o = [ext_at() for _ in range(C * npd)]
+    q_o = [ext_at() for _ in range(C * D)]
+    zn_o = [ext_at() for _ in range(C)]
+    terms = g2.evaluate_gate_constraints(circ["gates"], circ["programs"], circ["num_selectors"], w_o, c_o, pih)
+    van = g2.eval_vanishing_poly_permutation(log_n, zeta, w_o[:R], sg_o, zs_o, zn_o, pp_o, betas, gammas, alphas, D, terms)
+    zeta_n = zeta ** (1 << log_n)
+    holds = []
+    for c in range(C):
+        acc = g2.ext(0)
+        for d in reversed(range(D)):
+            acc = acc * zeta_n + q_o[c * D + d]
+        holds.append(van[c] == (zeta_n - g2.ext(1)) * acc)
+    return holds

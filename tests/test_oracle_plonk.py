@@ -398,41 +398,13 @@ def test_gates_as_data_prove_verify_and_reject():
 
 def test_python_reading_replays_a_proof_with_gates_as_data():
     """the second reading on a "SIPPPLK3" proof: transcript, the gate constraints at zeta from the OPENED constants and wires
-    (oracle/py/plonky2_generic.py evaluate_gate_constraints), the verifier's identity"""
+    (oracle/py/plonky2_generic.py evaluate_gate_constraints), the verifier's identity (tests/_verify.py py_plonk_replay)"""
     from oracle.py import plonky2_generic as g2
+    from tests import _verify
     ps, circ, wires, cs, gate, pis, pih = _synth(6, num_wires=36, num_routed=16)
-    log_n, R, D, C, K, W = 6, 16, 8, 2, 4, 36
+    log_n, R, D, C = 6, 16, 8, 2
     p = _oracle.plonk_params(R, D, C)
     fp = fri(log_n, rate_bits=3, cap_height=1, nq=3, arity=1, fpb=2)
     pf = [int(v) for v in _oracle.plonk_prove_gates(wires, cs, log_n, p, fp, circ, (1, 2, 3, 4), pis)]
-    cap_words = 4 << fp.cap_height
-    wcap, zcap, qcap = (pf[16 + k * cap_words:16 + (k + 1) * cap_words] for k in range(3))
     assert pf[len(pf) - len(pis):] == pis and g2.hash_no_pad(pis) == pih
-    ch = g2.Challenger()
-    ch.observe_many([1, 2, 3, 4])
-    ch.observe_many(pih)
-    ch.observe_cap([wcap[4 * k:4 * k + 4] for k in range(1 << fp.cap_height)])
-    betas, gammas = ch.get_n(C), ch.get_n(C)
-    ch.observe_cap([zcap[4 * k:4 * k + 4] for k in range(1 << fp.cap_height)])
-    alphas = ch.get_n(C)
-    ch.observe_cap([qcap[4 * k:4 * k + 4] for k in range(1 << fp.cap_height)])
-    zeta = ch.get_ext()
-    npd = _oracle.plonk_num_prods(p)
-    op = pf[16 + 3 * cap_words + 8:]
-    take = iter(range(0, 10 ** 9, 2))
-    ext_at = lambda: (lambda k: g2.Ext(op[k], op[k + 1]))(next(take))
-    c_o = [ext_at() for _ in range(K)]
-    sg_o = [ext_at() for _ in range(R)]
-    w_o = [ext_at() for _ in range(W)]
-    zs_o = [ext_at() for _ in range(C)]
-    pp_o = [ext_at() for _ in range(C * npd)]
-    q_o = [ext_at() for _ in range(C * D)]
-    zn_o = [ext_at() for _ in range(C)]
-    terms = g2.evaluate_gate_constraints(circ["gates"], circ["programs"], circ["num_selectors"], w_o, c_o, pih)
-    van = g2.eval_vanishing_poly_permutation(log_n, zeta, w_o[:R], sg_o, zs_o, zn_o, pp_o, betas, gammas, alphas, D, terms)
-    zeta_n = zeta ** (1 << log_n)
-    for c in range(C):
-        acc = g2.ext(0)
-        for d in reversed(range(D)):
-            acc = acc * zeta_n + q_o[c * D + d]
-        assert van[c] == (zeta_n - g2.ext(1)) * acc, c
+    assert _verify.py_plonk_replay(pf, circ, p, fp, (1, 2, 3, 4), pis) == [True] * C
