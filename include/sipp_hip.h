@@ -460,8 +460,15 @@ int sipp_plonk_prove_gates(sipp_ctx *ctx, const uint64_t *d_wires, const uint64_
  *                                                                       bits of index                                      (RandomAccessGenerator)
  *   SIPP_GEN_REDUCING       p = K, W                                    alpha (2), old acc (2), K coefficients, K accumulators (2 each) over
  *                                                                       F[X]/(X^2 - W): acc_i = acc_(i-1) alpha + c_i      (ReducingGenerator)
- *   SIPP_GEN_POSEIDON       p = in, out, sbox                           the permutation of w[in .. in+12): every S-box input of rounds 1 .. 29
- *                                                                       (36 + 22 + 48 wires from sbox) and the 12 outputs  (PoseidonGenerator)
+ *   SIPP_GEN_POSEIDON       p = in, out, sbox                           Poseidon without swap: the permutation of w[in .. in+12), every S-box
+ *                                                                       input of rounds 1 .. 29 (36 + 22 + 48 wires from sbox) and the 12
+ *                                                                       outputs
+ *   SIPP_GEN_POSEIDON_SWAP  p = in, out, sbox, swap, delta              Poseidon with swap (a Merkle-path step): delta_i = w[swap] (w[in+4+i] -
+ *                                                                       w[in+i]) into w[delta+i], i < 4, then the permutation as above of
+ *                                                                       (w[in+i] + delta_i, w[in+4+i] - delta_i, w[in+8 .. in+12)); upstream's
+ *                                                                       layout is in 0, out 12, swap 24, delta 25, sbox 29 = 135 wires
+ *                                                                       (PoseidonGenerator).  The written cells (out, sbox, delta) must not
+ *                                                                       meet the read cells (in, swap)
  * The generators are ROW-LOCAL: values that reach a gate's inputs through copy constraints from another gate's outputs have to be there
  * already (the caller orders its calls by level); d_constants = the circuit's constant columns [num_constants][N] (selectors first: the
  * front of d_constants_sigmas).  SIPP_E_BADARG for a layout that leaves the wire table or an unknown family. */
@@ -473,6 +480,7 @@ int sipp_plonk_prove_gates(sipp_ctx *ctx, const uint64_t *d_wires, const uint64_
 #define SIPP_GEN_RANDOM_ACCESS 6
 #define SIPP_GEN_REDUCING 7
 #define SIPP_GEN_POSEIDON 8
+#define SIPP_GEN_POSEIDON_SWAP 9
 typedef struct {
     uint32_t kind, selector_index, row;
     uint32_t p[5];

@@ -8,9 +8,12 @@
 //
 // Layout: the wire table [num_wires][N] the prover reads next, natural row order; one LANE PER ROW, one launch per generator; a lane whose
 // selector cell does not hold the generator's gate index leaves at once.  Consecutive lanes = consecutive rows of one column: every load
-// and store is coalesced; nothing is staged.  The Poseidon generator is the only one with real arithmetic (the naive 30-round form: the
+// and store is coalesced; nothing is staged.  The Poseidon generators are the only ones with real arithmetic (the naive 30-round form: the
 // S-box INPUTS of every round are wires, so the lazy partial-round form of the hash kernels does not apply): 12 x 12 small-constant
-// products per round on exactly accumulated 32-bit halves, one reduction per output.
+// products per round on exactly accumulated 32-bit halves, one reduction per output.  The partial-round S-box input is element 0 of the
+// naive state; upstream's fast partial rounds change the basis of elements 1 .. 11 only, so they write the same values into those wires.
+// SIPP_GEN_POSEIDON_SWAP is upstream's PoseidonGate with its swap wire (a Merkle-path step): delta_i = swap (in[4+i] - in[i]) goes to its
+// wires, the permutation runs on (in[i] + delta_i, in[4+i] - delta_i, in[8 .. 12)).
 #include "ctx.hpp"
 #include "poseidon_constants.h"
 #include <mutex>
@@ -53,6 +56,32 @@ __device__ __forceinline__ void mds(uint64_t (&s)[12]) {
     }
 #pragma unroll
     for (int r = 0; r < 12; r++) s[r] = out[r];
+}
+
+// the 30 rounds of the naive permutation on s, every S-box input of rounds 1 .. 29 into its wire (sbox + 12 (r - 1) + i, sbox + 36 + (r - 4),
+// sbox + 58 + 12 (r - 26) + i), the outputs into out .. out + 12
+template <class WireRef>
+__device__ __forceinline__ void poseidon_rounds(WireRef& W, uint64_t (&s)[12], uint32_t out, uint32_t sb) {
+#pragma unroll 1
+    for (uint32_t rnd = 0; rnd < 30; rnd++) {
+        const bool full = rnd < 4 || rnd >= 26;
+#pragma unroll
+        for (int l = 0; l < 12; l++) s[l] = gl::add(s[l], w_rc[12 * rnd + l]);
+        if (full) {
+            const uint32_t base = rnd < 4 ? sb + 12 * (rnd - 1) : sb + 58 + 12 * (rnd - 26);
+#pragma unroll
+            for (int l = 0; l < 12; l++) {
+                if (rnd) W(base + l) = s[l];
+                s[l] = pow7(s[l]);
+            }
+        } else {
+            W(sb + 36 + (rnd - 4)) = s[0];
+            s[0] = pow7(s[0]);
+        }
+        mds(s);
+    }
+#pragma unroll
+    for (int l = 0; l < 12; l++) W(out + l) = s[l];
 }
 
 // one generator on one row
@@ -112,30 +141,26 @@ __device__ __forceinline__ void run_generator(uint64_t* wires, const uint64_t* c
         break;
     }
     case SIPP_GEN_POSEIDON: {
-        const uint32_t in = g.p[0], out = g.p[1], sb = g.p[2];
+        uint64_t s[12];
+#pragma unroll
+        for (int l = 0; l < 12; l++) s[l] = W(g.p[0] + l);
+        poseidon_rounds(W, s, g.p[1], g.p[2]);
+        break;
+    }
+    case SIPP_GEN_POSEIDON_SWAP: {
+        const uint32_t in = g.p[0], dl = g.p[4];
         uint64_t s[12];
 #pragma unroll
         for (int l = 0; l < 12; l++) s[l] = W(in + l);
-#pragma unroll 1
-        for (uint32_t rnd = 0; rnd < 30; rnd++) {
-            const bool full = rnd < 4 || rnd >= 26;
+        const uint64_t b = W(g.p[3]);       // any field value: booleanity is the constraints' job
 #pragma unroll
-            for (int l = 0; l < 12; l++) s[l] = gl::add(s[l], w_rc[12 * rnd + l]);
-            if (full) {
-                const uint32_t base = rnd < 4 ? sb + 12 * (rnd - 1) : sb + 58 + 12 * (rnd - 26);
-#pragma unroll
-                for (int l = 0; l < 12; l++) {
-                    if (rnd) W(base + l) = s[l];
-                    s[l] = pow7(s[l]);
-                }
-            } else {
-                W(sb + 36 + (rnd - 4)) = s[0];
-                s[0] = pow7(s[0]);
-            }
-            mds(s);
+        for (int l = 0; l < 4; l++) {
+            const uint64_t d = gl::mul(b, gl::sub(s[4 + l], s[l]));
+            W(dl + l) = d;
+            s[l] = gl::add(s[l], d);
+            s[4 + l] = gl::sub(s[4 + l], d);
         }
-#pragma unroll
-        for (int l = 0; l < 12; l++) W(out + l) = s[l];
+        poseidon_rounds(W, s, g.p[1], g.p[2]);
         break;
     }
     default: break;
@@ -234,6 +259,78 @@ __global__ void __launch_bounds__(64) plonk_witness_level_coop_kernel(LevelArgs 
     if (act) a.wires[(size_t)(out + e) * n + i] = s;
 }
 
+__device__ __forceinline__ bool is_poseidon(uint32_t kind) { return kind == SIPP_GEN_POSEIDON || kind == SIPP_GEN_POSEIDON_SWAP; }
+
+// The same sixteen lanes per row when the circuit has a swap generator or more than one Poseidon layout: every row gets its own
+// Poseidon-family generator (the last one whose selector value it holds; any other match runs on lane 0 first), so one level may mix
+// layouts and the two kinds.  On a swap row lanes 0 .. 7 read their element and its partner, lanes 0 .. 3 store the deltas.  (The
+// per-row parameters cost the single-generator case above ~15 % of its level time, so that case keeps its own kernel.)
+__global__ void __launch_bounds__(64) plonk_witness_level_coop_rows_kernel(LevelArgs a) {
+    __shared__ uint64_t sh[4][12];
+    const uint32_t grp = threadIdx.x >> 4, l = threadIdx.x & 15, k = blockIdx.x * 4 + grp, n = a.n;
+    bool ok = k < a.count;
+    uint32_t i = ok ? a.rows[k] : 0;
+    if (ok && i >= n) {
+        if (l == 0) *a.err = 1;
+        ok = false;
+        i = 0;
+    }
+    int pq = -1;                                              // this row's Poseidon-family generator
+    uint32_t in = 0, out = 0, sb = 0, sw = 0, dl = 0;
+    bool swp = false;
+    if (ok) {
+        for (uint32_t q = 0; q < a.n_gens; q++)               // uniform loop: the parameters are picked, never indexed per lane
+            if (is_poseidon(a.g[q].kind) && a.consts[(size_t)a.g[q].selector_index * n + i] == a.g[q].row) {
+                pq = (int)q;
+                in = a.g[q].p[0], out = a.g[q].p[1], sb = a.g[q].p[2], sw = a.g[q].p[3], dl = a.g[q].p[4];
+                swp = a.g[q].kind == SIPP_GEN_POSEIDON_SWAP;
+            }
+        if (l == 0)
+            for (uint32_t q = 0; q < a.n_gens; q++)
+                if ((int)q != pq && a.consts[(size_t)a.g[q].selector_index * n + i] == a.g[q].row) run_generator(a.wires, a.consts, n, i, a.g[q], a.pih);
+    }
+    const bool is_pos = pq >= 0;
+    if (!__syncthreads_or(is_pos)) return;                    // block-uniform: no Poseidon row among the four
+    const uint32_t e = l < 12 ? l : 0;                        // lanes 12 .. 15 shadow element 0 and never store
+    const bool act = is_pos && l < 12;
+    uint32_t coef[12];                                        // this lane's row of the MDS matrix
+#pragma unroll
+    for (int c = 0; c < 12; c++) coef[c] = w_mds_circ[(c + 12 - e) % 12] + ((e == 0 && c == 0) ? MDS_DIAG0 : 0);
+    uint64_t s = act ? a.wires[(size_t)(in + e) * n + i] : 0;
+    if (swp && l < 8) {                                       // (in[j] + d_j, in[4+j] - d_j), d_j = swap (in[4+j] - in[j])
+        const uint32_t j = l & 3;
+        const uint64_t lhs = a.wires[(size_t)(in + j) * n + i], rhs = a.wires[(size_t)(in + 4 + j) * n + i];
+        const uint64_t d = gl::mul(a.wires[(size_t)sw * n + i], gl::sub(rhs, lhs));
+        s = l < 4 ? gl::add(lhs, d) : gl::sub(rhs, d);
+        if (l < 4) a.wires[(size_t)(dl + j) * n + i] = d;
+    }
+#pragma unroll 1
+    for (uint32_t rnd = 0; rnd < 30; rnd++) {
+        const bool full = rnd < 4 || rnd >= 26;
+        s = gl::add(s, w_rc[12 * rnd + e]);
+        if (full || e == 0) {
+            if (act && rnd) {
+                const uint32_t w = full ? (rnd < 4 ? sb + 12 * (rnd - 1) : sb + 58 + 12 * (rnd - 26)) + e : sb + 36 + (rnd - 4);
+                a.wires[(size_t)w * n + i] = s;
+            }
+            s = pow7(s);
+        }
+        if (l < 12) sh[grp][l] = s;
+        __syncthreads();
+        uint64_t al = 0, ah = 0;
+#pragma unroll
+        for (int c = 0; c < 12; c++) {
+            const uint64_t v = sh[grp][c];
+            al += (uint64_t)(uint32_t)v * coef[c];
+            ah += (v >> 32) * coef[c];
+        }
+        const uint64_t lo = al + (ah << 32);
+        s = gl::reduce96((uint32_t)(ah >> 32) + (lo < al ? 1u : 0u), lo);
+        __syncthreads();
+    }
+    if (act) a.wires[(size_t)(out + e) * n + i] = s;
+}
+
 __global__ void __launch_bounds__(256) plonk_witness_copy_kernel(uint64_t* wires, const uint64_t* src, const uint64_t* dst, uint32_t count,
                                                                  uint64_t cells, int* err) {
     const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
@@ -259,14 +356,24 @@ bool layout_ok(const sipp_plonk_generator& g, uint32_t num_wires, uint32_t num_c
     case SIPP_GEN_RANDOM_ACCESS: return g.p[2] >= 1 && g.p[2] <= 6 && g.p[1] >= 2 + (1u << g.p[2]) + g.p[2] && (uint64_t)g.p[0] * g.p[1] <= nw;
     case SIPP_GEN_REDUCING: return 4ull + 3ull * g.p[0] <= nw;
     case SIPP_GEN_POSEIDON: return (uint64_t)g.p[0] + 12 <= nw && (uint64_t)g.p[1] + 12 <= nw && (uint64_t)g.p[2] + 106 <= nw;
+    case SIPP_GEN_POSEIDON_SWAP: {
+        // written cells (out, sbox, delta) must not meet the read cells (in, swap): the two launch paths read and write in different orders
+        const uint64_t in = g.p[0], out = g.p[1], sb = g.p[2], sw = g.p[3], dl = g.p[4];
+        if (in + 12 > nw || out + 12 > nw || sb + 106 > nw || sw + 1 > nw || dl + 4 > nw) return false;
+        auto meet = [](uint64_t x, uint64_t lx, uint64_t y, uint64_t ly) { return x < y + ly && y < x + lx; };
+        const uint64_t wr[3][2] = {{out, 12}, {sb, 106}, {dl, 4}};
+        for (const auto& w : wr)
+            if (meet(w[0], w[1], in, 12) || meet(w[0], w[1], sw, 1)) return false;
+        return true;
+    }
     default: return false;
     }
 }
 
 const char* gen_name(uint32_t kind) {
     static const char* names[] = {"", "witness_arithmetic", "witness_base_split", "witness_constant", "witness_public_input", "witness_u32",
-                                  "witness_random_access", "witness_reducing", "witness_poseidon"};
-    return kind <= SIPP_GEN_POSEIDON ? names[kind] : "witness";
+                                  "witness_random_access", "witness_reducing", "witness_poseidon", "witness_poseidon_swap"};
+    return kind <= SIPP_GEN_POSEIDON_SWAP ? names[kind] : "witness";
 }
 
 }  // namespace
@@ -281,7 +388,7 @@ static int witness_prepare(sipp_ctx* ctx, const uint64_t* d_wires, const uint64_
         if (!layout_ok(gens[k], num_wires, num_constants))
             return sipp_fail(ctx, SIPP_E_BADARG, "plonk witness: a generator's layout leaves the wire table / the constants, or its family is unknown");
         needs_pih |= gens[k].kind == SIPP_GEN_PUBLIC_INPUT;
-        needs_rc |= gens[k].kind == SIPP_GEN_POSEIDON;
+        needs_rc |= gens[k].kind == SIPP_GEN_POSEIDON || gens[k].kind == SIPP_GEN_POSEIDON_SWAP;
     }
     if (needs_pih && !public_inputs_hash) return sipp_fail(ctx, SIPP_E_BADARG, "plonk witness: a PublicInput generator without the public-inputs hash");
     SIPP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
@@ -343,9 +450,13 @@ extern "C" int sipp_plonk_generate_witness_levels(sipp_ctx* ctx, uint64_t* d_wir
         SIPP_TRY(sipp_table_put(ctx, 101, 0, 0, std::vector<uint64_t>{0}, &t));
         d_err = reinterpret_cast<int*>(t);
     }
-    int pos_gen = -1;
-    for (size_t q = 0; q < n_gens; q++)
-        if (gens[q].kind == SIPP_GEN_POSEIDON) pos_gen = (int)q;      // (two Poseidon layouts in one circuit: the last one gets the lanes)
+    int pos_gen = -1, n_pos = 0;
+    bool any_swap = false;
+    for (size_t q = 0; q < n_gens; q++) {
+        if (gens[q].kind == SIPP_GEN_POSEIDON || gens[q].kind == SIPP_GEN_POSEIDON_SWAP) pos_gen = (int)q, n_pos++;
+        any_swap |= gens[q].kind == SIPP_GEN_POSEIDON_SWAP;
+    }
+    const bool per_row = any_swap || n_pos > 1;     // the lanes go to each row's own Poseidon-family generator
     auto launch_all = [&]() -> hipError_t {
         (void)hipMemsetAsync(d_err, 0, sizeof(int), ctx->stream);
         for (uint32_t l = 0; l < L; l++) {
@@ -357,7 +468,9 @@ extern "C" int sipp_plonk_generate_witness_levels(sipp_ctx* ctx, uint64_t* d_wir
                 for (size_t q = 0; q < n_gens; q++) a.g[q] = gens[q];
                 if (cnt >= COOP_BELOW_ROWS)      // wide level: throughput, one lane per row
                     hipLaunchKernelGGL(plonk_witness_level_kernel, dim3((cnt + 63) / 64), dim3(64), 0, ctx->stream, a);
-                else                             // thin level: latency, sixteen lanes per row
+                else if (per_row)                // thin level: latency, sixteen lanes per row
+                    hipLaunchKernelGGL(plonk_witness_level_coop_rows_kernel, dim3((cnt + 3) / 4), dim3(64), 0, ctx->stream, a);
+                else
                     hipLaunchKernelGGL(plonk_witness_level_coop_kernel, dim3((cnt + 3) / 4), dim3(64), 0, ctx->stream, a, pos_gen);
             }
             const uint32_t c0 = sched->copy_offsets[l], cc = sched->copy_offsets[l + 1] - c0;
