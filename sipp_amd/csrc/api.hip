@@ -3,7 +3,7 @@
 #include <algorithm>
 #include <string>
 
-#include "ctx.hpp"
+#include "commit.hpp"
 #include "host_poseidon.hpp"
 
 int sipp_poseidon_init_constants(sipp_ctx* ctx);  // poseidon.hip
@@ -267,33 +267,11 @@ int sipp_ntt_batch(sipp_ctx* ctx, uint64_t* d_cols, size_t col_stride, size_t nc
 }
 
 // values (natural) -> coeffs (natural) + LDE (leaf order)
-static int lde_from_values(sipp_ctx* ctx, const uint64_t* d_values, uint64_t* d_coeffs, uint64_t* d_lde, size_t ncols,
-                           uint32_t log_n) {
-    const size_t n = (size_t)1 << log_n;
-    const uint32_t rb = ctx->cfg.rate_bits;
-    SIPP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    ArenaScope scope(ctx);   // released on every exit path; the stream is ordered, so later users of the block wait
-    uint64_t* src = const_cast<uint64_t*>(d_values);
-    int rc = sipp_lde_from_values(ctx, d_values, d_coeffs, d_lde, ncols, log_n, rb);
-    if (rc != SIPP_E_UNSUPPORTED) return rc;
-    rc = SIPP_OK;
-    if (d_values == d_coeffs) {
-        uint64_t* tmp = arena_alloc_t<uint64_t>(ctx, n * ncols);
-        if (!tmp) return SIPP_E_NOMEM;
-        SIPP_CHECK_HIP(ctx, hipMemcpyAsync(tmp, d_values, n * ncols * 8, hipMemcpyDeviceToDevice, ctx->stream));
-        src = tmp;
-    }
-    rc = sipp_bitrev_cols(ctx, src, n, d_coeffs, n, log_n, ncols);
-    if (rc == SIPP_OK) rc = sipp_ntt_dit(ctx, d_coeffs, n, log_n, ncols, /*inverse=*/true, NttDiag{});
-    if (rc == SIPP_OK)
-        rc = sipp_ntt_dif(ctx, d_coeffs, n, log_n, d_lde, n << rb, log_n + rb, ncols, false, NttDiag{gl::GEN, 0});
-    return rc;
-}
-
 int sipp_lde_batch(sipp_ctx* ctx, const uint64_t* d_values, uint64_t* d_coeffs, uint64_t* d_lde, size_t ncols,
                    uint32_t log_n) {
     if (!ctx || !d_values || !d_coeffs || !d_lde) return SIPP_E_BADARG;
-    SIPP_TRY(lde_from_values(ctx, d_values, d_coeffs, d_lde, ncols, log_n));
+    SIPP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    SIPP_TRY(commit_lde(ctx, d_values, false, d_coeffs, d_lde, ncols, log_n, ctx->cfg.rate_bits));
     return sipp_sync(ctx);
 }
 
@@ -305,30 +283,19 @@ int sipp_poseidon_leaves(sipp_ctx* ctx, const uint64_t* d_lde, size_t ncols, uin
     return sipp_sync(ctx);
 }
 
-static int read_cap(sipp_ctx* ctx, const uint64_t* d_tree, uint32_t log_leaves, uint64_t* cap_out) {
-    uint32_t ch = std::min(ctx->cfg.cap_height, log_leaves);
-    uint64_t off = 0;
-    for (uint32_t l = 0; l < log_leaves - ch; l++) off += (uint64_t)1 << (log_leaves - l);
-    SIPP_CHECK_HIP(ctx, hipMemcpyAsync(cap_out, d_tree + 4 * off, ((size_t)4 << ch) * 8, hipMemcpyDeviceToHost,
-                                       ctx->stream));
-    return sipp_sync(ctx);
-}
-
 int sipp_merkle_cap(sipp_ctx* ctx, uint64_t* d_tree, uint32_t log_leaves, uint64_t* cap_out) {
     if (!ctx || !d_tree || !cap_out) return SIPP_E_BADARG;
     SIPP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
     SIPP_TRY(sipp_k_merkle_levels(ctx, d_tree, log_leaves, ctx->cfg.cap_height));
-    return read_cap(ctx, d_tree, log_leaves, cap_out);
+    return read_cap(ctx, d_tree, log_leaves, ctx->cfg.cap_height, cap_out);
 }
 
 int sipp_commit_batch(sipp_ctx* ctx, const uint64_t* d_values, uint64_t* d_coeffs, uint64_t* d_lde, uint64_t* d_tree,
                       size_t ncols, uint32_t log_n, uint64_t* cap_out) {
     if (!ctx || !d_values || !d_coeffs || !d_lde || !d_tree || !cap_out) return SIPP_E_BADARG;
-    const uint32_t log_m = log_n + ctx->cfg.rate_bits;
-    SIPP_TRY(lde_from_values(ctx, d_values, d_coeffs, d_lde, ncols, log_n));
-    SIPP_TRY(sipp_k_poseidon_leaves(ctx, d_lde, (size_t)1 << log_m, ncols, log_m, d_tree));
-    SIPP_TRY(sipp_k_merkle_levels(ctx, d_tree, log_m, ctx->cfg.cap_height));
-    return read_cap(ctx, d_tree, log_m, cap_out);
+    SIPP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    return commit_batch(ctx, CommitParams{ctx->cfg.rate_bits, ctx->cfg.cap_height}, d_values, false, d_coeffs, d_lde, d_tree, ncols, log_n,
+                        cap_out);
 }
 
 int sipp_host_poseidon_permute(uint64_t* states, size_t n, int impl) {

@@ -156,12 +156,18 @@ static inline void* arena_alloc(sipp_ctx* ctx, size_t bytes) {
     if (ctx->arena_off > ctx->arena_peak) ctx->arena_peak = ctx->arena_off;
     return ctx->arena + off;
 }
-// releases everything allocated after its construction on EVERY exit path (error returns included)
+// releases everything allocated after its construction on EVERY exit path (error returns included).  Without `sync` the block goes
+// back while kernels may still use it: enough where every later user is ordered behind them on ctx->stream; a scope whose kernels also
+// read HOST memory of the enclosing function (or that spans a whole proof) waits for the stream first.
 struct ArenaScope {
     sipp_ctx* ctx;
     ArenaMark mark;
-    explicit ArenaScope(sipp_ctx* c) : ctx(c), mark(arena_mark(c)) {}
-    ~ArenaScope() { arena_release(ctx, mark); }
+    bool sync;
+    explicit ArenaScope(sipp_ctx* c, bool sync_first = false) : ctx(c), mark(arena_mark(c)), sync(sync_first) {}
+    ~ArenaScope() {
+        if (sync) (void)hipStreamSynchronize(ctx->stream);
+        arena_release(ctx, mark);
+    }
     ArenaScope(const ArenaScope&) = delete;
     ArenaScope& operator=(const ArenaScope&) = delete;
 };

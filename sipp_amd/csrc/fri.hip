@@ -10,17 +10,6 @@
 
 #include "prover.hpp"
 
-static size_t tree_words(uint32_t log_leaves) { return ((size_t)8 << log_leaves); }  // 2 * leaves * 4
-
-static int read_cap(sipp_ctx* ctx, const uint64_t* d_tree, uint32_t log_leaves, uint32_t cap_height, uint64_t* cap_host) {
-    const uint32_t ch = std::min(cap_height, log_leaves);
-    uint64_t off = 0;
-    for (uint32_t l = 0; l < log_leaves - ch; l++) off += (uint64_t)1 << (log_leaves - l);
-    SIPP_CHECK_HIP(ctx, hipMemcpyAsync(cap_host, d_tree + 4 * off, ((size_t)4 << ch) * 8, hipMemcpyDeviceToHost, ctx->stream));
-    SIPP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return SIPP_OK;
-}
-
 size_t sipp_fri_core_words(const FriParamsDev& p, uint32_t log_n, const uint32_t* leaf_words, int n_oracles) {
     const uint32_t log_m = log_n + p.rate_bits;
     const size_t cap = (size_t)4 << p.cap_height;
@@ -215,12 +204,8 @@ extern "C" {
 
 void sipp_fri_const_arity(sipp_fri_params* p, uint32_t arity_bits, uint32_t final_poly_bits, uint32_t degree_bits) {
     if (!p) return;
-    p->n_rounds = 0;
-    while (degree_bits > final_poly_bits && degree_bits + p->rate_bits - arity_bits >= p->cap_height && degree_bits >= arity_bits &&
-           p->n_rounds < SIPP_FRI_MAX_ROUNDS) {
-        p->arity_bits[p->n_rounds++] = arity_bits;
-        degree_bits -= arity_bits;
-    }
+    p->n_rounds = sipp_fri_const_arity_rounds(degree_bits, p->rate_bits, p->cap_height, arity_bits, final_poly_bits);
+    for (uint32_t r = 0; r < p->n_rounds; r++) p->arity_bits[r] = arity_bits;
 }
 
 int sipp_commit_batch_ex(sipp_ctx* ctx, const uint64_t* d_in, int from_coeffs, uint64_t* d_coeffs, uint64_t* d_lde, uint64_t* d_tree,
@@ -230,49 +215,18 @@ int sipp_commit_batch_ex(sipp_ctx* ctx, const uint64_t* d_in, int from_coeffs, u
     if (rate_bits < 1 || rate_bits > 3 || cap_height > 8 || (n_salt != 0 && (n_salt != SIPP_SALT_SIZE || !d_salt)))
         return sipp_fail(ctx, SIPP_E_UNSUPPORTED, "commit_batch_ex: blowup 2 / 4 / 8, cap height <= 8, salt 0 or 4 columns");
     SIPP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    const uint32_t log_m = log_n + rate_bits;
-    const size_t n = (size_t)1 << log_n, m = (size_t)1 << log_m;
-    ArenaScope scope(ctx);
-    int rc;
-    if (from_coeffs) {
-        if (d_in != d_coeffs) SIPP_CHECK_HIP(ctx, hipMemcpyAsync(d_coeffs, d_in, ncols * n * 8, hipMemcpyDeviceToDevice, ctx->stream));
-        rc = sipp_lde_from_coeffs(ctx, d_coeffs, d_lde, ncols, log_n, rate_bits);
-        if (rc == SIPP_E_UNSUPPORTED) rc = sipp_ntt_dif(ctx, d_coeffs, n, log_n, d_lde, m, log_m, ncols, false, NttDiag{gl::GEN, 0});
-    } else {
-        rc = d_in != d_coeffs ? sipp_lde_from_values(ctx, d_in, d_coeffs, d_lde, ncols, log_n, rate_bits) : SIPP_E_UNSUPPORTED;
-        if (rc == SIPP_E_UNSUPPORTED) {
-            const uint64_t* src = d_in;
-            if (d_in == d_coeffs) {
-                uint64_t* tmp = arena_alloc_t<uint64_t>(ctx, n * ncols);
-                if (!tmp) return SIPP_E_NOMEM;
-                SIPP_CHECK_HIP(ctx, hipMemcpyAsync(tmp, d_in, n * ncols * 8, hipMemcpyDeviceToDevice, ctx->stream));
-                src = tmp;
-            }
-            rc = sipp_bitrev_cols(ctx, src, n, d_coeffs, n, log_n, ncols);
-            if (rc == SIPP_OK) rc = sipp_ntt_dit(ctx, d_coeffs, n, log_n, ncols, true, NttDiag{});
-            if (rc == SIPP_OK) rc = sipp_ntt_dif(ctx, d_coeffs, n, log_n, d_lde, m, log_m, ncols, false, NttDiag{gl::GEN, 0});
-        }
-    }
-    // salt columns: natural LDE order in, leaf order (= bit-reversed rows) behind the polynomial columns
-    if (rc == SIPP_OK && n_salt) rc = sipp_bitrev_cols(ctx, d_salt, m, d_lde + ncols * m, m, log_m, n_salt);
-    if (rc == SIPP_OK) rc = sipp_k_poseidon_leaves(ctx, d_lde, m, ncols + n_salt, log_m, d_tree);
-    if (rc == SIPP_OK) rc = sipp_k_merkle_levels(ctx, d_tree, log_m, cap_height);
-    if (rc == SIPP_OK) rc = read_cap(ctx, d_tree, log_m, cap_height, cap_out);
-    else (void)hipStreamSynchronize(ctx->stream);
+    const int rc = commit_batch(ctx, CommitParams{rate_bits, cap_height, d_salt, n_salt}, d_in, from_coeffs != 0, d_coeffs, d_lde, d_tree, ncols,
+                                log_n, cap_out);
+    if (rc != SIPP_OK) (void)hipStreamSynchronize(ctx->stream);   // the caller may free its buffers after a failure as well
     return rc;
 }
 
 size_t sipp_fri_proof_size(const sipp_oracle* oracles, size_t n_oracles, const sipp_fri_batch* batches, size_t n_batches,
                            uint32_t log_n, const sipp_fri_params* p) {
     if (!oracles || !batches || !p || n_oracles == 0 || n_oracles > 8 || n_batches == 0) return 0;
-    FriParamsDev fp;
-    fp.rate_bits = p->rate_bits; fp.cap_height = p->cap_height; fp.pow_bits = p->pow_bits; fp.num_queries = p->num_queries;
-    fp.pow_rule = p->pow_rule;
+    const FriParamsDev fp(*p);
     uint32_t sum = 0;
-    for (uint32_t r = 0; r < p->n_rounds && r < SIPP_FRI_MAX_ROUNDS; r++) {
-        fp.arity_bits.push_back(p->arity_bits[r]);
-        sum += p->arity_bits[r];
-    }
+    for (uint32_t ab : fp.arity_bits) sum += ab;
     if (sum > log_n) return 0;
     uint32_t lw[8];
     for (size_t o = 0; o < n_oracles; o++) lw[o] = oracles[o].n_polys + oracles[o].n_salt;
@@ -299,24 +253,9 @@ int sipp_fri_prove_openings(sipp_ctx* ctx, const sipp_oracle* oracles, size_t n_
                 return sipp_fail(ctx, SIPP_E_BADARG, "fri: polynomial range outside its oracle");
         }
     const size_t n = (size_t)1 << log_n, m = n << p->rate_bits;
-    FriParamsDev fp;
-    fp.rate_bits = p->rate_bits; fp.cap_height = p->cap_height; fp.pow_bits = p->pow_bits; fp.num_queries = p->num_queries;
-    fp.pow_rule = p->pow_rule;
-    for (uint32_t r = 0; r < p->n_rounds; r++) fp.arity_bits.push_back(p->arity_bits[r]);
-    host::Challenger ch;
-    memcpy(ch.state, chs->state, sizeof ch.state);
-    memcpy(ch.in_buf, chs->in_buf, sizeof ch.in_buf);
-    memcpy(ch.out_buf, chs->out_buf, sizeof ch.out_buf);
-    ch.n_in = (uint32_t)chs->n_in;
-    ch.n_out = (uint32_t)chs->n_out;
-    struct Release {
-        sipp_ctx* c;
-        ArenaMark mk;
-        ~Release() {
-            (void)hipStreamSynchronize(c->stream);
-            arena_release(c, mk);
-        }
-    } release{ctx, arena_mark(ctx)};
+    const FriParamsDev fp(*p);
+    host::Challenger ch(*chs);
+    ArenaScope scope(ctx, /*sync_first=*/true);
     size_t pos = 0;
     uint64_t* pf = proof_out;
     {
@@ -370,16 +309,7 @@ int sipp_fri_prove_openings(sipp_ctx* ctx, const sipp_oracle* oracles, size_t n_
             for (uint32_t c = rg.col_begin; c < rg.col_end; c++) cols.push_back(oracles[rg.oracle].d_coeffs + (size_t)c * n);
         }
         std::vector<uint32_t> apow(6 * k + 6);
-        gl::E2 ap = gl::e2(1);
-        for (size_t c = 0; c < k; c++) {
-            const uint64_t comp[2] = {ap.c0, ap.c1};
-            for (int q = 0; q < 2; q++) {
-                apow[6 * c + 3 * q] = (uint32_t)comp[q] & 0x3FFFFFu;
-                apow[6 * c + 3 * q + 1] = (uint32_t)(comp[q] >> 22) & 0x3FFFFFu;
-                apow[6 * c + 3 * q + 2] = (uint32_t)(comp[q] >> 44);
-            }
-            ap = gl::mul(ap, alpha);
-        }
+        const gl::E2 ap = sipp_pow_limbs(alpha, k, apow.data());
         const uint64_t** d_cols = reinterpret_cast<const uint64_t**>(arena_alloc(ctx, (k + 1) * sizeof(uint64_t*)));
         uint32_t* d_apow = arena_alloc_t<uint32_t>(ctx, apow.size());
         if (!d_cols || !d_apow) return SIPP_E_NOMEM;
@@ -399,11 +329,7 @@ int sipp_fri_prove_openings(sipp_ctx* ctx, const sipp_oracle* oracles, size_t n_
     pf[2] = flen;
     if (pos != total) return sipp_fail(ctx, SIPP_E_BUFSZ, "internal: opening proof length mismatch");
     *proof_len = pos;
-    memcpy(chs->state, ch.state, sizeof ch.state);
-    memcpy(chs->in_buf, ch.in_buf, sizeof ch.in_buf);
-    memcpy(chs->out_buf, ch.out_buf, sizeof ch.out_buf);
-    chs->n_in = ch.n_in;
-    chs->n_out = ch.n_out;
+    ch.store(chs);
     return SIPP_OK;
 }
 

@@ -229,8 +229,8 @@ struct Acc160 {
     }
 };
 
-// c -> limbs for Acc6::mac
-GL_D void limbs3(uint32_t (&o)[3], uint64_t c) {
+// c -> limbs for Acc6::mac (the host builds the tables of constant weights with it)
+GL_HD void limbs3(uint32_t (&o)[3], uint64_t c) {
     o[0] = (uint32_t)c & 0x3FFFFFu;
     o[1] = (uint32_t)(c >> 22) & 0x3FFFFFu;
     o[2] = (uint32_t)(c >> 44);

@@ -4,7 +4,9 @@
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
+#include <string.h>
 
+#include "../../include/sipp_hip.h"
 #include "gl.hpp"
 #include "host_poseidon.hpp"
 
@@ -58,6 +60,20 @@ struct Challenger {
         r.c0 = get();
         r.c1 = get();
         return r;
+    }
+    // the transcript as the plain data of the C ABI, both ways (a plain copy: the callers check n_in / n_out of foreign states)
+    explicit Challenger(const sipp_challenger& c) : n_in((uint32_t)c.n_in), n_out((uint32_t)c.n_out) {
+        memcpy(state, c.state, sizeof state);
+        memcpy(in_buf, c.in_buf, sizeof in_buf);
+        memcpy(out_buf, c.out_buf, sizeof out_buf);
+    }
+    Challenger() = default;
+    void store(sipp_challenger* c) const {
+        memcpy(c->state, state, sizeof state);
+        memcpy(c->in_buf, in_buf, sizeof in_buf);
+        memcpy(c->out_buf, out_buf, sizeof out_buf);
+        c->n_in = n_in;
+        c->n_out = n_out;
     }
 };
 

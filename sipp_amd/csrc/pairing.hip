@@ -185,17 +185,6 @@ __device__ __forceinline__ void coop_sums_and_fold(T6& r, CoopScratch& sc) {
     }
     __syncthreads();
 }
-__device__ __forceinline__ void coop_mul(T6& r, const T6& a, const T6& b, CoopScratch& sc) {  // r may alias a or b
-    const uint32_t l = threadIdx.x;
-    if (l < 108) karatsuba_part(sc.part[l], a.c[(l / 3) / 6], b.c[(l / 3) % 6], l % 3);
-    __syncthreads();
-    if (l < 72) {
-        const uint32_t k = l >> 1, comp = l & 1;
-        (comp ? sc.prod[k].c1 : sc.prod[k].c0) = karatsuba_join(&sc.part[3 * k], comp);
-    }
-    __syncthreads();
-    coop_sums_and_fold(r, sc);
-}
 // the final exponentiation runs as ONE wave (its barriers cost nothing then; measured 1.93 ms against 2.19 ms with the
 // 128-thread products and cyclotomic squarings, whose additions on six lanes outweigh the saved products)
 struct CoopScratch64 {

@@ -542,6 +542,50 @@ struct PlonkExtra {
 int plonk_prove_impl(sipp_ctx* ctx, const uint64_t* d_wires, const uint64_t* d_sigmas, uint32_t log_n, const sipp_plonk_params* p,
                      const sipp_fri_params* fp, const uint64_t circuit_digest[4], const uint64_t public_inputs_hash[4], const PlonkExtra& ex,
                      uint64_t* proof_out, size_t proof_cap, size_t* proof_len);
+
+// The opening set of a plonk proof, for the prover and the two size functions: four oracles -- constants_sigmas (the sigmas alone
+// without a circuit) | wires | zs_partial_products | quotient chunks -- all opened at zeta, the C running products Z again at g zeta.
+// m = chunks of routed wires (check()).
+struct PlonkLayout {
+    uint32_t ncols[4];
+    sipp_poly_range at_zeta[4], at_gzeta[1];
+    size_t header_words;      // 8, or 16 with the gates as data ("SIPPPLK3")
+    PlonkLayout(const sipp_plonk_params* p, uint32_t m, const sipp_plonk_circuit* circ) {
+        const uint32_t R = p->num_routed_wires, C = p->num_challenges;
+        const uint32_t nc[4] = {(circ ? circ->num_constants : 0) + R, circ ? circ->num_wires : R, C * m, C * p->max_degree};
+        for (uint32_t o = 0; o < 4; o++) {
+            ncols[o] = nc[o];
+            at_zeta[o] = sipp_poly_range{o, 0, nc[o]};
+        }
+        at_gzeta[0] = sipp_poly_range{2, 0, C};
+        header_words = circ ? 16 : 8;
+    }
+    void batches(gl::E2 zeta, gl::E2 gzeta, sipp_fri_batch out[2]) const {
+        out[0] = sipp_fri_batch{{zeta.c0, zeta.c1}, 4, at_zeta};
+        out[1] = sipp_fri_batch{{gzeta.c0, gzeta.c1}, 1, at_gzeta};
+    }
+    // u64 words in front of the opening proof (header, the three caps the proof carries) and of the opening proof itself (0: the
+    // FRI parameters do not fit the degree)
+    size_t head_words(uint32_t log_n, const sipp_fri_params* fp) const {
+        return header_words + 3 * ((size_t)4 << std::min(fp->cap_height, log_n + fp->rate_bits));
+    }
+    size_t opening_words(uint32_t log_n, const sipp_fri_params* fp) const {
+        sipp_oracle oracles[4];
+        for (int o = 0; o < 4; o++) oracles[o] = sipp_oracle{nullptr, nullptr, nullptr, ncols[o], 0};
+        sipp_fri_batch b[2];
+        batches(gl::e2(0), gl::e2(0), b);
+        return sipp_fri_proof_size(oracles, 4, b, 2, log_n, fp);
+    }
+};
+// words of a whole proof; 0 when check() refuses the parameters or the FRI parameters do not fit
+size_t plonk_proof_words(uint32_t log_n, const sipp_plonk_params* p, const sipp_fri_params* fp, const sipp_plonk_circuit* circ,
+                         uint32_t n_public_inputs) {
+    uint32_t log_d, m;
+    if (!fp || check(nullptr, p, log_n, &log_d, &m) != SIPP_OK) return 0;
+    const PlonkLayout lay(p, m, circ);
+    const size_t op = lay.opening_words(log_n, fp);
+    return op ? lay.head_words(log_n, fp) + op + n_public_inputs : 0;
+}
 }  // namespace
 
 int sipp_plonk_perm_prove(sipp_ctx* ctx, const uint64_t* d_wires, const uint64_t* d_sigmas, uint32_t log_n, const sipp_plonk_params* p,
@@ -584,7 +628,8 @@ int plonk_prove_impl(sipp_ctx* ctx, const uint64_t* d_wires, const uint64_t* d_s
     const uint32_t R = p->num_routed_wires, D = p->max_degree, C = p->num_challenges, nz = C * m;
     const size_t n = (size_t)1 << log_n, M = n << fp->rate_bits, cap_n = (size_t)1 << std::min(fp->cap_height, log_n + fp->rate_bits);
     const uint32_t K = ex.circ ? ex.circ->num_constants : 0, Wn = ex.circ ? ex.circ->num_wires : R;
-    const uint32_t ncols[4] = {K + R, Wn, nz, C * D};
+    const PlonkLayout lay(p, m, ex.circ);
+    const uint32_t* ncols = lay.ncols;
     const uint64_t* d_sigma_vals = d_sigmas + (size_t)K * n;      // the sigmas behind the constant columns
     uint64_t *co[4], *lde[4], *tree[4];
     const sipp_oracle* pre[4] = {ex.sigmas_oracle, ex.wires_oracle, nullptr, nullptr};
@@ -597,7 +642,7 @@ int plonk_prove_impl(sipp_ctx* ctx, const uint64_t* d_wires, const uint64_t* d_s
         }
         co[o] = arena_alloc_t<uint64_t>(ctx, (size_t)ncols[o] * n);
         lde[o] = arena_alloc_t<uint64_t>(ctx, (size_t)ncols[o] * M);
-        tree[o] = arena_alloc_t<uint64_t>(ctx, 2 * M * 4);
+        tree[o] = arena_alloc_t<uint64_t>(ctx, tree_words(log_n + fp->rate_bits));
         if (!co[o] || !lde[o] || !tree[o]) return SIPP_E_NOMEM;
     }
     std::vector<uint64_t> caps(4 * cap_n * 4);
@@ -633,20 +678,14 @@ int plonk_prove_impl(sipp_ctx* ctx, const uint64_t* d_wires, const uint64_t* d_s
     const gl::E2 zeta = ch.get_ext();
     sipp_oracle oracles[4];
     for (int o = 0; o < 4; o++) oracles[o] = sipp_oracle{co[o], lde[o], tree[o], ncols[o], 0};
-    const sipp_poly_range r0[4] = {{0, 0, ncols[0]}, {1, 0, ncols[1]}, {2, 0, nz}, {3, 0, C * D}}, r1[1] = {{2, 0, C}};
-    const gl::E2 gz = gl::scale(zeta, gl::root_of_unity(log_n));
-    sipp_fri_batch batches[2] = {{{zeta.c0, zeta.c1}, 4, r0}, {{gz.c0, gz.c1}, 1, r1}};
-    const size_t op_cap = sipp_fri_proof_size(oracles, 4, batches, 2, log_n, fp);
-    const size_t hw = ex.circ ? 16 : 8;                          // header words
-    const size_t head = hw + 3 * cap_n * 4, tail = ex.v2 ? ex.n_public_inputs : 0;
+    sipp_fri_batch batches[2];
+    lay.batches(zeta, gl::scale(zeta, gl::root_of_unity(log_n)), batches);
+    const size_t op_cap = lay.opening_words(log_n, fp);
+    const size_t hw = lay.header_words, head = lay.head_words(log_n, fp), tail = ex.v2 ? ex.n_public_inputs : 0;
     if (op_cap == 0) return sipp_fail(ctx, SIPP_E_BADARG, "plonk: FRI parameters do not fit the degree");
     if (proof_cap < head + op_cap + tail) return sipp_fail(ctx, SIPP_E_BUFSZ, "plonk: proof buffer too small (see sipp_plonk_perm_proof_size)");
     sipp_challenger cs{};
-    memcpy(cs.state, ch.state, sizeof cs.state);
-    memcpy(cs.in_buf, ch.in_buf, sizeof cs.in_buf);
-    memcpy(cs.out_buf, ch.out_buf, sizeof cs.out_buf);
-    cs.n_in = ch.n_in;
-    cs.n_out = ch.n_out;
+    ch.store(&cs);
     size_t op_len = 0;
     SIPP_TRY(sipp_fri_prove_openings(ctx, oracles, 4, batches, 2, log_n, fp, &cs, proof_out + head, proof_cap - head - tail, &op_len));
     if (ex.circ) {
@@ -668,35 +707,14 @@ int plonk_prove_impl(sipp_ctx* ctx, const uint64_t* d_wires, const uint64_t* d_s
 }  // namespace
 
 size_t sipp_plonk_perm_proof_size(uint32_t log_n, const sipp_plonk_params* p, const sipp_fri_params* fp) {
-    // the bounds of check(): sizes below are u32 products
-    if (!p || !fp || p->max_degree < 2 || p->max_degree > 64 || (p->max_degree & (p->max_degree - 1)) || p->num_routed_wires == 0 ||
-        p->num_challenges == 0 || p->num_challenges > MAX_CH || (p->num_routed_wires + p->max_degree - 1) / p->max_degree > MAX_CHUNKS ||
-        log_n < 1 || log_n > 24)
-        return 0;
-    const uint32_t R = p->num_routed_wires, D = p->max_degree, C = p->num_challenges, nz = C * ((R + D - 1) / D);
-    const size_t cap_n = (size_t)1 << std::min(fp->cap_height, log_n + fp->rate_bits);
-    sipp_oracle oracles[4] = {{nullptr, nullptr, nullptr, R, 0}, {nullptr, nullptr, nullptr, R, 0}, {nullptr, nullptr, nullptr, nz, 0},
-                              {nullptr, nullptr, nullptr, C * D, 0}};
-    const sipp_poly_range r0[4] = {{0, 0, R}, {1, 0, R}, {2, 0, nz}, {3, 0, C * D}}, r1[1] = {{2, 0, C}};
-    sipp_fri_batch batches[2] = {{{0, 0}, 4, r0}, {{0, 0}, 1, r1}};
-    const size_t op = sipp_fri_proof_size(oracles, 4, batches, 2, log_n, fp);
-    return op ? 8 + 3 * cap_n * 4 + op : 0;
+    return plonk_proof_words(log_n, p, fp, nullptr, 0);
 }
 
 size_t sipp_plonk_gates_proof_size(uint32_t log_n, const sipp_plonk_params* p, const sipp_fri_params* fp, const sipp_plonk_circuit* c,
                                    uint32_t n_public_inputs) {
-    if (!p || !fp || !c || p->max_degree < 2 || p->max_degree > 64 || (p->max_degree & (p->max_degree - 1)) || p->num_routed_wires == 0 ||
-        p->num_challenges == 0 || p->num_challenges > MAX_CH || (p->num_routed_wires + p->max_degree - 1) / p->max_degree > MAX_CHUNKS ||
-        log_n < 1 || log_n > 24 || c->num_wires < p->num_routed_wires || c->num_wires > 4096 || c->num_constants > 1024)
-        return 0;
-    const uint32_t R = p->num_routed_wires, D = p->max_degree, C = p->num_challenges, nz = C * ((R + D - 1) / D);
-    const size_t cap_n = (size_t)1 << std::min(fp->cap_height, log_n + fp->rate_bits);
-    sipp_oracle oracles[4] = {{nullptr, nullptr, nullptr, c->num_constants + R, 0}, {nullptr, nullptr, nullptr, c->num_wires, 0},
-                              {nullptr, nullptr, nullptr, nz, 0}, {nullptr, nullptr, nullptr, C * D, 0}};
-    const sipp_poly_range r0[4] = {{0, 0, c->num_constants + R}, {1, 0, c->num_wires}, {2, 0, nz}, {3, 0, C * D}}, r1[1] = {{2, 0, C}};
-    sipp_fri_batch batches[2] = {{{0, 0}, 4, r0}, {{0, 0}, 1, r1}};
-    const size_t op = sipp_fri_proof_size(oracles, 4, batches, 2, log_n, fp);
-    return op ? 16 + 3 * cap_n * 4 + op + n_public_inputs : 0;
+    // (the circuit's own bounds: circuit_check)
+    if (!c || !p || c->num_wires < p->num_routed_wires || c->num_wires > 4096 || c->num_constants > 1024) return 0;
+    return plonk_proof_words(log_n, p, fp, c, n_public_inputs);
 }
 
 int sipp_plonk_prove_gates(sipp_ctx* ctx, const uint64_t* d_wires, const uint64_t* d_constants_sigmas, const sipp_oracle* wires_oracle,

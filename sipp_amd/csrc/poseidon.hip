@@ -329,7 +329,7 @@ int sipp_k_pow_search(sipp_ctx* ctx, const uint64_t state[12], const uint64_t* i
     if (pow_bits == 0) { *witness = 0; return SIPP_OK; }
     if (pow_bits > 32 || n_in > 7 || (resp_word != 0 && resp_word != 7))
         return sipp_fail(ctx, SIPP_E_UNSUPPORTED, "pow_search: unsupported parameters");
-    ArenaMark mk = arena_mark(ctx);
+    ArenaScope scope(ctx);
     unsigned long long* d_res = arena_alloc_t<unsigned long long>(ctx, 1);
     if (!d_res) return SIPP_E_NOMEM;
     PowArgs a;
@@ -355,7 +355,6 @@ int sipp_k_pow_search(sipp_ctx* ctx, const uint64_t state[12], const uint64_t* i
         SIPP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
         if (h_res != ~0ull) break;
     }
-    arena_release(ctx, mk);
     if (h_res == ~0ull) return sipp_fail(ctx, SIPP_E_UNSUPPORTED, "pow_search: no witness found");
     *witness = (uint64_t)h_res;
     return SIPP_OK;

@@ -1140,36 +1140,10 @@ __global__ void fri_fold_kernel(const uint64_t* __restrict__ in, size_t len_in, 
 // =====================================================================================================
 // query gathers
 // =====================================================================================================
-__global__ void gather_rows_kernel(const uint64_t* __restrict__ lde, size_t m, uint32_t ncols, const uint32_t* __restrict__ idx,
-                                   uint64_t* __restrict__ out) {
-    const uint32_t q = blockIdx.y;
-    const size_t x = idx[q];
-    for (uint32_t c = blockIdx.x * blockDim.x + threadIdx.x; c < ncols; c += gridDim.x * blockDim.x)
-        out[(size_t)q * ncols + c] = lde[(size_t)c * m + x];
-}
-
-// siblings of leaf idx[q] >> shift from level 0 up to (log_leaves - cap) levels; out [q][nsib][4]
-__global__ void gather_siblings_kernel(const uint64_t* __restrict__ tree, uint32_t log_leaves, uint32_t nsib, uint32_t shift,
-                                       const uint32_t* __restrict__ idx, uint64_t* __restrict__ out) {
-    const uint32_t q = blockIdx.x;
-    const uint32_t l = threadIdx.x >> 2, w = threadIdx.x & 3;
-    if (l >= nsib) return;
-    size_t off = 0;
-    for (uint32_t k = 0; k < l; k++) off += (size_t)1 << (log_leaves - k);
-    size_t node = (((size_t)idx[q] >> shift) >> l) ^ 1;
-    out[((size_t)q * nsib + l) * 4 + w] = tree[(off + node) * 4 + w];
-}
-
-// FRI round leaf: 2^ab ext values (interleaved c0, c1) at leaf index idx[q] >> shift; vals: [2][len] leaf order
-__global__ void gather_fri_leaf_kernel(const uint64_t* __restrict__ vals, size_t len, uint32_t shift, uint32_t ab,
-                                       const uint32_t* __restrict__ idx, uint64_t* __restrict__ out) {
-    const uint32_t q = blockIdx.x, t = threadIdx.x;  // 2 * arity threads
-    const size_t leaf = (size_t)idx[q] >> shift;
-    out[((size_t)q << (ab + 1)) + t] = vals[(size_t)(t & 1) * len + (leaf << ab) + (t >> 1)];
-}
-
-// every gather of a query phase in ONE launch: block (q, task) copies what one of the three kernels above copies for query q
-// (a dozen launches of a few microseconds each were 0.2 ms of launch gaps in every proof's FRI tail)
+// every gather of a query phase in ONE launch: block (q, task) copies for query q the row of an oracle (out [q][ncols]), the siblings of
+// leaf idx[q] >> shift from level 0 up (out [q][nsib][4]), or the FRI round leaf at idx[q] >> shift: 2^ab extension values of
+// vals [2][len] in leaf order, interleaved (c0, c1).  (One launch per gather -- a dozen of a few microseconds each -- was 0.2 ms of
+// launch gaps in every proof's FRI tail.)
 __global__ void __launch_bounds__(256) gather_tasks_kernel(const QueryGatherTask* __restrict__ tasks, const uint32_t* __restrict__ idx) {
     const QueryGatherTask t = tasks[blockIdx.y];
     const uint32_t q = blockIdx.x;
@@ -1235,36 +1209,6 @@ int sipp_k_z_columns(sipp_ctx* ctx, const air_spec_t* a, const uint64_t* d_trace
     return SIPP_OK;
 }
 
-// natural-order NTT on the host (sizes up to 2 R = 1024: the value-periodic columns below): out[i] = sum_j a[j] w^(i j), w a primitive
-// 2^log_n-th root (inverse: w^-1 and the factor 1 / n)
-static void host_ntt(uint64_t* a, uint32_t log_n, bool inverse) {
-    const size_t n = (size_t)1 << log_n;
-    for (size_t i = 0; i < n; i++) {
-        const size_t j = gl::bitrev((uint32_t)i, log_n);
-        if (i < j) std::swap(a[i], a[j]);
-    }
-    uint64_t root = gl::root_of_unity(log_n);
-    if (inverse) root = gl::inv(root);
-    for (uint32_t s = 1; s <= log_n; s++) {
-        const size_t mlen = (size_t)1 << s, h = mlen >> 1;
-        uint64_t wm = root;
-        for (uint32_t k = s; k < log_n; k++) wm = gl::sqr(wm);
-        for (size_t k = 0; k < n; k += mlen) {
-            uint64_t w = 1;
-            for (size_t j = 0; j < h; j++) {
-                const uint64_t t = gl::mul(w, a[k + j + h]), u = a[k + j];
-                a[k + j] = gl::add(u, t);
-                a[k + j + h] = gl::sub(u, t);
-                w = gl::mul(w, wm);
-            }
-        }
-    }
-    if (inverse) {
-        const uint64_t ninv = gl::inv((uint64_t)n);
-        for (size_t i = 0; i < n; i++) a[i] = gl::mul(a[i], ninv);
-    }
-}
-
 // PRECONDITION: every cell of d_lde / d_zlde / d_aux is CANONICAL (< p).  The lazy POLY path adds and subtracts +-1-coefficient
 // monomials with gl::add / gl::sub directly on raw operands (no product in between to canonicalise them): gl::sub(a, b) with b >= p
 // would be off by 2^32 - 1.  Every producer keeps this: the tree sweeps (ntt_tree.hip) and lde_column canonicalise at their last store
@@ -1327,14 +1271,14 @@ int sipp_k_quotient(sipp_ctx* ctx, const air_spec_t* a, uint32_t log_n, const ui
                 }
                 seen.emplace(vals, k);
                 for (size_t r = 0; r < R; r++) col[r] = gl::from_i64(vals[r]);
-                host_ntt(col.data(), lr, true);
+                sipp_host_ntt(col.data(), lr, true);
                 uint64_t f = 1;
                 for (size_t j = 0; j < R; j++) {
                     col[j] = gl::mul(col[j], f);
                     f = gl::mul(f, shift);
                 }
                 for (size_t j = R; j < R2; j++) col[j] = 0;
-                host_ntt(col.data(), lr + 1, false);
+                sipp_host_ntt(col.data(), lr + 1, false);
                 memcpy(&tab[(size_t)k * R2], col.data(), R2 * 8);
             }
             SIPP_TRY(sipp_table_put(ctx, 104, log_n, (uint64_t)a->kind, tab, &t));
@@ -1360,9 +1304,7 @@ int sipp_k_quotient(sipp_ctx* ctx, const air_spec_t* a, uint32_t log_n, const ui
         q.alpha16[ch] = gl::pow(alpha[ch], 16);
         uint64_t x = 1;
         for (int i = 0; i < 8; i++) {
-            q.ginv3[ch][i][0] = (uint32_t)x & 0x3FFFFFu;
-            q.ginv3[ch][i][1] = (uint32_t)(x >> 22) & 0x3FFFFFu;
-            q.ginv3[ch][i][2] = (uint32_t)(x >> 44);
+            gl::limbs3(q.ginv3[ch][i], x);
             x = gl::mul(x, gi);
         }
     }
@@ -1434,13 +1376,11 @@ int sipp_k_quotient(sipp_ctx* ctx, const air_spec_t* a, uint32_t log_n, const ui
         memcpy(h32 + ns, cnt.data(), (size_t)ns * 4);
         const size_t ap_at = (size_t)ns * 2 + (((size_t)2 * ns + 1) >> 1);     // behind the two u32 tables (ns + ns words)
         {
-            uint32_t* ap = reinterpret_cast<uint32_t*>(&host[ap_at]);
+            uint32_t(*ap)[3] = reinterpret_cast<uint32_t(*)[3]>(&host[ap_at]);
             for (int ch = 0; ch < 2; ch++) {
                 uint64_t x = 1;
                 for (int e = 0; e < 64; e++) {
-                    ap[(ch * 64 + e) * 3 + 0] = (uint32_t)x & 0x3FFFFFu;
-                    ap[(ch * 64 + e) * 3 + 1] = (uint32_t)(x >> 22) & 0x3FFFFFu;
-                    ap[(ch * 64 + e) * 3 + 2] = (uint32_t)(x >> 44);
+                    gl::limbs3(ap[ch * 64 + e], x);
                     x = gl::mul(x, alpha[ch]);
                 }
             }
@@ -1658,33 +1598,6 @@ int sipp_k_fri_fold(sipp_ctx* ctx, const uint64_t* d_in, size_t len_in, uint32_t
     ProfScope ps(ctx, "fri_fold");
     hipLaunchKernelGGL(fri_fold_kernel, dim3((unsigned)((len_out + 255) / 256)), dim3(256), 0, ctx->stream, d_in, len_in, arity_bits,
                        beta, d_out);
-    SIPP_CHECK_HIP(ctx, hipGetLastError());
-    return SIPP_OK;
-}
-
-int sipp_k_gather_rows(sipp_ctx* ctx, const uint64_t* d_lde, size_t m, uint32_t ncols, const uint32_t* d_idx, uint32_t nq,
-                       uint64_t* d_out) {
-    ProfScope ps(ctx, "query_gather");
-    unsigned gx = (ncols + 255) / 256;
-    hipLaunchKernelGGL(gather_rows_kernel, dim3(gx, nq), dim3(256), 0, ctx->stream, d_lde, m, ncols, d_idx, d_out);
-    SIPP_CHECK_HIP(ctx, hipGetLastError());
-    return SIPP_OK;
-}
-
-int sipp_k_gather_siblings(sipp_ctx* ctx, const uint64_t* d_tree, uint32_t log_leaves, uint32_t nsib, uint32_t shift,
-                           const uint32_t* d_idx, uint32_t nq, uint64_t* d_out) {
-    if (!nsib) return SIPP_OK;
-    ProfScope ps(ctx, "query_gather");
-    hipLaunchKernelGGL(gather_siblings_kernel, dim3(nq), dim3(4 * 32), 0, ctx->stream, d_tree, log_leaves, nsib, shift, d_idx, d_out);
-    SIPP_CHECK_HIP(ctx, hipGetLastError());
-    return SIPP_OK;
-}
-
-int sipp_k_gather_fri_leaf(sipp_ctx* ctx, const uint64_t* d_vals, size_t len, uint32_t shift, uint32_t arity_bits,
-                           const uint32_t* d_idx, uint32_t nq, uint64_t* d_out) {
-    ProfScope ps(ctx, "query_gather");
-    hipLaunchKernelGGL(gather_fri_leaf_kernel, dim3(nq), dim3(2u << arity_bits), 0, ctx->stream, d_vals, len, shift, arity_bits, d_idx,
-                       d_out);
     SIPP_CHECK_HIP(ctx, hipGetLastError());
     return SIPP_OK;
 }

@@ -2,8 +2,9 @@
 // host-side Fiat-Shamir challenger.
 #pragma once
 #include <functional>
+#include <utility>
 
-#include "ctx.hpp"
+#include "commit.hpp"
 #include "host_challenger.hpp"
 #include "host_poseidon.hpp"
 #include "poseidon_constants.h"
@@ -47,12 +48,6 @@ struct QueryGatherTask {
     uint32_t type, b, c, d;
 };
 int sipp_k_gather_tasks(sipp_ctx* ctx, const QueryGatherTask* d_tasks, uint32_t n_tasks, const uint32_t* d_idx, uint32_t nq);
-int sipp_k_gather_rows(sipp_ctx* ctx, const uint64_t* d_lde, size_t m, uint32_t ncols, const uint32_t* d_idx, uint32_t nq,
-                       uint64_t* d_out);
-int sipp_k_gather_siblings(sipp_ctx* ctx, const uint64_t* d_tree, uint32_t log_leaves, uint32_t nsib, uint32_t shift,
-                           const uint32_t* d_idx, uint32_t nq, uint64_t* d_out);
-int sipp_k_gather_fri_leaf(sipp_ctx* ctx, const uint64_t* d_vals, size_t len, uint32_t shift, uint32_t arity_bits,
-                           const uint32_t* d_idx, uint32_t nq, uint64_t* d_out);
 // poseidon.hip
 // leaf k = the 2^arity_bits consecutive (leaf-order) extension values [k 2^ab, (k + 1) 2^ab), flattened (c0, c1); hash_or_noop
 int sipp_k_fri_leaves(sipp_ctx* ctx, const uint64_t* d_vals, size_t len, uint32_t arity_bits, uint64_t* d_digests);
@@ -63,6 +58,49 @@ int sipp_k_pow_search(sipp_ctx* ctx, const uint64_t state[12], const uint64_t* i
 
 // ---- host Poseidon + duplex challenger: host_challenger.hpp (shared with the host-only verifier, verify.cpp) ----
 
+// ---- small host helpers of the provers ----------------------------------------------------------------------------
+// out [count][2][3]: the limbs (gl::limbs3) of the two components of base^c, c < count -- the constant weights of the lazy
+// combinations (prover.hip fri_combine_kernel and its kin).  Returns base^count.
+inline gl::E2 sipp_pow_limbs(gl::E2 base, size_t count, uint32_t* out) {
+    uint32_t(*o)[3] = reinterpret_cast<uint32_t(*)[3]>(out);
+    gl::E2 x = gl::e2(1);
+    for (size_t c = 0; c < count; c++) {
+        gl::limbs3(o[2 * c], x.c0);
+        gl::limbs3(o[2 * c + 1], x.c1);
+        x = gl::mul(x, base);
+    }
+    return x;
+}
+// natural-order radix-2 NTT on the host (the public-input polynomials, the value-periodic columns: sizes up to a few thousand):
+// out[i] = sum_j a[j] w^(i j), w a primitive 2^log_n-th root (inverse: w^-1 and the factor 1 / n)
+inline void sipp_host_ntt(uint64_t* a, uint32_t log_n, bool inverse) {
+    const size_t n = (size_t)1 << log_n;
+    for (size_t i = 0; i < n; i++) {
+        const size_t j = gl::bitrev((uint32_t)i, log_n);
+        if (i < j) std::swap(a[i], a[j]);
+    }
+    uint64_t root = gl::root_of_unity(log_n);
+    if (inverse) root = gl::inv(root);
+    for (uint32_t s = 1; s <= log_n; s++) {
+        const size_t mlen = (size_t)1 << s, h = mlen >> 1;
+        uint64_t wm = root;
+        for (uint32_t k = s; k < log_n; k++) wm = gl::sqr(wm);
+        for (size_t k = 0; k < n; k += mlen) {
+            uint64_t w = 1;
+            for (size_t j = 0; j < h; j++) {
+                const uint64_t t = gl::mul(w, a[k + j + h]), u = a[k + j];
+                a[k + j] = gl::add(u, t);
+                a[k + j + h] = gl::sub(u, t);
+                w = gl::mul(w, wm);
+            }
+        }
+    }
+    if (inverse) {
+        const uint64_t ninv = gl::inv((uint64_t)n);
+        for (size_t i = 0; i < n; i++) a[i] = gl::mul(a[i], ninv);
+    }
+}
+
 // ---- the FRI core (fri.hip) ------------------------------------------------------------------------------------
 struct FriOracleDev {
     const uint64_t* lde;    // [ncols][stride] leaf order (salt columns, if any, are the last ones)
@@ -70,9 +108,29 @@ struct FriOracleDev {
     uint32_t ncols;         // words per leaf
     const uint64_t* tree;   // levels back to back
 };
+// rounds of FriReductionStrategy::ConstantArityBits(arity_bits, final_poly_bits) for 2^degree_bits coefficients: fold while the
+// polynomial is longer than the final one and the folded layer still has a cap
+inline uint32_t sipp_fri_const_arity_rounds(uint32_t degree_bits, uint32_t rate_bits, uint32_t cap_height, uint32_t arity_bits,
+                                            uint32_t final_poly_bits) {
+    uint32_t rounds = 0;
+    while (degree_bits > final_poly_bits && degree_bits + rate_bits - arity_bits >= cap_height && degree_bits >= arity_bits &&
+           rounds < SIPP_FRI_MAX_ROUNDS) {
+        rounds++;
+        degree_bits -= arity_bits;
+    }
+    return rounds;
+}
 struct FriParamsDev {
     uint32_t rate_bits = 1, cap_height = 4, pow_bits = 16, num_queries = 84, pow_rule = 0;
     std::vector<uint32_t> arity_bits;   // FriParams::reduction_arity_bits
+    // the generic ABI's parameters (n_rounds beyond SIPP_FRI_MAX_ROUNDS is refused by the callers' checks, cut here)
+    explicit FriParamsDev(const sipp_fri_params& p)
+        : rate_bits(p.rate_bits), cap_height(p.cap_height), pow_bits(p.pow_bits), num_queries(p.num_queries), pow_rule(p.pow_rule),
+          arity_bits(p.arity_bits, p.arity_bits + (p.n_rounds < SIPP_FRI_MAX_ROUNDS ? p.n_rounds : SIPP_FRI_MAX_ROUNDS)) {}
+    // FriParams of a STARK over 2^degree_bits rows
+    FriParamsDev(const sipp_stark_config& c, uint32_t degree_bits)
+        : rate_bits(c.rate_bits), cap_height(c.cap_height), pow_bits(c.pow_bits), num_queries(c.num_queries), pow_rule(c.pow_rule),
+          arity_bits(sipp_fri_const_arity_rounds(degree_bits, c.rate_bits, c.cap_height, c.arity_bits, c.final_poly_bits), c.arity_bits) {}
 };
 // u64 words of the section sipp_fri_prove_core appends (caps, final polynomial, witness, query rounds)
 size_t sipp_fri_core_words(const FriParamsDev& p, uint32_t log_n, const uint32_t* leaf_words, int n_oracles);

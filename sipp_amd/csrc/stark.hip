@@ -53,21 +53,8 @@ static int shape_of(int kind, size_t num_io, Shape* s) {
     return SIPP_OK;
 }
 
-// FriParams of a STARK: FriReductionStrategy::ConstantArityBits(arity_bits, final_poly_bits)
-static FriParamsDev fri_params_of(const sipp_stark_config& c, uint32_t degree_bits) {
-    FriParamsDev p;
-    p.rate_bits = c.rate_bits; p.cap_height = c.cap_height; p.pow_bits = c.pow_bits; p.num_queries = c.num_queries;
-    p.pow_rule = c.pow_rule;
-    while (degree_bits > c.final_poly_bits && degree_bits + c.rate_bits - c.arity_bits >= c.cap_height &&
-           degree_bits >= c.arity_bits && p.arity_bits.size() < 32) {
-        p.arity_bits.push_back(c.arity_bits);
-        degree_bits -= c.arity_bits;
-    }
-    return p;
-}
-
 static size_t proof_words(const sipp_stark_config& cfg, const Shape& s) {
-    const FriParamsDev fp = fri_params_of(cfg, s.log_n);
+    const FriParamsDev fp(cfg, s.log_n);
     const uint32_t log_m = s.log_n + cfg.rate_bits;
     const size_t cap = (size_t)4 << cfg.cap_height;
     size_t w = 16 + 3 * cap + 2 * (size_t)(2 * s.W + 2 * s.P + s.Q);
@@ -93,83 +80,6 @@ static int upload_ios(sipp_ctx* ctx, int kind, const uint32_t* ios, size_t num_i
     SIPP_CHECK_HIP(ctx, hipMemcpyAsync(*d_ios, h, words * 4, hipMemcpyHostToDevice, ctx->stream));
     SIPP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the pinned buffer is reused below
     return SIPP_OK;
-}
-
-// ---- commitment helpers -------------------------------------------------------------------------------
-static size_t tree_words(uint32_t log_leaves) { return ((size_t)8 << log_leaves); }  // 2 * leaves * 4
-
-static int read_cap(sipp_ctx* ctx, const uint64_t* d_tree, uint32_t log_leaves, uint64_t* cap_host) {
-    const uint32_t ch = std::min(ctx->cfg.cap_height, log_leaves);
-    uint64_t off = 0;
-    for (uint32_t l = 0; l < log_leaves - ch; l++) off += (uint64_t)1 << (log_leaves - l);
-    SIPP_CHECK_HIP(ctx, hipMemcpyAsync(cap_host, d_tree + 4 * off, ((size_t)4 << ch) * 8, hipMemcpyDeviceToHost, ctx->stream));
-    SIPP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return SIPP_OK;
-}
-
-// coeffs [ncols][n] natural -> lde [ncols][m] leaf order -> tree (launches only; read_cap collects the cap)
-static int commit_coeffs_launch(sipp_ctx* ctx, const uint64_t* d_coeffs, size_t ncols, uint32_t log_n, uint64_t* d_lde,
-                                uint64_t* d_tree) {
-    const uint32_t log_m = log_n + ctx->cfg.rate_bits;
-    int rc = sipp_lde_from_coeffs(ctx, d_coeffs, d_lde, ncols, log_n, ctx->cfg.rate_bits);
-    if (rc == SIPP_E_UNSUPPORTED)
-        rc = sipp_ntt_dif(ctx, d_coeffs, (size_t)1 << log_n, log_n, d_lde, (size_t)1 << log_m, log_m, ncols, false,
-                          NttDiag{gl::GEN, 0});
-    SIPP_TRY(rc);
-    SIPP_TRY(sipp_k_poseidon_leaves(ctx, d_lde, (size_t)1 << log_m, ncols, log_m, d_tree));
-    return sipp_k_merkle_levels(ctx, d_tree, log_m, ctx->cfg.cap_height);
-}
-static int commit_coeffs(sipp_ctx* ctx, const uint64_t* d_coeffs, size_t ncols, uint32_t log_n, uint64_t* d_lde,
-                         uint64_t* d_tree, uint64_t* cap_host) {
-    SIPP_TRY(commit_coeffs_launch(ctx, d_coeffs, ncols, log_n, d_lde, d_tree));
-    return read_cap(ctx, d_tree, log_n + ctx->cfg.rate_bits, cap_host);
-}
-
-// values [ncols][n] natural -> coeffs -> lde -> tree (launches only)
-static int commit_values_launch(sipp_ctx* ctx, const uint64_t* d_values, size_t ncols, uint32_t log_n, uint64_t* d_coeffs,
-                                uint64_t* d_lde, uint64_t* d_tree) {
-    const size_t n = (size_t)1 << log_n;
-    const uint32_t log_m = log_n + ctx->cfg.rate_bits;
-    const int rc = sipp_lde_from_values(ctx, d_values, d_coeffs, d_lde, ncols, log_n, ctx->cfg.rate_bits);
-    if (rc == SIPP_OK) {   // fused: coefficients and LDE are both in place
-        SIPP_TRY(sipp_k_poseidon_leaves(ctx, d_lde, (size_t)1 << log_m, ncols, log_m, d_tree));
-        return sipp_k_merkle_levels(ctx, d_tree, log_m, ctx->cfg.cap_height);
-    }
-    if (rc != SIPP_E_UNSUPPORTED) return rc;
-    SIPP_TRY(sipp_bitrev_cols(ctx, d_values, n, d_coeffs, n, log_n, ncols));
-    SIPP_TRY(sipp_ntt_dit(ctx, d_coeffs, n, log_n, ncols, true, NttDiag{}));
-    return commit_coeffs_launch(ctx, d_coeffs, ncols, log_n, d_lde, d_tree);
-}
-static int commit_values(sipp_ctx* ctx, const uint64_t* d_values, size_t ncols, uint32_t log_n, uint64_t* d_coeffs,
-                         uint64_t* d_lde, uint64_t* d_tree, uint64_t* cap_host) {
-    SIPP_TRY(commit_values_launch(ctx, d_values, ncols, log_n, d_coeffs, d_lde, d_tree));
-    return read_cap(ctx, d_tree, log_n + ctx->cfg.rate_bits, cap_host);
-}
-
-// ---- small host FFT for the public-input polynomials (size = number of IOs) ----------------------------
-static void host_ifft(std::vector<uint64_t>& a, uint32_t log_n) {
-    const size_t n = (size_t)1 << log_n;
-    for (size_t i = 0; i < n; i++) {
-        size_t j = gl::bitrev((uint32_t)i, log_n);
-        if (i < j) std::swap(a[i], a[j]);
-    }
-    const uint64_t root = gl::inv(gl::root_of_unity(log_n));
-    for (uint32_t s = 1; s <= log_n; s++) {
-        const size_t mlen = (size_t)1 << s, h = mlen >> 1;
-        uint64_t wm = root;
-        for (uint32_t k = s; k < log_n; k++) wm = gl::sqr(wm);
-        for (size_t k = 0; k < n; k += mlen) {
-            uint64_t w = 1;
-            for (size_t j = 0; j < h; j++) {
-                uint64_t t = gl::mul(w, a[k + j + h]), u = a[k + j];
-                a[k + j] = gl::add(u, t);
-                a[k + j + h] = gl::sub(u, t);
-                w = gl::mul(w, wm);
-            }
-        }
-    }
-    const uint64_t ninv = gl::inv((uint64_t)n);
-    for (auto& v : a) v = gl::mul(v, ninv);
 }
 
 // ---- BN254 Fq on the host, only for the public basis change of Fq12 public inputs (tools/air_gen.py build_fq12):
@@ -283,7 +193,7 @@ static int prove_impl(sipp_ctx* ctx, int kind, const uint32_t* ios, size_t num_i
     Shape s;
     SIPP_TRY(shape_of(kind, num_io_in, &s));
     const air_spec_t* a = s.air;
-    const FriParamsDev fp = fri_params_of(cfg, s.log_n);
+    const FriParamsDev fp(cfg, s.log_n);
     const uint32_t log_n = s.log_n, log_m = log_n + cfg.rate_bits, R = (uint32_t)fp.arity_bits.size();
     // the layer kernels (transforms, leaf hashing) work on at least 16 values: a limit of this implementation, not of FRI --
     // refused here, before any work, instead of by a kernel wrapper in the middle of the proof
@@ -310,15 +220,8 @@ static int prove_impl(sipp_ctx* ctx, int kind, const uint32_t* ios, size_t num_i
         fprintf(stderr, "[sipp kind %d] %-18s %8.3f ms\n", kind, what, std::chrono::duration<double, std::milli>(now - t_prev).count());
         t_prev = now;
     };
-    ArenaMark mark = arena_mark(ctx);
-    struct Release {
-        sipp_ctx* c;
-        ArenaMark m;
-        ~Release() {
-            (void)hipStreamSynchronize(c->stream);
-            arena_release(c, m);
-        }
-    } release{ctx, mark};
+    ArenaScope scope(ctx, /*sync_first=*/true);
+    const CommitParams cp{cfg.rate_bits, cfg.cap_height};
 
     uint64_t* pf = proof_out;
     size_t pos = 0;
@@ -371,7 +274,7 @@ static int prove_impl(sipp_ctx* ctx, int kind, const uint32_t* ios, size_t num_i
     uint64_t cap_host[4 << 8];
 
     // ---- 1. trace commitment ----
-    SIPP_TRY(commit_values_launch(ctx, d_trace, (size_t)W, log_n, T.coeffs, T.lde, T.tree));
+    SIPP_TRY(commit_launch(ctx, cp, d_trace, false, T.coeffs, T.lde, T.tree, (size_t)W, log_n));
     // Fiat-Shamir starts from the statement (hashed on the host while the commitment kernels run)
     // (cfg.fs_rule = SIPP_FS_UPSTREAM: starky's recalled order instead -- the challenger starts at the trace cap)
     host::Challenger ch;
@@ -407,7 +310,7 @@ static int prove_impl(sipp_ctx* ctx, int kind, const uint32_t* ios, size_t num_i
                     col[io] = part == 0 ? (w & 0xffff) : part == 1 ? (w >> 16) : w;
                 }
             }
-            host_ifft(col, log_io);
+            sipp_host_ntt(col.data(), log_io, /*inverse=*/true);
             if (shift) {
                 const uint64_t sft = gl::inv(gl::pow(g, (uint64_t)shift));
                 uint64_t f = 1;
@@ -419,7 +322,7 @@ static int prove_impl(sipp_ctx* ctx, int kind, const uint32_t* ios, size_t num_i
             memcpy(&auxc[(size_t)ai * nio], col.data(), nio * 8);
         }
     }
-    SIPP_TRY(read_cap(ctx, T.tree, log_m, cap_host));
+    SIPP_TRY(read_cap(ctx, T.tree, log_m, cfg.cap_height, cap_host));
     ch.observe_many(cap_host, cap_words);
     push(cap_host, cap_words);
     tick("trace commit");
@@ -432,12 +335,11 @@ static int prove_impl(sipp_ctx* ctx, int kind, const uint32_t* ios, size_t num_i
         if (cfg.lookup_rule == SIPP_LOOKUP_SHARED) beta[i] = gamma[i];     // both factors of a lookup under ONE challenge (sipp_hip.h)
     }
     {
-        ArenaMark mz = arena_mark(ctx);
+        ArenaScope z_scope(ctx);   // the Z values go back before the quotient allocates (commit_batch returns synchronised)
         uint64_t* d_zv = arena_alloc_t<uint64_t>(ctx, (size_t)P * n);
         if (!d_zv) return SIPP_E_NOMEM;
         SIPP_TRY(sipp_k_z_columns(ctx, a, d_trace, log_n, beta, gamma, d_zv));
-        SIPP_TRY(commit_values(ctx, d_zv, (size_t)P, log_n, Z.coeffs, Z.lde, Z.tree, cap_host));
-        arena_release(ctx, mz);
+        SIPP_TRY(commit_batch(ctx, cp, d_zv, false, Z.coeffs, Z.lde, Z.tree, (size_t)P, log_n, cap_host));
     }
     ch.observe_many(cap_host, cap_words);
     push(cap_host, cap_words);
@@ -450,7 +352,7 @@ static int prove_impl(sipp_ctx* ctx, int kind, const uint32_t* ios, size_t num_i
 
     // ---- 4. quotient ----
     {
-        ArenaMark mark_q = arena_mark(ctx);
+        ArenaScope q_scope(ctx);   // the quotient scratch goes back before the openings allocate
         // (the public-input polynomials' coefficients were interpolated on the host while the trace commitment ran: auxc)
         uint64_t* d_auxc = arena_alloc_t<uint64_t>(ctx, (size_t)n_aux * nio + 1);
         uint64_t* d_aux = arena_alloc_t<uint64_t>(ctx, (size_t)n_aux * mq + 1);
@@ -467,8 +369,7 @@ static int prove_impl(sipp_ctx* ctx, int kind, const uint32_t* ios, size_t num_i
         // coset iNTT: leaf-order values -> natural coefficients of q(x) (undo the shift 7)
         SIPP_TRY(sipp_ntt_dit(ctx, Qo.coeffs, mq, log_mq, 2, true, NttDiag{gl::inv(gl::GEN), 0}));
         // [2][2N] natural == 4 chunks of N coefficients, contiguous
-        SIPP_TRY(commit_coeffs(ctx, Qo.coeffs, (size_t)Q, log_n, Qo.lde, Qo.tree, cap_host));
-        arena_release(ctx, mark_q);
+        SIPP_TRY(commit_batch(ctx, cp, Qo.coeffs, true, Qo.coeffs, Qo.lde, Qo.tree, (size_t)Q, log_n, cap_host));
     }
     ch.observe_many(cap_host, cap_words);
     push(cap_host, cap_words);
@@ -517,16 +418,7 @@ static int prove_impl(sipp_ctx* ctx, int kind, const uint32_t* ios, size_t num_i
     {
         // limbs of alpha^c (c0, c1) for the lazy combination (prover.hip::fri_combine_kernel)
         std::vector<uint32_t> apow((size_t)(W + P + Q) * 6);
-        gl::E2 ap = gl::e2(1);
-        for (int c = 0; c < W + P + Q; c++) {
-            const uint64_t comp[2] = {ap.c0, ap.c1};
-            for (int q = 0; q < 2; q++) {
-                apow[6 * c + 3 * q] = (uint32_t)comp[q] & 0x3FFFFFu;
-                apow[6 * c + 3 * q + 1] = (uint32_t)(comp[q] >> 22) & 0x3FFFFFu;
-                apow[6 * c + 3 * q + 2] = (uint32_t)(comp[q] >> 44);
-            }
-            ap = gl::mul(ap, fa);
-        }
+        sipp_pow_limbs(fa, (size_t)(W + P + Q), apow.data());
         uint32_t* d_apow = arena_alloc_t<uint32_t>(ctx, apow.size());
         if (!d_final || !d_apow) return SIPP_E_NOMEM;
         SIPP_CHECK_HIP(ctx, hipMemcpyAsync(d_apow, apow.data(), apow.size() * 4, hipMemcpyHostToDevice, ctx->stream));
@@ -624,7 +516,7 @@ int sipp_trace_build(sipp_ctx* ctx, int kind, const uint32_t* ios, size_t num_io
     SIPP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
     Shape s;
     SIPP_TRY(shape_of(kind, num_io, &s));
-    ArenaMark m = arena_mark(ctx);
+    ArenaScope scope(ctx);
     uint32_t* d_ios = nullptr;
     int rc = upload_ios(ctx, kind, ios, num_io, s, &d_ios, nullptr);
     int* d_err = arena_alloc_t<int>(ctx, 1);
@@ -639,7 +531,6 @@ int sipp_trace_build(sipp_ctx* ctx, int kind, const uint32_t* ios, size_t num_io
         rc = sipp_sync(ctx);
         if (rc == SIPP_OK && h_err) rc = sipp_fail(ctx, h_err, "trace fill: IO record not provable");
     }
-    arena_release(ctx, m);
     return rc;
 }
 

@@ -1098,24 +1098,15 @@ extern "C" int sipp_fri_verify_openings(const uint64_t* proof, size_t len, const
     std::vector<FriBatchV> bv(n_batches);
     for (size_t b = 0; b < n_batches; b++) bv[b] = FriBatchV{E2{batches[b].point[0], batches[b].point[1]}, batches[b].n_ranges, batches[b].ranges};
     std::vector<uint32_t> zero(n_oracles, 0);
-    host::Challenger ch;
-    memcpy(ch.state, chal->state, sizeof ch.state);
-    memcpy(ch.in_buf, chal->in_buf, sizeof ch.in_buf);
-    memcpy(ch.out_buf, chal->out_buf, sizeof ch.out_buf);
     if (chal->n_in > 8 || chal->n_out > 8) return SIPP_E_BADARG;
-    ch.n_in = (uint32_t)chal->n_in;
-    ch.n_out = (uint32_t)chal->n_out;
+    host::Challenger ch(*chal);
     int r;
     try {
         r = fri_openings_verify(proof, len, caps, ncols, n_salt ? n_salt : zero.data(), n_oracles, bv.data(), n_batches, log_n, *p, ch);
     } catch (...) {                        // (allocation failure: nothing crosses the C boundary)
         return SIPP_E_NOMEM;
     }
-    memcpy(chal->state, ch.state, sizeof ch.state);
-    memcpy(chal->in_buf, ch.in_buf, sizeof ch.in_buf);
-    memcpy(chal->out_buf, ch.out_buf, sizeof ch.out_buf);
-    chal->n_in = ch.n_in;
-    chal->n_out = ch.n_out;
+    ch.store(chal);
     if (reason) *reason = r;
     return r == 0 ? SIPP_OK : SIPP_E_VERIFY;
 }

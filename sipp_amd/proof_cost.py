@@ -20,7 +20,7 @@ def shape(kind, num_io):
 
 
 def fri_arities(log_n, rate_bits=1, cap_height=4, arity_bits=4, final_poly_bits=5):
-    """FriReductionStrategy::ConstantArityBits as stark.hip fri_params_of reads it"""
+    """FriReductionStrategy::ConstantArityBits as prover.hpp sipp_fri_const_arity_rounds reads it"""
     out, d = [], log_n
     while d > final_poly_bits and d + rate_bits - arity_bits >= cap_height and d >= arity_bits and len(out) < 32:
         out.append(arity_bits)
