@@ -321,8 +321,8 @@ int sipp_commit_batch_ex(sipp_ctx *ctx, const uint64_t *d_in, int from_coeffs, u
                          const uint64_t *d_salt, uint32_t n_salt, uint64_t *cap_out);
 typedef struct { uint32_t oracle, col_begin, col_end; } sipp_poly_range;
 typedef struct {
-    uint64_t point[2];              /* extension element (c0, c1), not in the trace subgroup */
-    uint32_t n_ranges;
+    uint64_t point[2];              /* extension element (c0, c1), not in the trace subgroup (SIPP_E_SUBGROUP); zero is allowed */
+    uint32_t n_ranges;              /* may be 0, and ranges may be empty (col_begin == col_end): a batch without a polynomial opens nothing */
     const sipp_poly_range *ranges;  /* FriBatchInfo::polynomials as ranges of oracle columns, in opening order */
 } sipp_fri_batch;
 /* plonky2 Challenger state as plain data: the caller's transcript goes in and comes out */

@@ -8,73 +8,24 @@ import os
 import sys
 import time
 
-import numpy as np
-
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import sipp_amd  # noqa: E402
 from sipp_amd._lib import to_device  # noqa: E402
 from tests import _oracle, _verify  # noqa: E402
+from tests._fri_cases import stress_config, stress_data  # noqa: E402
 from tests.test_gpu_fri_generic import gpu_challenger, to_params  # noqa: E402
 
-P = _oracle.P
 first = int(sys.argv[1]) if len(sys.argv) > 1 else 700
 count = int(sys.argv[2]) if len(sys.argv) > 2 else 40
 ctx = sipp_amd.Ctx(workspace_bytes=4 << 30)
 bad = skipped = declined = 0
 t0 = time.time()
 for seed in range(first, first + count):
-    rng = np.random.default_rng(seed)
-    log_n = int(rng.integers(10, 15))       # the GPU layer supports degree bits 10 .. 24
-    rate_bits = int(rng.integers(1, 4))
-    n, m = 1 << log_n, 1 << (log_n + rate_bits)
-    n_or = int(rng.integers(1, 5))
-    widths = [int([1, 2, 4, 5, 8, 9, 17, 33][int(rng.integers(0, 8))]) for _ in range(n_or)]
-    salted = [bool(rng.integers(0, 2)) for _ in range(n_or)]
-    mixed = bool(rng.integers(0, 3) == 0)
-    pow_rule = int(rng.integers(0, 2))
-    nq = int(rng.integers(1, 13))
-    pow_bits = int(rng.integers(0, 11))
-    if mixed:
-        arities, left = [], log_n
-        while left > 0 and len(arities) < 6 and rng.integers(0, 4):
-            a = int(rng.integers(1, min(4, left) + 1))
-            arities.append(a)
-            left -= a
-        if not arities:
-            arities = [min(2, log_n)]
-        final_bits = log_n - sum(arities)
-        cap_height = int(rng.integers(0, min(5, final_bits + rate_bits) + 1))
-        fp = _oracle.fri_params(rate_bits=rate_bits, cap_height=cap_height, pow_bits=pow_bits, num_queries=nq, pow_rule=pow_rule, hiding=1,
-                                arities=arities)
-        desc = "arities %s" % arities
-    else:
-        arity = int(rng.integers(1, 5))
-        final_poly_bits = int(rng.integers(0, 6))
-        cap_height = int(rng.integers(0, 6))
-        fp = _oracle.fri_params(rate_bits=rate_bits, cap_height=cap_height, pow_bits=pow_bits, num_queries=nq, pow_rule=pow_rule, hiding=1,
-                                arity_bits=arity, final_poly_bits=final_poly_bits, degree_bits=log_n)
-        desc = "arity %d final %d rounds %d" % (arity, final_poly_bits, fp.n_rounds)
-    tag = "seed %d: log_n %d blowup %d cap %d %s pow %d/%d q %d widths %s salted %s" % (
-        seed, log_n, 1 << rate_bits, cap_height, desc, pow_bits, pow_rule, nq, widths, [int(x) for x in salted])
+    cfg, rng = stress_config(seed)       # tests/_fri_cases.py: the configuration as a function of the seed
+    log_n, rate_bits, cap_height, fp, tag = cfg["log_n"], cfg["rate_bits"], cfg["cap_height"], cfg["fp"], cfg["tag"]
     try:
-        oracles = []
-        for k in range(n_or):
-            vals = _oracle.rand_field(rng, (widths[k], n))
-            salt = _oracle.rand_field(rng, (4, m)) if salted[k] else None
-            oracles.append(_oracle.SaltedBatch(vals, log_n, rate_bits, cap_height, from_values=(k % 2 == 0), salt=salt))
-        zeta = tuple(int(x) for x in _oracle.rand_field(rng, 2))
-        w = pow(1753635133440165772, 1 << (32 - log_n), P)
-        gz = (zeta[0] * w % P, zeta[1] * w % P)
-        batches = [(zeta, [(k, 0, widths[k]) for k in range(n_or)])]
-        sub = []
-        for k in range(n_or):
-            if rng.integers(0, 2):
-                lo = int(rng.integers(0, widths[k]))
-                hi = int(rng.integers(lo + 1, widths[k] + 1))
-                sub.append((k, lo, hi))
-        if sub:
-            batches.append((gz, sub))
+        oracles, batches = stress_data(cfg, rng)
         gch, och = gpu_challenger([seed, 1, 2])
         ref = _oracle.fri_prove_openings(oracles, batches, log_n, fp, och)
     except Exception as e:      # noqa: BLE001 -- a configuration the oracle itself refuses (e.g. cap higher than the last layer)

@@ -253,6 +253,12 @@ int sipp_fri_prove_openings(sipp_ctx* ctx, const sipp_oracle* oracles, size_t n_
                 return sipp_fail(ctx, SIPP_E_BADARG, "fri: polynomial range outside its oracle");
         }
     const size_t n = (size_t)1 << log_n, m = n << p->rate_bits;
+    // every refusal of the arguments comes before the first proof word is written and before the first launch
+    std::vector<gl::E2> points(n_batches);
+    for (size_t b = 0; b < n_batches; b++) {
+        points[b] = gl::E2{batches[b].point[0], batches[b].point[1]};
+        if (gl::eq(gl::pow(points[b], (uint64_t)n), gl::e2(1))) return sipp_fail(ctx, SIPP_E_SUBGROUP, "fri: opening point in the subgroup");
+    }
     const FriParamsDev fp(*p);
     host::Challenger ch(*chs);
     ArenaScope scope(ctx, /*sync_first=*/true);
@@ -265,14 +271,15 @@ int sipp_fri_prove_openings(sipp_ctx* ctx, const sipp_oracle* oracles, size_t n_
     }
     // ---- opened values: per batch a power table of its point, one dot product per polynomial ----
     std::vector<uint64_t*> d_zp(n_batches), d_zip(n_batches);
-    std::vector<gl::E2> points(n_batches);
     for (size_t b = 0; b < n_batches; b++) {
-        points[b] = gl::E2{batches[b].point[0], batches[b].point[1]};
-        if (gl::eq(gl::pow(points[b], (uint64_t)n), gl::e2(1))) return sipp_fail(ctx, SIPP_E_SUBGROUP, "fri: opening point in the subgroup");
         d_zp[b] = arena_alloc_t<uint64_t>(ctx, 2 * n);
-        d_zip[b] = arena_alloc_t<uint64_t>(ctx, 2 * n);
-        if (!d_zp[b] || !d_zip[b]) return SIPP_E_NOMEM;
+        if (!d_zp[b]) return SIPP_E_NOMEM;
         SIPP_TRY(sipp_k_pow_table(ctx, points[b], n, d_zp[b]));
+        // the point zero has no inverse: its table of z^k (1, 0, 0, ...) still opens the constant terms, and the quotient below is
+        // the composition shifted down by one coefficient instead of a division (d_zip stays NULL)
+        if (gl::canon(points[b].c0) == 0 && gl::canon(points[b].c1) == 0) continue;
+        d_zip[b] = arena_alloc_t<uint64_t>(ctx, 2 * n);
+        if (!d_zip[b]) return SIPP_E_NOMEM;
         SIPP_TRY(sipp_k_pow_table(ctx, gl::inv(points[b]), n, d_zip[b]));
     }
     for (size_t b = 0; b < n_batches; b++) {
@@ -287,8 +294,10 @@ int sipp_fri_prove_openings(sipp_ctx* ctx, const sipp_oracle* oracles, size_t n_
             at += cnt;
         }
         std::vector<uint64_t> hop(4 * k + 4);
-        SIPP_CHECK_HIP(ctx, hipMemcpyAsync(hop.data(), d_open, (4 * k) * 8, hipMemcpyDeviceToHost, ctx->stream));
-        SIPP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (k) {   // (a batch without a polynomial opens nothing: no zero-byte copy)
+            SIPP_CHECK_HIP(ctx, hipMemcpyAsync(hop.data(), d_open, (4 * k) * 8, hipMemcpyDeviceToHost, ctx->stream));
+            SIPP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        }
         for (size_t j = 0; j < k; j++) {
             memcpy(pf + pos, &hop[4 * j], 16);
             pos += 2;
@@ -313,7 +322,10 @@ int sipp_fri_prove_openings(sipp_ctx* ctx, const sipp_oracle* oracles, size_t n_
         const uint64_t** d_cols = reinterpret_cast<const uint64_t**>(arena_alloc(ctx, (k + 1) * sizeof(uint64_t*)));
         uint32_t* d_apow = arena_alloc_t<uint32_t>(ctx, apow.size());
         if (!d_cols || !d_apow) return SIPP_E_NOMEM;
-        SIPP_CHECK_HIP(ctx, hipMemcpyAsync(d_cols, cols.data(), k * sizeof(uint64_t*), hipMemcpyHostToDevice, ctx->stream));
+        // a batch without a polynomial (k = 0: no range, or empty ranges only) is the zero composition: its column table is empty
+        // (nothing to copy, and an empty vector's data() may be NULL), the combine kernel writes zeros for total = 0 without reading
+        // a column or a weight, the quotient is zero and the shift alpha^0 = 1 leaves the sum of the batches before it as it is
+        if (k) SIPP_CHECK_HIP(ctx, hipMemcpyAsync(d_cols, cols.data(), k * sizeof(uint64_t*), hipMemcpyHostToDevice, ctx->stream));
         SIPP_CHECK_HIP(ctx, hipMemcpyAsync(d_apow, apow.data(), apow.size() * 4, hipMemcpyHostToDevice, ctx->stream));
         SIPP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));   // the host vectors go out of scope
         // alpha.shift_poly: final = final * alpha^(len of THIS batch) + quotient; `ap` is alpha^k here

@@ -1000,6 +1000,21 @@ __global__ void fri_accum_kernel(uint64_t* __restrict__ acc, const uint64_t* __r
     acc[k] = r.c0;
     acc[n + k] = r.c1;
 }
+// the quotient at the point ZERO: (F(X) - F(0)) / X is F shifted down by one coefficient (the division kernels below need the table
+// of z^-k, which does not exist there).  F = sum over slices of partial (slot 0 of [slices][4][n]); q [2][n]
+__global__ void fri_shift_down_kernel(const uint64_t* __restrict__ partial, int slices, size_t n, uint64_t* __restrict__ q) {
+    size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    uint64_t c0 = 0, c1 = 0;
+    if (k + 1 < n)
+        for (int sl = 0; sl < slices; sl++) {
+            const uint64_t* p = partial + (size_t)sl * 4 * n;
+            c0 = gl::add(c0, p[k + 1]);
+            c1 = gl::add(c1, p[n + k + 1]);
+        }
+    q[k] = c0;
+    q[n + k] = c1;
+}
 // fin[0] = 0, fin[k + 1] = acc[k]   (multiplication by X; acc[n - 1] is zero by construction)
 __global__ void fri_mulx_kernel(const uint64_t* __restrict__ acc, size_t n, uint64_t* __restrict__ fin) {
     size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1554,6 +1569,7 @@ int sipp_k_fri_final(sipp_ctx* ctx, const uint64_t* const src[3], const int cnt[
 }
 
 // (F(X) - F(z)) / (X - z) of the composition F = sum_j alpha^j col_j of one generic batch, then acc = acc * shift + quotient
+// (d_zip = the table of z^-k; NULL for z = 0, where the quotient is F without its constant term, shifted down)
 int sipp_k_fri_batch_quotient(sipp_ctx* ctx, const uint64_t* const* d_cols, int total, size_t n, const uint32_t* d_apow3,
                               const uint64_t* d_zp, const uint64_t* d_zip, gl::E2 shift, bool first, uint64_t* d_acc) {
     ArenaScope scope(ctx);   // the scratch goes back on EVERY exit path (the stream is ordered: later users of the block wait)
@@ -1577,7 +1593,11 @@ int sipp_k_fri_batch_quotient(sipp_ctx* ctx, const uint64_t* const* d_cols, int 
         ProfScope ps(ctx, "fri_combine");
         hipLaunchKernelGGL(fri_gcombine_kernel, dim3((unsigned)(n / 256), slices), dim3(256), 0, ctx->stream, c);
     }
-    {
+    if (!d_zip) {   // the point zero (the caller's branch): no division
+        ProfScope ps(ctx, "fri_shift_down");
+        hipLaunchKernelGGL(fri_shift_down_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, partial, slices, n, q);
+        hipLaunchKernelGGL(fri_accum_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_acc, q, n, shift, first ? 1 : 0);
+    } else {
         ProfScope ps(ctx, "fri_divide");
         hipLaunchKernelGGL(fri_divide_tiles, dim3(ntiles, 1), dim3(1024), 0, ctx->stream, d, scan, totals);
         hipLaunchKernelGGL(fri_divide_carry, dim3(1), dim3(256), 0, ctx->stream, totals, (int)ntiles);
