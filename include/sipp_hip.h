@@ -469,6 +469,9 @@ int sipp_plonk_prove_gates(sipp_ctx *ctx, const uint64_t *d_wires, const uint64_
  *                                                                       layout is in 0, out 12, swap 24, delta 25, sbox 29 = 135 wires
  *                                                                       (PoseidonGenerator).  The written cells (out, sbox, delta) must not
  *                                                                       meet the read cells (in, swap)
+ * Defined behaviour outside a gate's range (the constraints, not the generators, refuse such rows): BASE_SPLIT drops the bits of w[0] at
+ * and above n_limbs * bits; U32_MUL_ADD takes the low 32 bits of an operand that is not a u32, and with a stride wider than 5 + 2 limbs
+ * the cells behind an op's limbs stay untouched; RANDOM_ACCESS with an index >= 2^bits selects by the low `bits` bits of the index.
  * The generators are ROW-LOCAL: values that reach a gate's inputs through copy constraints from another gate's outputs have to be there
  * already (the caller orders its calls by level); d_constants = the circuit's constant columns [num_constants][N] (selectors first: the
  * front of d_constants_sigmas).  SIPP_E_BADARG for a layout that leaves the wire table or an unknown family. */

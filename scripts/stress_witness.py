@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """One-off stress run of the outer prover's witness generation and CircuitData (GPU box): RANDOM sizes (2^10 .. 2^15 rows), witness seeds,
 chain lengths (0 = row-local generators; 1 .. 300 links: the level schedule), public inputs; the device's wire table cell for cell
-against oracle/plonk_witness.c (itself = the numpy generator), graph replay and one-by-one launches alike; for the smaller sizes the
+against oracle/plonk_witness.c (itself = the numpy generator), graph replay and one-by-one launches alike, once more with edge values of
+tests/_witness_edges.py planted in one cell of a hundred; for the smaller sizes the
 whole `data.prove(pw)` through sipp_circuit_build / _prove word for word against oracle/plonk_gates.c, and through both verifiers.
 usage: stress_witness.py [first_seed=2600] [count=20]"""
 import os
@@ -17,6 +18,7 @@ import plonk_synth as ps  # noqa: E402
 import sipp_amd  # noqa: E402
 from sipp_amd._lib import to_device, to_host  # noqa: E402
 from tests import _oracle  # noqa: E402
+from tests import _witness_edges as we  # noqa: E402
 from tests.test_gpu_fri_generic import to_params  # noqa: E402
 
 first = int(sys.argv[1]) if len(sys.argv) > 1 else 2600
@@ -38,19 +40,24 @@ for seed in range(first, first + count):
     wires, cs, gate = ps.witness(circ, log_n, seed, pih, chain_len=chain)
     sc = ps.chain_schedule(log_n, chain) if chain else None
     blank = ps.blank_generated(circ, wires, gate, value=int(rng.integers(0, 1 << 62)), sched=sc)
-    ref = _oracle.plonk_generate_witness_levels(blank, cs[:K], log_n, gens, pih, sc) if sc else _oracle.plonk_generate_witness(blank, cs[:K], log_n, gens, pih)
+    cpu = lambda t: _oracle.plonk_generate_witness_levels(t, cs[:K], log_n, gens, pih, sc) if sc else _oracle.plonk_generate_witness(t, cs[:K], log_n, gens, pih)
+    ref = cpu(blank)
     ok = bool((ref == wires).all())
+    # the same table with one cell in a hundred replaced by an edge value of tests/_witness_edges.py (inputs out of their gates' ranges
+    # included: the generators' behaviour there is defined, include/sipp_hip.h)
+    edged = np.where(rng.random(blank.shape) < 0.01, np.array(we.MORE, dtype=np.uint64)[rng.integers(0, len(we.MORE), size=blank.shape)], blank)
     d_cs = to_device(cs)
     sched = sipp_amd.PlonkSchedule.from_dict(sc) if sc else None
-    for route in ((4, 0, 0) if sc else (0,)):
-        L.sipp_ctx_set_kernel_routes(ctx.h, route)
-        d_w = to_device(blank)
-        if sc:
-            ctx.plonk_generate_witness_levels(d_w, d_cs[:K], log_n, gens, pih, sched)
-        else:
-            ctx.plonk_generate_witness(d_w, d_cs[:K], log_n, gens, pih)
-            ctx.sync()
-        ok = ok and bool((to_host(d_w) == ref).all())
+    for table, want in ((blank, ref), (edged, cpu(edged))):
+        for route in ((4, 0, 0) if sc else (0,)):
+            L.sipp_ctx_set_kernel_routes(ctx.h, route)
+            d_w = to_device(table)
+            if sc:
+                ctx.plonk_generate_witness_levels(d_w, d_cs[:K], log_n, gens, pih, sched)
+            else:
+                ctx.plonk_generate_witness(d_w, d_cs[:K], log_n, gens, pih)
+                ctx.sync()
+            ok = ok and bool((to_host(d_w) == want).all())
     L.sipp_ctx_set_kernel_routes(ctx.h, 0)
     note = ""
     if log_n <= 12:
