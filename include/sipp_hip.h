@@ -125,10 +125,14 @@ int sipp_ctx_create_checked(sipp_ctx **out, int device, const sipp_stark_config 
  *   SIPP_ROUTE_LDE_COLUMN_WIDE     columns of 2^13 / 2^14 rows through the whole-column-in-LDS transform instead of the tree sweeps
  *   SIPP_ROUTE_WITNESS_NO_GRAPH    sipp_plonk_generate_witness_levels launches its two kernels per level one by one instead of replaying
  *                                  the captured hipGraph
+ *   SIPP_ROUTE_WITNESS_INTERP_ONE_LANE  on thin levels a SIPP_GEN_COSET_INTERPOLATION row runs on lane 0 of its sixteen lanes instead of the
+ *                                  sixteen-lane scan (one point per lane).  Bit 8 stays unassigned: the setter refuses it as an unknown
+ *                                  bit, which tests/test_gpu_stark.py holds it to
  * Only while no proof is in flight on the ctx. */
 #define SIPP_ROUTE_OPENINGS_UNGROUPED 1u
 #define SIPP_ROUTE_LDE_COLUMN_WIDE 2u
 #define SIPP_ROUTE_WITNESS_NO_GRAPH 4u
+#define SIPP_ROUTE_WITNESS_INTERP_ONE_LANE 16u
 int sipp_ctx_set_kernel_routes(sipp_ctx *ctx, uint32_t routes);
 void sipp_ctx_destroy(sipp_ctx *ctx);
 /* The ctx's HIP stream: level > 0 = a stream of the highest priority the device offers; level <= 0 = a stream with a hardware
@@ -469,6 +473,24 @@ int sipp_plonk_prove_gates(sipp_ctx *ctx, const uint64_t *d_wires, const uint64_
  *                                                                       layout is in 0, out 12, swap 24, delta 25, sbox 29 = 135 wires
  *                                                                       (PoseidonGenerator).  The written cells (out, sbox, delta) must not
  *                                                                       meet the read cells (in, swap)
+ *   SIPP_GEN_ARITHMETIC_EXT p = n_ops, const col c0, const col c1, W    per op at b = 8k over F[X]/(X^2 - W): (w[b+6], w[b+7]) = c0 (w[b], w[b+1])
+ *                                                                       (w[b+2], w[b+3]) + c1 (w[b+4], w[b+5])             (ArithmeticExtensionGenerator)
+ *   SIPP_GEN_EXPONENTIATION p = n_bits (1 .. 64)                        base 0, bits 1 .. n_bits (little-endian), output 1 + n_bits, intermediates
+ *                                                                       from 2 + n_bits: the bits from the top wire down, prev_0 = 1,
+ *                                                                       intermediate_i = prev_i^2 (bit base + 1 - bit), bit = w[n_bits - i] as a
+ *                                                                       field value; output = the last intermediate         (ExponentiationGenerator)
+ *   SIPP_GEN_COSET_INTERPOLATION p = subgroup_bits s (1 .. 4), degree d (>= 2), W
+ *                                                                       n = 2^s: shift 0, n values (2 each) from 1, the evaluation point (2), the
+ *                                                                       evaluation value (2), then from 5 + 2n: ni = (n - 2) / (d - 1)
+ *                                                                       intermediate evals (2 each), ni intermediate products (2 each), the
+ *                                                                       shifted point (2) = point * inv(shift) (0 for shift 0).  Over the domain
+ *                                                                       x_i = g^i (g of order n) with the barycentric weights w_i = g^i / n:
+ *                                                                       (e, q) starts at (0, 1) and takes point after point
+ *                                                                       (e (shifted - x_i) + value_i w_i q, q (shifted - x_i)); the first chunk
+ *                                                                       is min(d, n) points, the others d - 1; the state after every chunk but
+ *                                                                       the last goes to intermediate c, the last e to the evaluation value
+ *                                                                                                                          (InterpolationGenerator)
+ * The three families above take ANY field value in every input cell; W != 0.
  * Defined behaviour outside a gate's range (the constraints, not the generators, refuse such rows): BASE_SPLIT drops the bits of w[0] at
  * and above n_limbs * bits; U32_MUL_ADD takes the low 32 bits of an operand that is not a u32, and with a stride wider than 5 + 2 limbs
  * the cells behind an op's limbs stay untouched; RANDOM_ACCESS with an index >= 2^bits selects by the low `bits` bits of the index.
@@ -484,6 +506,9 @@ int sipp_plonk_prove_gates(sipp_ctx *ctx, const uint64_t *d_wires, const uint64_
 #define SIPP_GEN_REDUCING 7
 #define SIPP_GEN_POSEIDON 8
 #define SIPP_GEN_POSEIDON_SWAP 9
+#define SIPP_GEN_ARITHMETIC_EXT 10
+#define SIPP_GEN_EXPONENTIATION 11
+#define SIPP_GEN_COSET_INTERPOLATION 12
 typedef struct {
     uint32_t kind, selector_index, row;
     uint32_t p[5];

@@ -14,6 +14,9 @@
 // naive state; upstream's fast partial rounds change the basis of elements 1 .. 11 only, so they write the same values into those wires.
 // SIPP_GEN_POSEIDON_SWAP is upstream's PoseidonGate with its swap wire (a Merkle-path step): delta_i = swap (in[4+i] - in[i]) goes to its
 // wires, the permutation runs on (in[i] + delta_i, in[4+i] - delta_i, in[8 .. 12)).
+// The FRI fold's families (recalled gates/arithmetic_extension.rs, exponentiation.rs, coset_interpolation.rs) work over F[X]/(X^2 - W), W
+// passed as data: SIPP_GEN_ARITHMETIC_EXT, SIPP_GEN_EXPONENTIATION, and SIPP_GEN_COSET_INTERPOLATION, the barycentric evaluation of the
+// polynomial through n = 2^s values on the coset shift * <g> at a point, in chunks whose partial states are wires.
 #include "ctx.hpp"
 #include "poseidon_constants.h"
 #include <mutex>
@@ -23,6 +26,21 @@ namespace {
 __constant__ uint64_t w_rc[360];
 __constant__ uint32_t w_mds_circ[12] = {17, 15, 41, 16, 2, 28, 13, 13, 39, 18, 34, 20};
 constexpr uint32_t MDS_DIAG0 = 8;
+
+// the interpolation domain: the powers of the primitive root of order 16 (x_i of the order-n subgroup = entry i * 16 / n), and 1 / 2^s
+__constant__ uint64_t w_om16[16] = {0x1ull, 0xefffffff00000001ull, 0xfffffffeff000001ull, 0xffffffff00000ull, 0x1000000000000ull, 0x1000ull,
+                                    0xfffffeff00000101ull, 0xffffffef00000001ull, 0xffffffff00000000ull, 0x1000000000000000ull, 0x1000000ull,
+                                    0xffefffff00100001ull, 0xfffeffff00000001ull, 0xfffffffefffff001ull, 0xffffffff00ull, 0x1000000000ull};
+__constant__ uint64_t w_ninv[5] = {0x1ull, 0x7fffffff80000001ull, 0xbfffffff40000001ull, 0xdfffffff20000001ull, 0xefffffff10000001ull};
+
+// F[X]/(X^2 - nr)
+struct X2 {
+    uint64_t a, b;
+};
+__device__ __forceinline__ X2 xmul(X2 x, X2 y, uint64_t nr) {
+    return X2{gl::add(gl::mul(x.a, y.a), gl::mul(nr, gl::mul(x.b, y.b))), gl::add(gl::mul(x.a, y.b), gl::mul(x.b, y.a))};
+}
+__device__ __forceinline__ X2 xadd(X2 x, X2 y) { return X2{gl::add(x.a, y.a), gl::add(x.b, y.b)}; }
 
 struct GenArgs {
     uint64_t* wires;
@@ -163,7 +181,101 @@ __device__ __forceinline__ void run_generator(uint64_t* wires, const uint64_t* c
         poseidon_rounds(W, s, g.p[1], g.p[2]);
         break;
     }
+    case SIPP_GEN_ARITHMETIC_EXT: {
+        const uint64_t c0 = K(g.p[1]), c1 = K(g.p[2]), nr = g.p[3];
+        for (uint32_t k = 0; k < g.p[0]; k++) {
+            const uint32_t b = 8 * k;
+            const X2 m = xmul(X2{W(b), W(b + 1)}, X2{W(b + 2), W(b + 3)}, nr);
+            W(b + 6) = gl::add(gl::mul(c0, m.a), gl::mul(c1, W(b + 4)));
+            W(b + 7) = gl::add(gl::mul(c0, m.b), gl::mul(c1, W(b + 5)));
+        }
+        break;
+    }
+    case SIPP_GEN_EXPONENTIATION: {
+        const uint32_t nb = g.p[0];
+        const uint64_t base = W(0);
+        uint64_t prev = 1;
+        for (uint32_t k = 0; k < nb; k++) {
+            const uint64_t bit = W(nb - k);     // any field value: bit base + 1 - bit
+            prev = gl::mul(gl::sqr(prev), gl::sub(gl::add(gl::mul(bit, base), 1), bit));
+            W(2 + nb + k) = prev;
+        }
+        W(1 + nb) = prev;
+        break;
+    }
+    case SIPP_GEN_COSET_INTERPOLATION: {
+        const uint32_t s = g.p[0], d = g.p[1], np = 1u << s, ni = (np - 2) / (d - 1), start = 5 + 2 * np;
+        const uint64_t nr = g.p[2], si = gl::inv(W(0));
+        const X2 sh{gl::mul(W(1 + 2 * np), si), gl::mul(W(2 + 2 * np), si)};
+        W(start + 4 * ni) = sh.a;
+        W(start + 4 * ni + 1) = sh.b;
+        X2 e{0, 0}, q{1, 0};
+        uint32_t bound = d < np ? d : np, c = 0;
+        for (uint32_t k = 0; k < np; k++) {
+            const uint64_t x = w_om16[k << (4 - s)], wt = gl::mul(x, w_ninv[s]);
+            const X2 t{gl::sub(sh.a, x), sh.b}, vw{gl::mul(W(1 + 2 * k), wt), gl::mul(W(2 + 2 * k), wt)};
+            e = xadd(xmul(e, t, nr), xmul(vw, q, nr));
+            q = xmul(q, t, nr);
+            if (k + 1 == bound && k + 1 < np) {     // a chunk ends before the last point: its state is a pair of wires
+                W(start + 2 * c) = e.a;
+                W(start + 2 * c + 1) = e.b;
+                W(start + 2 * ni + 2 * c) = q.a;
+                W(start + 2 * ni + 2 * c + 1) = q.b;
+                c++;
+                bound += d - 1;
+            }
+        }
+        W(3 + 2 * np) = e.a;
+        W(4 + 2 * np) = e.b;
+        break;
+    }
     default: break;
+    }
+}
+
+// SIPP_GEN_COSET_INTERPOLATION on the sixteen lanes of a row (all lanes of the wave call it; act = the row holds the generator): lane k
+// owns point k as the pair (t_k, v_k w_k) = (shifted - x_k, value_k w_k).  Under (T1, E1) (T2, E2) = (T1 T2, E1 T2 + T1 E2), which is
+// associative with the identity (1, 0), the product of the first k + 1 pairs is (q, e) after point k: an inclusive scan in four steps
+// of three extension products gives every chunk boundary at once, where one lane walks 3 n dependent products.  A row's lanes are one
+// DPP row: shuffles of width 16, no LDS, no barrier.  Every lane of the row computes inv(shift) (lanes of a wave share their
+// instructions: one lane alone would take the same time); lanes >= n carry the identity.
+__device__ __forceinline__ void interpolation_lanes(uint64_t* wires, uint32_t n, uint32_t i, uint32_t l, bool act, uint32_t s, uint32_t d,
+                                                    uint64_t nr) {
+    auto W = [&](uint32_t j) -> uint64_t& { return wires[(size_t)j * n + i]; };
+    const uint32_t np = act ? 1u << s : 0, ni = act ? (np - 2) / (d - 1) : 0, start = 5 + 2 * np;
+    X2 T{1, 0}, E{0, 0};
+    if (act) {
+        const uint64_t si = gl::inv(W(0));
+        const X2 sh{gl::mul(W(1 + 2 * np), si), gl::mul(W(2 + 2 * np), si)};
+        if (l == 0) {
+            W(start + 4 * ni) = sh.a;
+            W(start + 4 * ni + 1) = sh.b;
+        }
+        if (l < np) {
+            const uint64_t x = w_om16[l << (4 - s)], wt = gl::mul(x, w_ninv[s]);
+            T = X2{gl::sub(sh.a, x), sh.b};
+            E = X2{gl::mul(W(1 + 2 * l), wt), gl::mul(W(2 + 2 * l), wt)};
+        }
+    }
+#pragma unroll
+    for (uint32_t off = 1; off < 16; off <<= 1) {
+        const X2 Tl{__shfl_up((unsigned long long)T.a, off, 16), __shfl_up((unsigned long long)T.b, off, 16)};
+        const X2 El{__shfl_up((unsigned long long)E.a, off, 16), __shfl_up((unsigned long long)E.b, off, 16)};
+        if (l >= off) {
+            E = xadd(xmul(El, T, nr), xmul(Tl, E, nr));
+            T = xmul(Tl, T, nr);
+        }
+    }
+    if (l >= np) return;
+    if (l == np - 1) {
+        W(3 + 2 * np) = E.a;
+        W(4 + 2 * np) = E.b;
+    } else if (l + 1 >= d && (l + 1 - d) % (d - 1) == 0) {     // the last point of a chunk that is not the last
+        const uint32_t c = (l + 1 - d) / (d - 1);
+        W(start + 2 * c) = E.a;
+        W(start + 2 * c + 1) = E.b;
+        W(start + 2 * ni + 2 * c) = T.a;
+        W(start + 2 * ni + 2 * c + 1) = T.b;
     }
 }
 
@@ -265,7 +377,10 @@ __device__ __forceinline__ bool is_poseidon(uint32_t kind) { return kind == SIPP
 // Poseidon-family generator (the last one whose selector value it holds; any other match runs on lane 0 first), so one level may mix
 // layouts and the two kinds.  On a swap row lanes 0 .. 7 read their element and its partner, lanes 0 .. 3 store the deltas.  (The
 // per-row parameters cost the single-generator case above ~15 % of its level time, so that case keeps its own kernel.)
-__global__ void __launch_bounds__(64) plonk_witness_level_coop_rows_kernel(LevelArgs a) {
+// INTERP: the circuit has a SIPP_GEN_COSET_INTERPOLATION generator; a row that holds it spreads its points over its sixteen lanes
+// (interpolation_lanes) unless one_lane (SIPP_ROUTE_WITNESS_INTERP_ONE_LANE) leaves it to lane 0 with the short families.
+template <bool INTERP>
+__global__ void __launch_bounds__(64) plonk_witness_level_coop_rows_kernel(LevelArgs a, bool one_lane) {
     __shared__ uint64_t sh[4][12];
     const uint32_t grp = threadIdx.x >> 4, l = threadIdx.x & 15, k = blockIdx.x * 4 + grp, n = a.n;
     bool ok = k < a.count;
@@ -275,20 +390,26 @@ __global__ void __launch_bounds__(64) plonk_witness_level_coop_rows_kernel(Level
         ok = false;
         i = 0;
     }
-    int pq = -1;                                              // this row's Poseidon-family generator
-    uint32_t in = 0, out = 0, sb = 0, sw = 0, dl = 0;
+    int pq = -1, iq = -1;                                     // this row's Poseidon-family generator, its sixteen-lane interpolation
+    uint32_t in = 0, out = 0, sb = 0, sw = 0, dl = 0, is = 1, id = 2, inr = 0;
     bool swp = false;
     if (ok) {
-        for (uint32_t q = 0; q < a.n_gens; q++)               // uniform loop: the parameters are picked, never indexed per lane
+        for (uint32_t q = 0; q < a.n_gens; q++) {             // uniform loop: the parameters are picked, never indexed per lane
             if (is_poseidon(a.g[q].kind) && a.consts[(size_t)a.g[q].selector_index * n + i] == a.g[q].row) {
                 pq = (int)q;
                 in = a.g[q].p[0], out = a.g[q].p[1], sb = a.g[q].p[2], sw = a.g[q].p[3], dl = a.g[q].p[4];
                 swp = a.g[q].kind == SIPP_GEN_POSEIDON_SWAP;
             }
+            if (INTERP && !one_lane && a.g[q].kind == SIPP_GEN_COSET_INTERPOLATION &&
+                a.consts[(size_t)a.g[q].selector_index * n + i] == a.g[q].row)
+                iq = (int)q, is = a.g[q].p[0], id = a.g[q].p[1], inr = a.g[q].p[2];
+        }
         if (l == 0)
             for (uint32_t q = 0; q < a.n_gens; q++)
-                if ((int)q != pq && a.consts[(size_t)a.g[q].selector_index * n + i] == a.g[q].row) run_generator(a.wires, a.consts, n, i, a.g[q], a.pih);
+                if ((int)q != pq && (int)q != iq && a.consts[(size_t)a.g[q].selector_index * n + i] == a.g[q].row)
+                    run_generator(a.wires, a.consts, n, i, a.g[q], a.pih);
     }
+    if (INTERP && __syncthreads_or(iq >= 0)) interpolation_lanes(a.wires, n, i, l, iq >= 0, is, id, inr);   // block-uniform
     const bool is_pos = pq >= 0;
     if (!__syncthreads_or(is_pos)) return;                    // block-uniform: no Poseidon row among the four
     const uint32_t e = l < 12 ? l : 0;                        // lanes 12 .. 15 shadow element 0 and never store
@@ -356,6 +477,13 @@ bool layout_ok(const sipp_plonk_generator& g, uint32_t num_wires, uint32_t num_c
     case SIPP_GEN_RANDOM_ACCESS: return g.p[2] >= 1 && g.p[2] <= 6 && g.p[1] >= 2 + (1u << g.p[2]) + g.p[2] && (uint64_t)g.p[0] * g.p[1] <= nw;
     case SIPP_GEN_REDUCING: return 4ull + 3ull * g.p[0] <= nw;
     case SIPP_GEN_POSEIDON: return (uint64_t)g.p[0] + 12 <= nw && (uint64_t)g.p[1] + 12 <= nw && (uint64_t)g.p[2] + 106 <= nw;
+    case SIPP_GEN_ARITHMETIC_EXT: return g.p[0] >= 1 && 8ull * g.p[0] <= nw && g.p[1] < num_constants && g.p[2] < num_constants && g.p[3] != 0;
+    case SIPP_GEN_EXPONENTIATION: return g.p[0] >= 1 && g.p[0] <= 64 && 2ull + 2ull * g.p[0] <= nw;
+    case SIPP_GEN_COSET_INTERPOLATION: {
+        if (g.p[0] < 1 || g.p[0] > 4 || g.p[1] < 2 || g.p[2] == 0) return false;
+        const uint64_t np = 1ull << g.p[0], ni = (np - 2) / (g.p[1] - 1);
+        return 5 + 2 * np + 4 * ni + 2 <= nw;
+    }
     case SIPP_GEN_POSEIDON_SWAP: {
         // written cells (out, sbox, delta) must not meet the read cells (in, swap): the two launch paths read and write in different orders
         const uint64_t in = g.p[0], out = g.p[1], sb = g.p[2], sw = g.p[3], dl = g.p[4];
@@ -372,8 +500,9 @@ bool layout_ok(const sipp_plonk_generator& g, uint32_t num_wires, uint32_t num_c
 
 const char* gen_name(uint32_t kind) {
     static const char* names[] = {"", "witness_arithmetic", "witness_base_split", "witness_constant", "witness_public_input", "witness_u32",
-                                  "witness_random_access", "witness_reducing", "witness_poseidon", "witness_poseidon_swap"};
-    return kind <= SIPP_GEN_POSEIDON_SWAP ? names[kind] : "witness";
+                                  "witness_random_access", "witness_reducing", "witness_poseidon", "witness_poseidon_swap",
+                                  "witness_arithmetic_ext", "witness_exponentiation", "witness_coset_interpolation"};
+    return kind <= SIPP_GEN_COSET_INTERPOLATION ? names[kind] : "witness";
 }
 
 }  // namespace
@@ -451,12 +580,14 @@ extern "C" int sipp_plonk_generate_witness_levels(sipp_ctx* ctx, uint64_t* d_wir
         d_err = reinterpret_cast<int*>(t);
     }
     int pos_gen = -1, n_pos = 0;
-    bool any_swap = false;
+    bool any_swap = false, any_interp = false;
     for (size_t q = 0; q < n_gens; q++) {
         if (gens[q].kind == SIPP_GEN_POSEIDON || gens[q].kind == SIPP_GEN_POSEIDON_SWAP) pos_gen = (int)q, n_pos++;
         any_swap |= gens[q].kind == SIPP_GEN_POSEIDON_SWAP;
+        any_interp |= gens[q].kind == SIPP_GEN_COSET_INTERPOLATION;
     }
-    const bool per_row = any_swap || n_pos > 1;     // the lanes go to each row's own Poseidon-family generator
+    const bool per_row = any_swap || n_pos > 1 || any_interp;     // the lanes go to each row's own Poseidon-family / interpolation generator
+    const bool one_lane = any_interp && (ctx->kernel_routes & SIPP_ROUTE_WITNESS_INTERP_ONE_LANE);
     auto launch_all = [&]() -> hipError_t {
         (void)hipMemsetAsync(d_err, 0, sizeof(int), ctx->stream);
         for (uint32_t l = 0; l < L; l++) {
@@ -468,8 +599,10 @@ extern "C" int sipp_plonk_generate_witness_levels(sipp_ctx* ctx, uint64_t* d_wir
                 for (size_t q = 0; q < n_gens; q++) a.g[q] = gens[q];
                 if (cnt >= COOP_BELOW_ROWS)      // wide level: throughput, one lane per row
                     hipLaunchKernelGGL(plonk_witness_level_kernel, dim3((cnt + 63) / 64), dim3(64), 0, ctx->stream, a);
-                else if (per_row)                // thin level: latency, sixteen lanes per row
-                    hipLaunchKernelGGL(plonk_witness_level_coop_rows_kernel, dim3((cnt + 3) / 4), dim3(64), 0, ctx->stream, a);
+                else if (any_interp)             // thin level: latency, sixteen lanes per row
+                    hipLaunchKernelGGL(plonk_witness_level_coop_rows_kernel<true>, dim3((cnt + 3) / 4), dim3(64), 0, ctx->stream, a, one_lane);
+                else if (per_row)
+                    hipLaunchKernelGGL(plonk_witness_level_coop_rows_kernel<false>, dim3((cnt + 3) / 4), dim3(64), 0, ctx->stream, a, false);
                 else
                     hipLaunchKernelGGL(plonk_witness_level_coop_kernel, dim3((cnt + 3) / 4), dim3(64), 0, ctx->stream, a, pos_gen);
             }
@@ -486,7 +619,7 @@ extern "C" int sipp_plonk_generate_witness_levels(sipp_ctx* ctx, uint64_t* d_wir
         SIPP_CHECK_HIP(ctx, launch_all());
     } else {
         // key: everything the captured kernel arguments hold
-        std::vector<uint64_t> key = {(uint64_t)(uintptr_t)d_wires, (uint64_t)(uintptr_t)d_constants, log_n, num_wires, num_constants, n_gens, L,
+        std::vector<uint64_t> key = {(uint64_t)(uintptr_t)d_wires, (uint64_t)(uintptr_t)d_constants, log_n, num_wires, num_constants, n_gens, L, one_lane,
                                      (uint64_t)(uintptr_t)sched->d_rows, (uint64_t)(uintptr_t)sched->d_copy_src, (uint64_t)(uintptr_t)sched->d_copy_dst};
         for (int q = 0; q < 4; q++) key.push_back(public_inputs_hash ? public_inputs_hash[q] : 0);
         for (size_t q = 0; q < n_gens; q++) {
