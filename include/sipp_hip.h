@@ -128,11 +128,15 @@ int sipp_ctx_create_checked(sipp_ctx **out, int device, const sipp_stark_config 
  *   SIPP_ROUTE_WITNESS_INTERP_ONE_LANE  on thin levels a SIPP_GEN_COSET_INTERPOLATION row runs on lane 0 of its sixteen lanes instead of the
  *                                  sixteen-lane scan (one point per lane).  Bit 8 stays unassigned: the setter refuses it as an unknown
  *                                  bit, which tests/test_gpu_stark.py holds it to
+ *   SIPP_ROUTE_WITNESS_REDUCE_ONE_LANE  on thin levels of a circuit with a SIPP_GEN_REDUCING_EXT or SIPP_GEN_QUOTIENT_EXT generator, a
+ *                                  SIPP_GEN_REDUCING / _REDUCING_EXT row runs on lane 0 of its sixteen lanes instead of the sixteen-lane scan
+ *                                  (a chunk of ceil(K / 16) coefficients per lane).  Circuits without such a generator never take the scan
  * Only while no proof is in flight on the ctx. */
 #define SIPP_ROUTE_OPENINGS_UNGROUPED 1u
 #define SIPP_ROUTE_LDE_COLUMN_WIDE 2u
 #define SIPP_ROUTE_WITNESS_NO_GRAPH 4u
 #define SIPP_ROUTE_WITNESS_INTERP_ONE_LANE 16u
+#define SIPP_ROUTE_WITNESS_REDUCE_ONE_LANE 32u
 int sipp_ctx_set_kernel_routes(sipp_ctx *ctx, uint32_t routes);
 void sipp_ctx_destroy(sipp_ctx *ctx);
 /* The ctx's HIP stream: level > 0 = a stream of the highest priority the device offers; level <= 0 = a stream with a hardware
@@ -490,7 +494,17 @@ int sipp_plonk_prove_gates(sipp_ctx *ctx, const uint64_t *d_wires, const uint64_
  *                                                                       is min(d, n) points, the others d - 1; the state after every chunk but
  *                                                                       the last goes to intermediate c, the last e to the evaluation value
  *                                                                                                                          (InterpolationGenerator)
- * The three families above take ANY field value in every input cell; W != 0.
+ *   SIPP_GEN_REDUCING_EXT   p = K (>= 1), W                             SIPP_GEN_REDUCING with extension coefficients: alpha (2) at 0, old acc (2)
+ *                                                                       at 2, K coefficients (2 each) from 4, K accumulators (2 each) from
+ *                                                                       4 + 2K: acc_i = acc_(i-1) alpha + c_i              (ReducingExtensionGenerator)
+ *   SIPP_GEN_QUOTIENT_EXT   p = n_ops, const col c0, const col c1, W    on a row of SIPP_GEN_ARITHMETIC_EXT's shape (out = c0 a m + c1 c per op at
+ *                                                                       b = 8k): READS a = (w[b], w[b+1]), c = (w[b+4], w[b+5]) and out =
+ *                                                                       (w[b+6], w[b+7]), WRITES the multiplicand (w[b+2], w[b+3]) =
+ *                                                                       (out - c1 c) inv(c0 a), inv(x0 + x1 X) = (x0 - x1 X) inv(x0^2 - W x1^2)
+ *                                                                       with inv(0) = 0: a = 0, c0 = 0, or an a of zero norm under a residue W
+ *                                                                       all write (0, 0).  The constraints, not the generator, refuse such
+ *                                                                       rows (they hold only if out = c1 c)               (QuotientGeneratorExtension)
+ * The five families above take ANY field value in every input cell; W != 0.
  * Defined behaviour outside a gate's range (the constraints, not the generators, refuse such rows): BASE_SPLIT drops the bits of w[0] at
  * and above n_limbs * bits; U32_MUL_ADD takes the low 32 bits of an operand that is not a u32, and with a stride wider than 5 + 2 limbs
  * the cells behind an op's limbs stay untouched; RANDOM_ACCESS with an index >= 2^bits selects by the low `bits` bits of the index.
@@ -509,6 +523,8 @@ int sipp_plonk_prove_gates(sipp_ctx *ctx, const uint64_t *d_wires, const uint64_
 #define SIPP_GEN_ARITHMETIC_EXT 10
 #define SIPP_GEN_EXPONENTIATION 11
 #define SIPP_GEN_COSET_INTERPOLATION 12
+#define SIPP_GEN_REDUCING_EXT 13
+#define SIPP_GEN_QUOTIENT_EXT 14
 typedef struct {
     uint32_t kind, selector_index, row;
     uint32_t p[5];

@@ -122,10 +122,15 @@ pub struct SippPlonkCircuit {
 
 /// sipp_ctx_set_kernel_routes: a thin level's interpolation rows on lane 0 instead of the sixteen-lane scan
 pub const SIPP_ROUTE_WITNESS_INTERP_ONE_LANE: u32 = 16;
+/// sipp_ctx_set_kernel_routes: a thin level's reducing rows (kinds 7 and 13) on lane 0 instead of the sixteen-lane scan
+pub const SIPP_ROUTE_WITNESS_REDUCE_ONE_LANE: u32 = 32;
 /// SIPP_GEN_*: the extension-field arithmetic, exponentiation and coset-interpolation generators (p[] as in include/sipp_hip.h)
 pub const SIPP_GEN_ARITHMETIC_EXT: u32 = 10;
 pub const SIPP_GEN_EXPONENTIATION: u32 = 11;
 pub const SIPP_GEN_COSET_INTERPOLATION: u32 = 12;
+/// SIPP_GEN_*: FRI's initial combination: the reduction of extension coefficients and the quotient generator of an ArithmeticExt row
+pub const SIPP_GEN_REDUCING_EXT: u32 = 13;
+pub const SIPP_GEN_QUOTIENT_EXT: u32 = 14;
 
 /// one gate family's witness generator with its layout (include/sipp_hip.h, "WITNESS GENERATORS"): kind = SIPP_GEN_*
 #[repr(C)]

@@ -130,7 +130,7 @@ int sipp_ctx_create_checked(sipp_ctx** out, int device, const sipp_stark_config*
 
 int sipp_ctx_set_kernel_routes(sipp_ctx* ctx, uint32_t routes) {
     if (!ctx || (routes & ~(uint32_t)(SIPP_ROUTE_OPENINGS_UNGROUPED | SIPP_ROUTE_LDE_COLUMN_WIDE | SIPP_ROUTE_WITNESS_NO_GRAPH |
-                                     SIPP_ROUTE_WITNESS_INTERP_ONE_LANE))) return SIPP_E_BADARG;
+                                     SIPP_ROUTE_WITNESS_INTERP_ONE_LANE | SIPP_ROUTE_WITNESS_REDUCE_ONE_LANE))) return SIPP_E_BADARG;
     std::unique_lock<std::mutex> lk(ctx->async.mu);
     if (ctx->async.has_job) {
         lk.unlock();

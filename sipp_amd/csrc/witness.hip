@@ -17,6 +17,9 @@
 // The FRI fold's families (recalled gates/arithmetic_extension.rs, exponentiation.rs, coset_interpolation.rs) work over F[X]/(X^2 - W), W
 // passed as data: SIPP_GEN_ARITHMETIC_EXT, SIPP_GEN_EXPONENTIATION, and SIPP_GEN_COSET_INTERPOLATION, the barycentric evaluation of the
 // polynomial through n = 2^s values on the coset shift * <g> at a point, in chunks whose partial states are wires.
+// FRI's initial combination (recalled gates/reducing_extension.rs, and gadgets/arithmetic_extension.rs div_add_extension with its
+// QuotientGeneratorExtension) adds SIPP_GEN_REDUCING_EXT, the reduction of extension coefficients, and SIPP_GEN_QUOTIENT_EXT, which fills
+// the multiplicand of an ArithmeticExtension-shaped row from its output: the one generator here that inverts.
 #include "ctx.hpp"
 #include "poseidon_constants.h"
 #include <mutex>
@@ -41,6 +44,11 @@ __device__ __forceinline__ X2 xmul(X2 x, X2 y, uint64_t nr) {
     return X2{gl::add(gl::mul(x.a, y.a), gl::mul(nr, gl::mul(x.b, y.b))), gl::add(gl::mul(x.a, y.b), gl::mul(x.b, y.a))};
 }
 __device__ __forceinline__ X2 xadd(X2 x, X2 y) { return X2{gl::add(x.a, y.a), gl::add(x.b, y.b)}; }
+// (x.a - x.b X) inv(x.a^2 - nr x.b^2); gl::inv(0) = 0: zero, and an element of zero norm under a residue nr, give (0, 0)
+__device__ __forceinline__ X2 xinv(X2 x, uint64_t nr) {
+    const uint64_t ni = gl::inv(gl::sub(gl::mul(x.a, x.a), gl::mul(nr, gl::mul(x.b, x.b))));
+    return X2{gl::mul(x.a, ni), gl::mul(gl::sub(0, x.b), ni)};
+}
 
 struct GenArgs {
     uint64_t* wires;
@@ -229,7 +237,71 @@ __device__ __forceinline__ void run_generator(uint64_t* wires, const uint64_t* c
         W(4 + 2 * np) = e.b;
         break;
     }
+    case SIPP_GEN_REDUCING_EXT: {
+        const uint32_t Kc = g.p[0];
+        const uint64_t nr = g.p[1];
+        const X2 al{W(0), W(1)};
+        X2 acc{W(2), W(3)};
+        for (uint32_t l = 0; l < Kc; l++) {
+            acc = xadd(xmul(acc, al, nr), X2{W(4 + 2 * l), W(5 + 2 * l)});
+            W(4 + 2 * Kc + 2 * l) = acc.a;
+            W(5 + 2 * Kc + 2 * l) = acc.b;
+        }
+        break;
+    }
+    case SIPP_GEN_QUOTIENT_EXT: {
+        const uint64_t c0 = K(g.p[1]), c1 = K(g.p[2]), nr = g.p[3];
+        for (uint32_t k = 0; k < g.p[0]; k++) {
+            const uint32_t b = 8 * k;
+            // (out - c1 c) inv(c0 a): a zero denominator writes (0, 0), and the row's constraints hold only if out = c1 c
+            const X2 num{gl::sub(W(b + 6), gl::mul(c1, W(b + 4))), gl::sub(W(b + 7), gl::mul(c1, W(b + 5)))};
+            const X2 m = xmul(num, xinv(X2{gl::mul(c0, W(b)), gl::mul(c0, W(b + 1))}, nr), nr);
+            W(b + 2) = m.a;
+            W(b + 3) = m.b;
+        }
+        break;
+    }
     default: break;
+    }
+}
+
+// SIPP_GEN_REDUCING / SIPP_GEN_REDUCING_EXT on the sixteen lanes of a row (all lanes of the wave call it; act = the row holds the
+// generator, ext = its coefficients are extension elements): lane l owns the chunk of m = ceil(K / 16) consecutive coefficients from
+// l m as the affine map acc -> acc M + C, (M, C) = (alpha^len, Horner of the chunk from 0).  Under (M1, C1) (M2, C2) = (M1 M2, C1 M2 + C2),
+// associative with the identity (1, 0), an inclusive scan in four steps of two independent extension products gives every lane the map
+// of everything up to its chunk's end; the lane takes the map before its chunk from its neighbour, applies it to the old accumulator
+// and replays its chunk, storing the accumulators: about 2 m + 5 dependent products where one lane walks K.  Shuffles of width 16, no
+// LDS, no barrier.  The coefficients are read twice (the second time from cache): K has no bound that registers could hold.
+__device__ __forceinline__ void reducing_lanes(uint64_t* wires, uint32_t n, uint32_t i, uint32_t l, bool act, bool ext, uint32_t Kc,
+                                               uint64_t nr) {
+    auto W = [&](uint32_t j) -> uint64_t& { return wires[(size_t)j * n + i]; };
+    const uint32_t m = (Kc + 15) / 16, first = l * m, cnt = !act || first >= Kc ? 0 : (Kc - first < m ? Kc - first : m);
+    auto coef = [&](uint32_t j) -> X2 { return ext ? X2{W(4 + 2 * j), W(5 + 2 * j)} : X2{W(4 + j), 0}; };
+    const X2 al = act ? X2{W(0), W(1)} : X2{0, 0};
+    X2 M{1, 0}, C{0, 0};
+    for (uint32_t t = 0; t < cnt; t++) {
+        C = xadd(xmul(C, al, nr), coef(first + t));
+        M = xmul(M, al, nr);
+    }
+#pragma unroll
+    for (uint32_t off = 1; off < 16; off <<= 1) {
+        const X2 Ml{__shfl_up((unsigned long long)M.a, off, 16), __shfl_up((unsigned long long)M.b, off, 16)};
+        const X2 Cl{__shfl_up((unsigned long long)C.a, off, 16), __shfl_up((unsigned long long)C.b, off, 16)};
+        if (l >= off) {
+            C = xadd(xmul(Cl, M, nr), C);
+            M = xmul(Ml, M, nr);
+        }
+    }
+    X2 Me{__shfl_up((unsigned long long)M.a, 1, 16), __shfl_up((unsigned long long)M.b, 1, 16)};
+    X2 Ce{__shfl_up((unsigned long long)C.a, 1, 16), __shfl_up((unsigned long long)C.b, 1, 16)};
+    if (l == 0) Me = X2{1, 0}, Ce = X2{0, 0};
+    if (!cnt) return;
+    const uint32_t accs = ext ? 4 + 2 * Kc : 4 + Kc;
+    X2 acc = xadd(xmul(X2{W(2), W(3)}, Me, nr), Ce);
+    for (uint32_t t = 0; t < cnt; t++) {
+        acc = xadd(xmul(acc, al, nr), coef(first + t));
+        W(accs + 2 * (first + t)) = acc.a;
+        W(accs + 2 * (first + t) + 1) = acc.b;
     }
 }
 
@@ -379,8 +451,12 @@ __device__ __forceinline__ bool is_poseidon(uint32_t kind) { return kind == SIPP
 // per-row parameters cost the single-generator case above ~15 % of its level time, so that case keeps its own kernel.)
 // INTERP: the circuit has a SIPP_GEN_COSET_INTERPOLATION generator; a row that holds it spreads its points over its sixteen lanes
 // (interpolation_lanes) unless one_lane (SIPP_ROUTE_WITNESS_INTERP_ONE_LANE) leaves it to lane 0 with the short families.
-template <bool INTERP>
-__global__ void __launch_bounds__(64) plonk_witness_level_coop_rows_kernel(LevelArgs a, bool one_lane) {
+// REDUCE: the circuit has a SIPP_GEN_REDUCING_EXT or SIPP_GEN_QUOTIENT_EXT generator (FRI's initial combination, whose reducing rows are
+// a query's longest chain); a row that holds SIPP_GEN_REDUCING or _REDUCING_EXT spreads its coefficients over its sixteen lanes
+// (reducing_lanes) unless reduce_one_lane (SIPP_ROUTE_WITNESS_REDUCE_ONE_LANE).  It implies INTERP's code: an interpolation generator
+// may or may not be there.
+template <bool INTERP, bool REDUCE>
+__global__ void __launch_bounds__(64) plonk_witness_level_coop_rows_kernel(LevelArgs a, bool one_lane, bool reduce_one_lane) {
     __shared__ uint64_t sh[4][12];
     const uint32_t grp = threadIdx.x >> 4, l = threadIdx.x & 15, k = blockIdx.x * 4 + grp, n = a.n;
     bool ok = k < a.count;
@@ -390,9 +466,9 @@ __global__ void __launch_bounds__(64) plonk_witness_level_coop_rows_kernel(Level
         ok = false;
         i = 0;
     }
-    int pq = -1, iq = -1;                                     // this row's Poseidon-family generator, its sixteen-lane interpolation
-    uint32_t in = 0, out = 0, sb = 0, sw = 0, dl = 0, is = 1, id = 2, inr = 0;
-    bool swp = false;
+    int pq = -1, iq = -1, rq = -1;                            // this row's Poseidon-family generator, its sixteen-lane interpolation / reduction
+    uint32_t in = 0, out = 0, sb = 0, sw = 0, dl = 0, is = 1, id = 2, inr = 0, rk = 0, rnr = 0;
+    bool swp = false, rext = false;
     if (ok) {
         for (uint32_t q = 0; q < a.n_gens; q++) {             // uniform loop: the parameters are picked, never indexed per lane
             if (is_poseidon(a.g[q].kind) && a.consts[(size_t)a.g[q].selector_index * n + i] == a.g[q].row) {
@@ -403,13 +479,17 @@ __global__ void __launch_bounds__(64) plonk_witness_level_coop_rows_kernel(Level
             if (INTERP && !one_lane && a.g[q].kind == SIPP_GEN_COSET_INTERPOLATION &&
                 a.consts[(size_t)a.g[q].selector_index * n + i] == a.g[q].row)
                 iq = (int)q, is = a.g[q].p[0], id = a.g[q].p[1], inr = a.g[q].p[2];
+            if (REDUCE && !reduce_one_lane && (a.g[q].kind == SIPP_GEN_REDUCING || a.g[q].kind == SIPP_GEN_REDUCING_EXT) &&
+                a.consts[(size_t)a.g[q].selector_index * n + i] == a.g[q].row)
+                rq = (int)q, rk = a.g[q].p[0], rnr = a.g[q].p[1], rext = a.g[q].kind == SIPP_GEN_REDUCING_EXT;
         }
         if (l == 0)
             for (uint32_t q = 0; q < a.n_gens; q++)
-                if ((int)q != pq && (int)q != iq && a.consts[(size_t)a.g[q].selector_index * n + i] == a.g[q].row)
+                if ((int)q != pq && (int)q != iq && (int)q != rq && a.consts[(size_t)a.g[q].selector_index * n + i] == a.g[q].row)
                     run_generator(a.wires, a.consts, n, i, a.g[q], a.pih);
     }
     if (INTERP && __syncthreads_or(iq >= 0)) interpolation_lanes(a.wires, n, i, l, iq >= 0, is, id, inr);   // block-uniform
+    if (REDUCE && __syncthreads_or(rq >= 0)) reducing_lanes(a.wires, n, i, l, rq >= 0, rext, rk, rnr);      // block-uniform
     const bool is_pos = pq >= 0;
     if (!__syncthreads_or(is_pos)) return;                    // block-uniform: no Poseidon row among the four
     const uint32_t e = l < 12 ? l : 0;                        // lanes 12 .. 15 shadow element 0 and never store
@@ -484,6 +564,8 @@ bool layout_ok(const sipp_plonk_generator& g, uint32_t num_wires, uint32_t num_c
         const uint64_t np = 1ull << g.p[0], ni = (np - 2) / (g.p[1] - 1);
         return 5 + 2 * np + 4 * ni + 2 <= nw;
     }
+    case SIPP_GEN_REDUCING_EXT: return g.p[0] >= 1 && 4ull + 4ull * g.p[0] <= nw && g.p[1] != 0;
+    case SIPP_GEN_QUOTIENT_EXT: return g.p[0] >= 1 && 8ull * g.p[0] <= nw && g.p[1] < num_constants && g.p[2] < num_constants && g.p[3] != 0;
     case SIPP_GEN_POSEIDON_SWAP: {
         // written cells (out, sbox, delta) must not meet the read cells (in, swap): the two launch paths read and write in different orders
         const uint64_t in = g.p[0], out = g.p[1], sb = g.p[2], sw = g.p[3], dl = g.p[4];
@@ -501,8 +583,9 @@ bool layout_ok(const sipp_plonk_generator& g, uint32_t num_wires, uint32_t num_c
 const char* gen_name(uint32_t kind) {
     static const char* names[] = {"", "witness_arithmetic", "witness_base_split", "witness_constant", "witness_public_input", "witness_u32",
                                   "witness_random_access", "witness_reducing", "witness_poseidon", "witness_poseidon_swap",
-                                  "witness_arithmetic_ext", "witness_exponentiation", "witness_coset_interpolation"};
-    return kind <= SIPP_GEN_COSET_INTERPOLATION ? names[kind] : "witness";
+                                  "witness_arithmetic_ext", "witness_exponentiation", "witness_coset_interpolation",
+                                  "witness_reducing_ext", "witness_quotient_ext"};
+    return kind <= SIPP_GEN_QUOTIENT_EXT ? names[kind] : "witness";
 }
 
 }  // namespace
@@ -580,14 +663,17 @@ extern "C" int sipp_plonk_generate_witness_levels(sipp_ctx* ctx, uint64_t* d_wir
         d_err = reinterpret_cast<int*>(t);
     }
     int pos_gen = -1, n_pos = 0;
-    bool any_swap = false, any_interp = false;
+    bool any_swap = false, any_interp = false, any_initial = false;
     for (size_t q = 0; q < n_gens; q++) {
         if (gens[q].kind == SIPP_GEN_POSEIDON || gens[q].kind == SIPP_GEN_POSEIDON_SWAP) pos_gen = (int)q, n_pos++;
         any_swap |= gens[q].kind == SIPP_GEN_POSEIDON_SWAP;
         any_interp |= gens[q].kind == SIPP_GEN_COSET_INTERPOLATION;
+        any_initial |= gens[q].kind == SIPP_GEN_REDUCING_EXT || gens[q].kind == SIPP_GEN_QUOTIENT_EXT;
     }
     const bool per_row = any_swap || n_pos > 1 || any_interp;     // the lanes go to each row's own Poseidon-family / interpolation generator
     const bool one_lane = any_interp && (ctx->kernel_routes & SIPP_ROUTE_WITNESS_INTERP_ONE_LANE);
+    // only a circuit of FRI's initial combination takes the sixteen-lane reduction: every other circuit launches what it always did
+    const bool reduce_one_lane = any_initial && (ctx->kernel_routes & SIPP_ROUTE_WITNESS_REDUCE_ONE_LANE);
     auto launch_all = [&]() -> hipError_t {
         (void)hipMemsetAsync(d_err, 0, sizeof(int), ctx->stream);
         for (uint32_t l = 0; l < L; l++) {
@@ -599,10 +685,15 @@ extern "C" int sipp_plonk_generate_witness_levels(sipp_ctx* ctx, uint64_t* d_wir
                 for (size_t q = 0; q < n_gens; q++) a.g[q] = gens[q];
                 if (cnt >= COOP_BELOW_ROWS)      // wide level: throughput, one lane per row
                     hipLaunchKernelGGL(plonk_witness_level_kernel, dim3((cnt + 63) / 64), dim3(64), 0, ctx->stream, a);
-                else if (any_interp)             // thin level: latency, sixteen lanes per row
-                    hipLaunchKernelGGL(plonk_witness_level_coop_rows_kernel<true>, dim3((cnt + 3) / 4), dim3(64), 0, ctx->stream, a, one_lane);
+                else if (any_initial)            // thin level: latency, sixteen lanes per row
+                    hipLaunchKernelGGL((plonk_witness_level_coop_rows_kernel<true, true>), dim3((cnt + 3) / 4), dim3(64), 0, ctx->stream, a, one_lane,
+                                       reduce_one_lane);
+                else if (any_interp)
+                    hipLaunchKernelGGL((plonk_witness_level_coop_rows_kernel<true, false>), dim3((cnt + 3) / 4), dim3(64), 0, ctx->stream, a, one_lane,
+                                       false);
                 else if (per_row)
-                    hipLaunchKernelGGL(plonk_witness_level_coop_rows_kernel<false>, dim3((cnt + 3) / 4), dim3(64), 0, ctx->stream, a, false);
+                    hipLaunchKernelGGL((plonk_witness_level_coop_rows_kernel<false, false>), dim3((cnt + 3) / 4), dim3(64), 0, ctx->stream, a, false,
+                                       false);
                 else
                     hipLaunchKernelGGL(plonk_witness_level_coop_kernel, dim3((cnt + 3) / 4), dim3(64), 0, ctx->stream, a, pos_gen);
             }
@@ -619,7 +710,8 @@ extern "C" int sipp_plonk_generate_witness_levels(sipp_ctx* ctx, uint64_t* d_wir
         SIPP_CHECK_HIP(ctx, launch_all());
     } else {
         // key: everything the captured kernel arguments hold
-        std::vector<uint64_t> key = {(uint64_t)(uintptr_t)d_wires, (uint64_t)(uintptr_t)d_constants, log_n, num_wires, num_constants, n_gens, L, one_lane,
+        std::vector<uint64_t> key = {(uint64_t)(uintptr_t)d_wires, (uint64_t)(uintptr_t)d_constants, log_n, num_wires, num_constants, n_gens, L,
+                                     (uint64_t)one_lane | ((uint64_t)reduce_one_lane << 1),
                                      (uint64_t)(uintptr_t)sched->d_rows, (uint64_t)(uintptr_t)sched->d_copy_src, (uint64_t)(uintptr_t)sched->d_copy_dst};
         for (int q = 0; q < 4; q++) key.push_back(public_inputs_hash ? public_inputs_hash[q] : 0);
         for (size_t q = 0; q < n_gens; q++) {

@@ -21,7 +21,7 @@ Exponentiation row gives (g^-1)^rev(within), an arithmetic op multiplies it by x
 bit-reversed order and beta_r, its evaluation value is the next `old`; arity_bits squarings of x; the index drops its low arity_bits bits.
 ArithmeticExt rows then evaluate the final polynomial at (x, 0) by Horner; the result is the last `old`.
 
-Out of scope: fri_combine_initial (the first `old` is a public input); the Merkle paths of the opened cosets (MerkleOpeningCircuit's job);
+Out of scope: fri_combine_initial (the first `old` is a public input; sipp_amd/fri_initial.py proves it); the Merkle paths of the opened cosets (MerkleOpeningCircuit's job);
 the proof of work; mixed arities (one arity for every round: plonky2's ConstantArityBits).
 
 numpy only; imports nothing from the test oracle."""
