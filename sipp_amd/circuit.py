@@ -1,0 +1,389 @@
+"""What the outer prover's statement circuits (sipp_amd/merkle.py, fri_fold.py, fri_initial.py) share: the field and program helpers, the
+gate programs more than one of them uses, the builder that turns rows and feeds into what the prover takes, and the prover wrapper.
+
+  _gl_mul, _powers, ...     Goldilocks over numpy (sigmas only); _Prog, the program words of sipp_plonk_circuit; _Cells, the union-find
+                            whose sets become the permutation cycles
+  GEN_*                     include/sipp_hip.h SIPP_GEN_*
+  public_input_into, constant_into, base_sum_into, random_access_into
+                            the gate programs without a home of their own; the Poseidon swap gate is sipp_amd/merkle.py's, arithmetic-ext,
+                            exponentiation and coset interpolation are sipp_amd/fri_fold.py's, the reducing gates sipp_amd/fri_initial.py's
+  CircuitBuilder            the gate registry (selector groups, programs, generators); rows by new_row(); wiring by place(), which ties
+                            the cells, schedules the copies and gives every row the level behind its latest computed source, and tie();
+                            the public-input Poseidon chain; finish(), which fixes N and makes the cycles and the level schedule.  A
+                            circuit is a subclass: it declares its gates, writes its statement as builder calls and finishes
+  CircuitProver             a built circuit through the library's CircuitData
+
+numpy only; imports nothing from the test oracle."""
+import numpy as np
+
+P = 0xFFFFFFFF00000001
+PP = np.uint64(P)
+M32 = np.uint64(0xFFFFFFFF)
+EPS = np.uint64(0xFFFFFFFF)
+UNUSED = 0xFFFFFFFF
+
+# include/sipp_hip.h SIPP_GEN_*
+GEN_BASE_SPLIT, GEN_CONSTANT, GEN_PUBLIC_INPUT, GEN_RANDOM_ACCESS, GEN_REDUCING, GEN_POSEIDON_SWAP = 2, 3, 4, 6, 7, 9
+GEN_ARITHMETIC_EXT, GEN_EXPONENTIATION, GEN_COSET_INTERPOLATION, GEN_REDUCING_EXT, GEN_QUOTIENT_EXT = 10, 11, 12, 13, 14
+# program factor kinds
+_W, _K, _PIH = 0, 1, 2
+# upstream's PoseidonGate layout (SIPP_GEN_POSEIDON_SWAP): 135 wires
+SWAP_LAYOUT = {"in_": 0, "out": 12, "swap": 24, "delta": 25, "sbox": 29}
+# the gates every circuit starts with (CircuitBuilder.declare_basic)
+NOOP, PUBLIC_INPUT, CONSTANT, BASE_SUM = range(4)
+
+
+# ---- Goldilocks over numpy (sigmas only) ----------------------------------------------------------------------------------------------
+def _gl_mul(a, b):
+    a = np.asarray(a, dtype=np.uint64)
+    b = np.asarray(b, dtype=np.uint64)
+    a0, a1, b0, b1 = a & M32, a >> np.uint64(32), b & M32, b >> np.uint64(32)
+    ll, lh, hl, hh = a0 * b0, a0 * b1, a1 * b0, a1 * b1
+    mid = lh + hl
+    cmid = (mid < lh).astype(np.uint64)
+    lo = ll + (mid << np.uint64(32))
+    clo = (lo < ll).astype(np.uint64)
+    hi = hh + (mid >> np.uint64(32)) + (cmid << np.uint64(32)) + clo
+    h0, h1 = hi & M32, hi >> np.uint64(32)
+    t0 = lo - h1
+    t0 = np.where(lo < h1, t0 - EPS, t0)
+    t1 = (h0 << np.uint64(32)) - h0
+    r = t0 + t1
+    r = np.where(r < t1, r + EPS, r)
+    return np.where(r >= PP, r - PP, r)
+
+
+def _powers(base, n):
+    out = np.ones(n, dtype=np.uint64)
+    m, b = 1, int(base)
+    while m < n:
+        out[m:2 * m] = _gl_mul(out[:m], np.uint64(b))
+        b = b * b % P
+        m *= 2
+    return out
+
+
+def _root_of_unity(log_n):
+    return pow(1753635133440165772, 1 << (32 - log_n), P)
+
+
+def _i64(c):
+    c %= P
+    return c if c < (1 << 63) else c - P
+
+
+class _Prog:
+    """program words of sipp_plonk_circuit: per constraint n_mono, then per monomial coef, n_factors, (kind, index) x n_factors"""
+
+    def __init__(self):
+        self.words = []
+        self.count = 0
+
+    def constraint(self, monos):
+        merged = {}
+        for coef, factors in monos:
+            key = tuple(sorted(factors))
+            merged[key] = (merged.get(key, 0) + coef) % P
+        items = [(c, k) for k, c in merged.items() if c]
+        self.words.append(len(items))
+        for coef, factors in items:
+            self.words.extend([_i64(coef), len(factors)])
+            for kind, idx in factors:
+                self.words.extend([kind, idx])
+        self.count += 1
+
+
+def _words(fill, *args):
+    pr = _Prog()
+    fill(pr, *args)
+    return pr, np.array(pr.words, dtype=np.int64)
+
+
+class _Cells:
+    """union-find over cells: every set of tied cells becomes one permutation cycle"""
+
+    def __init__(self):
+        self.parent = {}
+
+    def find(self, x):
+        p = self.parent.setdefault(x, x)
+        while p != self.parent[p]:
+            self.parent[p] = self.parent[self.parent[p]]
+            p = self.parent[p]
+        self.parent[x] = p
+        return p
+
+    def tie(self, a, b):
+        ra, rb = self.find(a), self.find(b)
+        if ra != rb:
+            self.parent[max(ra, rb)] = min(ra, rb)
+
+    def groups(self):
+        out = {}
+        for x in sorted(self.parent):
+            out.setdefault(self.find(x), []).append(x)
+        return out
+
+
+def fri_params(log_n, rate_bits=3, cap_height=4, pow_bits=16, num_queries=28, arity_bits=4, final_poly_bits=5):
+    """sipp_fri_params with plonky2's ConstantArityBits(arity_bits, final_poly_bits) reduction for degree_bits = log_n"""
+    from . import _lib
+    p = _lib.FriParams()
+    p.rate_bits, p.cap_height, p.pow_bits, p.num_queries, p.pow_rule, p.hiding = rate_bits, cap_height, pow_bits, num_queries, 0, 0
+    d, k = log_n, 0
+    while d > final_poly_bits and d + rate_bits - arity_bits >= cap_height and d >= arity_bits and k < 32:
+        p.arity_bits[k] = arity_bits
+        d -= arity_bits
+        k += 1
+    p.n_rounds = k
+    return p
+
+
+# ---- the gate programs more than one circuit uses ---------------------------------------------------------------------------------------
+def public_input_into(pr):
+    for i in range(4):
+        pr.constraint([(1, [(_W, i)]), (-1, [(_PIH, i)])])
+
+
+def constant_into(pr, k0):
+    pr.constraint([(1, [(_W, 0)]), (-1, [(_K, k0)])])
+
+
+def base_sum_into(pr, n_bits):
+    """1-bit limbs: the sum, then every limb's booleanity"""
+    pr.constraint([(1 << i, [(_W, 1 + i)]) for i in range(n_bits)] + [(-1, [(_W, 0)])])
+    for i in range(n_bits):
+        pr.constraint([(1, [(_W, 1 + i), (_W, 1 + i)]), (-1, [(_W, 1 + i)])])
+
+
+def random_access_into(pr, copies, stride, bits):
+    """per copy at b = stride cp: index, claimed, 2^bits items, `bits` bits (SIPP_GEN_RANDOM_ACCESS); degree bits + 1"""
+    ln = 1 << bits
+    for cp in range(copies):
+        b = stride * cp
+        bit = [(_W, b + 2 + ln + l) for l in range(bits)]
+        for x in bit:
+            pr.constraint([(1, [x, x]), (-1, [x])])
+        pr.constraint([(1 << l, [bit[l]]) for l in range(bits)] + [(-1, [(_W, b)])])
+        # the folded list: sum_j item_j prod_l (bit_l if bit l of j else 1 - bit_l), expanded into monomials
+        monos = []
+        for j in range(ln):
+            terms = [(1, [(_W, b + 2 + j)])]
+            for l in range(bits):
+                if (j >> l) & 1:
+                    terms = [(c, f + [bit[l]]) for c, f in terms]
+                else:
+                    terms = [t for c, f in terms for t in ((c, f), (-c, f + [bit[l]]))]
+            monos += terms
+        pr.constraint(monos + [(-1, [(_W, b + 1)])])
+
+
+def pi(t):
+    """public input t as a source of place()"""
+    return ("pi", t)
+
+
+class CircuitBuilder:
+    """Gates, rows and wiring of one circuit.  A cell is (wire, row) until finish() knows N, then wire * N + row.  A source of place()
+    is pi(t) or the cell of a row placed before: a row that reads a cell before a generator can have written it does not build."""
+
+    def __init__(self, num_wires, num_routed, gate_names, gate_group, n_constants, n_pi):
+        """gate_group: the selector group of every gate, ascending; n_constants: the constant columns behind the selector columns"""
+        assert len(gate_names) == len(gate_group) and list(gate_group) == sorted(gate_group) and n_constants in (1, 2)
+        self.num_wires, self.num_routed, self.gate_names, self.n_pi = num_wires, num_routed, gate_names, n_pi
+        self.n_pi_rows = -(-n_pi // 8)
+        lay = SWAP_LAYOUT
+        self.s_in, self.s_out, self.s_swap, self.s_delta, self.s_sbox = lay["in_"], lay["out"], lay["swap"], lay["delta"], lay["sbox"]
+        self.num_selectors = gate_group[-1] + 1
+        self.num_constants = self.num_selectors + n_constants
+        self.k0, self.k1 = self.num_selectors, self.num_selectors + 1          # the constant columns (k1: if there are two)
+        # selector groups [lo, hi): filter degree (hi - lo - 1) + 1, and with the gate's degree at most 8
+        self.groups = [(gate_group.index(g), gate_group.index(g) + gate_group.count(g)) for g in range(self.num_selectors)]
+        self._group, self._prog, self.gates, self._generators = gate_group, _Prog(), [], []
+        self._rows, self._level = [], {}                        # row -> (gate, c0, c1); row -> level
+        self._uf, self._copies = _Cells(), []                   # copies: (level of the source, src cell, dst cell)
+        self._pi_cells = [None] * n_pi                          # one cell of public input t: every cell of its cycle takes its value
+
+    # ---- gates ----
+    def declare(self, index, degree, gen=None, fill=None, *args):
+        """the next gate: gen = (kind, p0, ...) is its generator's tuple without (selector, row); fill(pr, *args) writes its program"""
+        assert index == len(self.gates)
+        group, pr = self._group[index], self._prog
+        lo, hi = self.groups[group]
+        assert (hi - lo - 1) + 1 + degree <= 8, self.gate_names[index]
+        off, cnt = len(pr.words), pr.count
+        if fill:
+            fill(pr, *args)
+        self.gates.append((group, index, lo, hi, off, pr.count - cnt))
+        if gen:
+            self._generators.append((gen[0], group, index) + (tuple(gen[1:]) + (0,) * 5)[:5])
+
+    def declare_basic(self, n_bits):
+        """the gates every circuit starts with: Noop, PublicInput, Constant, BaseSum with n_bits 1-bit limbs"""
+        self.declare(NOOP, 0)
+        self.declare(PUBLIC_INPUT, 1, (GEN_PUBLIC_INPUT,), public_input_into)
+        self.declare(CONSTANT, 1, (GEN_CONSTANT, 1, self.k0), constant_into, self.k0)
+        self.declare(BASE_SUM, 2, (GEN_BASE_SPLIT, n_bits, 1), base_sum_into, n_bits)
+
+    # ---- rows and wiring ----
+    def new_row(self, gate, c0=0, c1=0):
+        self._rows.append((gate, c0 % P, c1 % P))
+        return len(self._rows) - 1
+
+    def public_input(self, t, cell):
+        if self._pi_cells[t] is None:
+            self._pi_cells[t] = cell
+        self._uf.tie(self._pi_cells[t], cell)
+
+    def tie(self, a, b):
+        """a copy constraint between source a and cell b without a scheduled copy: generators write both, or b is an input cell"""
+        if a[0] == "pi":
+            self.public_input(a[1], b)
+        else:
+            self._uf.tie(a, b)
+
+    def place(self, row, feeds=()):
+        """feeds = [(wire, source)]: ties every source to its cell of the row and schedules the copies at their sources' levels; the row
+        runs one level behind its latest computed source"""
+        lv = 0
+        for wire, s in feeds:
+            if s[0] == "pi":
+                self.public_input(s[1], (wire, row))
+            else:
+                at = self._level[s[1]]
+                self._uf.tie(s, (wire, row))
+                self._copies.append((at, s, (wire, row)))
+                lv = max(lv, at + 1)
+        self._level[row] = lv
+
+    def constant(self, v):
+        """a Constant row of value v -> (the row, its cell)"""
+        r = self.new_row(CONSTANT, v)
+        self.place(r)
+        return r, (0, r)
+
+    def hash_rows(self, gate, zero, sources):
+        """a chain of swap-0 Poseidon rows (hash_n_to_hash_no_pad, overwrite mode) over the sources: every row absorbs the next 8 of them
+        or what is left, its other inputs are the outputs of the row before or zero -> the rows; the digest is the last row's out 0 .. 3"""
+        rows = []
+        for at in range(0, len(sources), 8):
+            r = self.new_row(gate)
+            feeds = [(self.s_in + t, s) for t, s in enumerate(sources[at:at + 8])]
+            feeds += [(self.s_in + t, (self.s_out + t, rows[-1]) if rows else zero) for t in range(len(feeds), 12)]
+            self.place(r, feeds + [(self.s_swap, zero)])
+            rows.append(r)
+        return rows
+
+    def hash_public_inputs(self, gate, zero):
+        """the public inputs hashed in circuit: the chain's digest is the PublicInput row's by copy constraint (both generated: no copy),
+        which the prover binds to hash_no_pad(public inputs)"""
+        self.chain_row = self.hash_rows(gate, zero, [pi(t) for t in range(self.n_pi)])
+        for t in range(4):
+            self.tie((self.s_out + t, self.chain_row[-1]), (t, self.pi_row))
+
+    def finish(self, min_log_n):
+        """N is known: cells become wire * N + row.  min_log_n: the device prover's FRI takes degree bits 10 .. 24; smaller circuits
+        are padded with Noop rows"""
+        assert len(self.gates) == len(self.gate_names)
+        self.programs = np.array(self._prog.words, dtype=np.int64)
+        rows = self._rows
+        self.rows_used = len(rows)
+        self.log_n = max(min_log_n, (len(rows) - 1).bit_length())
+        n = self.n = 1 << self.log_n
+        self.gate = np.full(n, NOOP, dtype=np.int64)
+        self.c0, self.c1 = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint64)
+        for r, (g, c0, c1) in enumerate(rows):
+            self.gate[r], self.c0[r], self.c1[r] = g, c0, c1
+        cell = lambda c: c[0] * n + c[1]
+        groups = self._uf.groups()
+        self.cycles = [sorted(cell(c) for c in g) for g in groups.values() if len(g) > 1]
+        self.pi_cells = [cell(c) for c in self._pi_cells]
+        self.pi_cycle = [sorted(cell(x) for x in groups[self._uf.find(c)]) for c in self._pi_cells]
+        row_level = np.full(n, -1, dtype=np.int64)
+        for r, lv in self._level.items():
+            row_level[r] = lv
+        assert (row_level[:len(rows)] >= 0).all()
+        self.row_level = row_level
+        self.n_levels = int(row_level.max()) + 1
+        lev = np.array([c[0] for c in self._copies], dtype=np.int64)
+        src = np.array([cell(c[1]) for c in self._copies], dtype=np.uint64)
+        dst = np.array([cell(c[2]) for c in self._copies], dtype=np.uint64)
+        o = np.argsort(lev, kind="stable")
+        lev, src, dst = lev[o], src[o], dst[o]
+        sched_rows = np.flatnonzero(row_level >= 0)
+        order = sched_rows[np.lexsort((sched_rows, self.gate[sched_rows], row_level[sched_rows]))].astype(np.uint32)
+        self._schedule = {"n_levels": self.n_levels, "row_level": row_level, "rows": order,
+                          "level_offsets": np.searchsorted(row_level[order], np.arange(self.n_levels + 1)).astype(np.uint32),
+                          "copy_src": src, "copy_dst": dst,
+                          "copy_offsets": np.searchsorted(lev, np.arange(self.n_levels + 1)).astype(np.uint32)}
+
+    # ---- the public face ----
+    def circuit(self):
+        """the circuit dict of tools/plonk_synth.circuit(): num_wires, num_routed, num_constants, num_selectors, gates, programs"""
+        return {"num_wires": self.num_wires, "num_routed": self.num_routed, "num_constants": self.num_constants,
+                "num_selectors": self.num_selectors, "gates": list(self.gates), "programs": self.programs,
+                "num_gate_constraints": max(g[5] for g in self.gates), "gate_names": self.gate_names}
+
+    def generators(self):
+        """[(kind, selector_index, row, p0 .. p4)] (include/sipp_hip.h sipp_plonk_generator)"""
+        return list(self._generators)
+
+    def schedule(self):
+        """the level schedule of sipp_plonk_generate_witness_levels: n_levels, row_level, rows, level_offsets, copy_src / copy_dst
+        (cell = wire * N + row), copy_offsets"""
+        return self._schedule
+
+    def constants_sigmas(self):
+        """[num_constants + num_routed][N]: the selector columns, the constant columns, the sigmas of the copy cycles (k_i = 7^i)"""
+        n, R = self.n, self.num_routed
+        sels = [np.where((self.gate >= lo) & (self.gate < hi), self.gate, UNUSED).astype(np.uint64) for lo, hi in self.groups]
+        perm = np.arange(R * n, dtype=np.int64)
+        for cyc in self.cycles:
+            c = np.asarray(cyc, dtype=np.int64)
+            assert int(c.max()) < R * n
+            perm[c] = np.roll(c, -1)
+        pw = _powers(_root_of_unity(self.log_n), n)
+        ks = np.array([pow(7, j, P) for j in range(R)], dtype=np.uint64)
+        pm = perm.reshape(R, n)
+        sig = np.empty((R, n), dtype=np.uint64)
+        for j in range(R):
+            sig[j] = _gl_mul(ks[pm[j] >> self.log_n], pw[pm[j] & (n - 1)])
+        consts = [self.c0, self.c1][:self.num_constants - self.num_selectors]
+        return np.ascontiguousarray(np.concatenate([np.stack(sels + consts), sig]).astype(np.uint64))
+
+    def public_input_witness(self, pis):
+        """[num_wires][N] with every cell on a cycle of a public input set (plonky2's PartialWitness), everything else 0: the generators
+        and the schedule's copies fill it -> (the array, its flat view)"""
+        w = np.zeros((self.num_wires, self.n), dtype=np.uint64)
+        flat = w.reshape(-1)
+        for t, cyc in enumerate(self.pi_cycle):
+            flat[np.asarray(cyc, dtype=np.int64)] = np.uint64(pis[t] % P)
+        return w, flat
+
+
+class CircuitProver:
+    """A circuit through the library's CircuitData (sipp_circuit_build / _prove / _verify): the constants_sigmas commitment and the schedule
+    go to the device once; prove(inputs) generates the witness there and returns the flat proof."""
+
+    def __init__(self, ctx, circ, fri=None, params=None, digest=None):
+        from . import _lib
+        self.circ = c = circ
+        self.params = params if params is not None else _lib.PlonkParams(c.num_routed, 8, 2)
+        self.fri = fri if fri is not None else fri_params(c.log_n)
+        self.circuit = c.circuit()
+        self._pc = _lib.PlonkCircuit.from_dict(self.circuit)
+        self.data = _lib.CircuitData(ctx, c.log_n, self.params, self.fri, self._pc, c.constants_sigmas(), c.generators(), sched=c.schedule(),
+                                     digest=digest)
+        self.cap, self.digest = self.data.cap, self.data.digest
+
+    def prove(self, *inputs):
+        """inputs: the circuit's partial_witness arguments, the public_inputs arguments first"""
+        c = self.circ
+        return self.data.prove(c.partial_witness(*inputs), c.public_inputs(*inputs[:c.n_public_args]))
+
+    def verify(self, proof):
+        """-> (status, refusing stage): (0, 0) = accepted"""
+        return self.data.verify(proof)
+
+    def close(self):
+        self.data.close()
