@@ -12,6 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import sipp_amd  # noqa: E402
 from oracle.py import bn254 as bn  # noqa: E402
+from tests import _exp_edges as edges  # noqa: E402  (the edge catalogue of the exponentiation tests: scalars, Fq12 elements, extreme points)
 from tests import _oracle  # noqa: E402
 
 first = int(sys.argv[1]) if len(sys.argv) > 1 else 100
@@ -33,7 +34,7 @@ for seed in range(first, first + count):
         if mode == 3:
             return (1 << 256) - 1 - int(rng.integers(0, 1 << 20))  # 256-bit exponents are legal (U256Target)
         if mode == 4:
-            return [0, 1, bn.R, bn.R + 1, (1 << 256) - 1, 1 << 255][int(rng.integers(0, 6))]
+            return edges.EDGE_SCALARS[int(rng.integers(0, len(edges.EDGE_SCALARS)))]
         return int.from_bytes(rng.bytes(32), "little") % bn.R or 1
 
     def fq():
@@ -41,25 +42,31 @@ for seed in range(first, first + count):
 
     def rand_f12():
         mode = rng.integers(0, 8)
-        if mode == 0:
-            return [1] + [0] * 11                               # one
-        if mode == 1:
-            return [0] * 12                                     # zero
-        if mode == 2:
-            return [bn.P - 1] + [0] * 11                        # minus one
-        if mode == 3:
-            return [fq()] + [0] * 11                            # a base-field element
+        if mode < 4:                                            # zero, one, all p - 1, all TOP, w^6, minus one
+            return list(edges.F12_SPECIAL[int(rng.integers(0, len(edges.F12_SPECIAL)))])
         if mode == 4:
-            return [0] * 6 + [1] + [0] * 5                      # w^6
+            return [fq()] + [0] * 11                            # a base-field element
         return [fq() for _ in range(12)]
+
+    def g1_point():
+        if rng.integers(0, 8) == 0:                             # a point with extreme coordinates (any curve point is legal)
+            pts = edges.g1_points()[1]
+            return pts[int(rng.integers(0, len(pts)))]
+        return bn.g1_mul(bn.G1, scalar() % bn.R or 1)
+
+    def g2_point():
+        if rng.integers(0, 8) == 0:                             # ... of the twist, outside the r-torsion
+            pts = edges.g2_points()[1]
+            return pts[int(rng.integers(0, len(pts)))]
+        return bn.g2_mul(bn.G2, scalar() % bn.R or 1)
 
     def words(e):
         return [(e >> (32 * i)) & 0xFFFFFFFF for i in range(8)]
 
     n1, n2, n12 = (int(rng.integers(1, 10)) for _ in range(3))
-    g1 = [bn.g1_to_u32(bn.g1_mul(bn.G1, scalar() % bn.R or 1)) + bn.g1_to_u32(bn.g1_mul(bn.G1, scalar() % bn.R or 2)) + words(scalar() % (1 << 256)) + [0] * 16
+    g1 = [bn.g1_to_u32(g1_point()) + bn.g1_to_u32(g1_point()) + words(scalar() % (1 << 256)) + [0] * 16
           for _ in range(n1)]
-    g2 = [bn.g2_to_u32(bn.g2_mul(bn.G2, scalar() % bn.R or 1)) + bn.g2_to_u32(bn.g2_mul(bn.G2, scalar() % bn.R or 2)) + words(scalar() % (1 << 256)) + [0] * 32
+    g2 = [bn.g2_to_u32(g2_point()) + bn.g2_to_u32(g2_point()) + words(scalar() % (1 << 256)) + [0] * 32
           for _ in range(n2)]
     f12 = [bn.f12_to_u32(rand_f12()) + bn.f12_to_u32(rand_f12()) + words(scalar()) + [0] * 96 for _ in range(n12)]
     if rng.integers(0, 4) == 0:      # a point off its curve in one record: both sides must refuse

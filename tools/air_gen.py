@@ -141,7 +141,7 @@ class Air:
         # assignment, so that the field identity forces the integer identity (0 is the only multiple of p there)
         worst = (1 << (ncl * lb - 1 + 16 * group)) + (1 << (bound_bits + 16 * (group - 1) + 1)) + (1 << (ncl * lb))
         assert worst < (1 << 64) - (1 << 32), (bound_bits, group, ncl, lb)
-        self.gadgets.append(dict(name=gname, prods=prods, lins=lins, ncl=ncl, lb=lb, coffset=coffset, group=group))
+        self.gadgets.append(dict(name=gname, prods=prods, lins=lins, ncl=ncl, lb=lb, coffset=coffset, group=group, bound_bits=bound_bits))
 
     def emit_gadgets(self):
         for g in self.gadgets:
