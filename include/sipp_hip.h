@@ -279,7 +279,10 @@ int sipp_map_to_g2(sipp_ctx *ctx, const uint32_t *msgs, size_t n, uint32_t *map_
  * g1: n x 16 u32 (x, y), g2: n x 32 u32 (x.c0, x.c1, y.c0, y.c1) -- the limb stream of src/transcript_native.rs:42-54;
  * all-zero coordinates stand for the point at infinity.  out: the 12 MyFq12 coefficients, 96 u32 (src/transcript_native.rs:32-40).
  * sipp_inner_products computes `count` independent products (pairs [k n, (k + 1) n) -> out[k]) in one pass, e.g. the Z_L and
- * Z_R of one SIPP round (src/prover_native.rs:51-52).  Uses the ctx's workspace (about 500 bytes per pair). */
+ * Z_R of one SIPP round (src/prover_native.rs:51-52).  Uses the ctx's workspace (about 600 bytes per pair; SIPP_E_NOMEM, nothing
+ * launched, if it does not fit).  n * count is at most 2^24 (SIPP_E_BADARG beyond, and for n = 0 or count = 0).
+ * Input contract: every coordinate is canonical (< p), every point that is not all-zero lies on its curve and B_i in G2; NEITHER is
+ * checked here (the result for other inputs is unspecified), and all-zero words in A_i or in B_i or in both mean infinity. */
 int sipp_inner_product(sipp_ctx *ctx, const uint32_t *g1, const uint32_t *g2, size_t n, uint32_t *out);
 int sipp_inner_products(sipp_ctx *ctx, const uint32_t *g1, const uint32_t *g2, size_t n, size_t count, uint32_t *out);
 
@@ -290,7 +293,12 @@ int sipp_inner_products(sipp_ctx *ctx, const uint32_t *g1, const uint32_t *g2, s
  *   statement (16n + 32n + 96 + 16 + 32 + 96 u32: A | B | Z | final_A | final_B | final_Z, src/statements.rs:24-39),
  *   the three obligation lists as complete IO records for sipp_*_exp_prove (src/verifier_circuit.rs:68-131:
  *   (n - 1) x 56, (n - 1) x 104 and 2 log2 n x 296 u32, round-major), and *accepted = (pairing(final_A, final_B) == final_Z).
- *   Any output pointer may be NULL.  The ctx's workspace must hold the widest fold (sipp_workspace_bytes(SIPP_G2_EXP, n / 2)). */
+ *   Any output pointer may be NULL.  The ctx's workspace must hold the widest fold (sipp_workspace_bytes(SIPP_G2_EXP, n / 2)).
+ * Where the chain DIVERGES from the reference (and from oracle/py/sipp_native.py): a point at infinity among A or B is the neutral
+ *   element there and folds like any other; here both calls refuse it with SIPP_E_WITNESS, as they refuse a point off its curve or a
+ *   fold that passes through infinity, because the exponentiation AIRs have no witness for such an obligation (n = 1, which folds
+ *   nothing, takes infinity as the products do).  After a refusal the ctx is usable as before: no fold stays in flight and the
+ *   workspace is handed back. */
 size_t sipp_native_proof_words(size_t n);
 int sipp_prove_native(sipp_ctx *ctx, const uint32_t *A, const uint32_t *B, size_t n, uint32_t *proof);
 int sipp_verify_native(sipp_ctx *ctx, const uint32_t *A, const uint32_t *B, size_t n, const uint32_t *proof,

@@ -1213,7 +1213,7 @@ int sipp_inner_products_groups(sipp_ctx* ctx, const uint32_t* g1, const uint32_t
 }
 
 extern "C" int sipp_inner_products(sipp_ctx* ctx, const uint32_t* g1, const uint32_t* g2, size_t n, size_t count, uint32_t* out) {
-    if (!ctx || n == 0 || count == 0 || n * count > ((size_t)1 << 24)) return SIPP_E_BADARG;
+    if (!ctx || n == 0 || count == 0 || count > ((size_t)1 << 24) / n) return SIPP_E_BADARG;  // (n * count may wrap)
     std::vector<uint32_t> off(count + 1);
     for (size_t k = 0; k <= count; k++) off[k] = (uint32_t)(k * n);
     return sipp_inner_products_groups(ctx, g1, g2, off.data(), count, out);
