@@ -58,6 +58,13 @@ struct GenArgs {
     uint64_t pih[4];
 };
 
+// row i holds generator g: its selector cell carries g's gate index
+__device__ __forceinline__ bool row_holds(const uint64_t* consts, uint32_t n, uint32_t i, const sipp_plonk_generator& g) {
+    return consts[(size_t)g.selector_index * n + i] == g.row;
+}
+
+__host__ __device__ __forceinline__ bool is_poseidon(uint32_t kind) { return kind == SIPP_GEN_POSEIDON || kind == SIPP_GEN_POSEIDON_SWAP; }
+
 __device__ __forceinline__ uint64_t pow7(uint64_t x) {
     const uint64_t x2 = gl::mul(x, x), x4 = gl::mul(x2, x2);
     return gl::mul(gl::mul(x4, x2), x);
@@ -354,7 +361,7 @@ __device__ __forceinline__ void interpolation_lanes(uint64_t* wires, uint32_t n,
 __global__ void __launch_bounds__(256) plonk_witness_kernel(GenArgs a) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, n = a.n;
     if (i >= n) return;
-    if (a.consts[(size_t)a.g.selector_index * n + i] != a.g.row) return;
+    if (!row_holds(a.consts, n, i, a.g)) return;
     run_generator(a.wires, a.consts, n, i, a.g, a.pih);
 }
 
@@ -383,39 +390,44 @@ __global__ void __launch_bounds__(64) plonk_witness_level_kernel(LevelArgs a) {
         return;
     }
     for (uint32_t q = 0; q < a.n_gens; q++)
-        if (a.consts[(size_t)a.g[q].selector_index * a.n + i] == a.g[q].row) run_generator(a.wires, a.consts, a.n, i, a.g[q], a.pih);
+        if (row_holds(a.consts, a.n, i, a.g[q])) run_generator(a.wires, a.consts, a.n, i, a.g[q], a.pih);
 }
 
 // THIN levels (a hash chain's link: a few hundred to a few thousand rows) are latency-bound -- one lane walking a whole permutation is
 // ~23 k dependent instructions.  Here a row gets SIXTEEN lanes (four rows per wave): lane l < 12 owns state element l of a Poseidon row,
 // S-boxes side by side, the MDS layer through LDS (every lane reads the twelve elements of its row and accumulates its own output from
-// exact 32-bit halves) -- ~3.5 k instructions deep; the short families run on lane 0 of their row's group.  pos = index of the Poseidon
-// generator in a.g, or -1.  One wave per block: the two barriers per round cost nothing.
-__global__ void __launch_bounds__(64) plonk_witness_level_coop_kernel(LevelArgs a, int pos) {
-    __shared__ uint64_t sh[4][12];
-    const uint32_t grp = threadIdx.x >> 4, l = threadIdx.x & 15, k = blockIdx.x * 4 + grp, n = a.n;
-    bool ok = k < a.count;
-    uint32_t i = ok ? a.rows[k] : 0;
+// exact 32-bit halves) -- ~3.5 k instructions deep; the short families run on lane 0 of their row's group.  One wave per block: the two
+// barriers per round cost nothing.
+
+// a lane's place in the two kernels below: group grp of the block's four, lane l of its sixteen, row i of the table.  ok is false, and
+// i = 0, for a group past the level's end and for a row outside the table, which raises the error flag.  (The arguments are scalars:
+// a reference to the kernel's LevelArgs cost either kernel four VGPRs.)
+struct CoopRow {
+    uint32_t grp, l, i;
+    bool ok;
+};
+__device__ __forceinline__ CoopRow coop_row(const uint32_t* rows, uint32_t count, uint32_t n, int* err) {
+    const uint32_t grp = threadIdx.x >> 4, l = threadIdx.x & 15, k = blockIdx.x * 4 + grp;
+    bool ok = k < count;
+    uint32_t i = ok ? rows[k] : 0;
     if (ok && i >= n) {
-        if (l == 0) *a.err = 1;
+        if (l == 0) *err = 1;
         ok = false;
         i = 0;
     }
-    bool is_pos = false;
-    if (ok) {
-        if (pos >= 0) is_pos = a.consts[(size_t)a.g[pos].selector_index * n + i] == a.g[pos].row;
-        if (l == 0)
-            for (uint32_t q = 0; q < a.n_gens; q++)
-                if ((int)q != pos && a.consts[(size_t)a.g[q].selector_index * n + i] == a.g[q].row) run_generator(a.wires, a.consts, n, i, a.g[q], a.pih);
-    }
-    if (pos < 0 || !__syncthreads_or(is_pos)) return;        // block-uniform: no Poseidon row among the four
-    const uint32_t in = a.g[pos].p[0], out = a.g[pos].p[1], sb = a.g[pos].p[2];
-    const uint32_t e = l < 12 ? l : 0;                        // lanes 12 .. 15 shadow element 0 and never store
-    const bool act = is_pos && l < 12;
+    return CoopRow{grp, l, i, ok};
+}
+
+// the 30 rounds on the sixteen lanes of row i, the one copy both kernels below run (all lanes of the block call it; act = the row is a
+// Poseidon row and l < 12): lane l starts from s, state element l behind the row's prelude, and stores its S-box inputs (the wires of
+// poseidon_rounds) and its output; lanes 12 .. 15 shadow element 0 and never store.  sh: the block's LDS tile, twelve words per group.
+// The exact half-product sum is written here and in mds(), nowhere else: one helper for both changed mds()'s register allocation.
+__device__ __forceinline__ void poseidon_lanes(uint64_t* wires, uint32_t n, uint32_t i, uint32_t grp, uint32_t l, bool act, uint64_t s,
+                                               uint32_t out, uint32_t sb, uint64_t (&sh)[4][12]) {
+    const uint32_t e = l < 12 ? l : 0;
     uint32_t coef[12];                                        // this lane's row of the MDS matrix
 #pragma unroll
     for (int c = 0; c < 12; c++) coef[c] = w_mds_circ[(c + 12 - e) % 12] + ((e == 0 && c == 0) ? MDS_DIAG0 : 0);
-    uint64_t s = act ? a.wires[(size_t)(in + e) * n + i] : 0;
 #pragma unroll 1
     for (uint32_t rnd = 0; rnd < 30; rnd++) {
         const bool full = rnd < 4 || rnd >= 26;
@@ -423,7 +435,7 @@ __global__ void __launch_bounds__(64) plonk_witness_level_coop_kernel(LevelArgs 
         if (full || e == 0) {
             if (act && rnd) {
                 const uint32_t w = full ? (rnd < 4 ? sb + 12 * (rnd - 1) : sb + 58 + 12 * (rnd - 26)) + e : sb + 36 + (rnd - 4);
-                a.wires[(size_t)w * n + i] = s;
+                wires[(size_t)w * n + i] = s;
             }
             s = pow7(s);
         }
@@ -440,10 +452,26 @@ __global__ void __launch_bounds__(64) plonk_witness_level_coop_kernel(LevelArgs 
         s = gl::reduce96((uint32_t)(ah >> 32) + (lo < al ? 1u : 0u), lo);
         __syncthreads();
     }
-    if (act) a.wires[(size_t)(out + e) * n + i] = s;
+    if (act) wires[(size_t)(out + e) * n + i] = s;
 }
 
-__device__ __forceinline__ bool is_poseidon(uint32_t kind) { return kind == SIPP_GEN_POSEIDON || kind == SIPP_GEN_POSEIDON_SWAP; }
+// the circuit's one Poseidon generator a.g[pos] (pos = -1: none) on the sixteen lanes, its parameters block-uniform
+__global__ void __launch_bounds__(64) plonk_witness_level_coop_kernel(LevelArgs a, int pos) {
+    __shared__ uint64_t sh[4][12];
+    const CoopRow row = coop_row(a.rows, a.count, a.n, a.err);
+    const uint32_t grp = row.grp, l = row.l, i = row.i, n = a.n;
+    bool is_pos = false;
+    if (row.ok) {
+        if (pos >= 0) is_pos = row_holds(a.consts, n, i, a.g[pos]);
+        if (l == 0)
+            for (uint32_t q = 0; q < a.n_gens; q++)
+                if ((int)q != pos && row_holds(a.consts, n, i, a.g[q])) run_generator(a.wires, a.consts, n, i, a.g[q], a.pih);
+    }
+    if (pos < 0 || !__syncthreads_or(is_pos)) return;        // block-uniform: no Poseidon row among the four
+    const uint32_t in = a.g[pos].p[0], out = a.g[pos].p[1], sb = a.g[pos].p[2];
+    const bool act = is_pos && l < 12;
+    poseidon_lanes(a.wires, n, i, grp, l, act, act ? a.wires[(size_t)(in + l) * n + i] : 0, out, sb, sh);
+}
 
 // The same sixteen lanes per row when the circuit has a swap generator or more than one Poseidon layout: every row gets its own
 // Poseidon-family generator (the last one whose selector value it holds; any other match runs on lane 0 first), so one level may mix
@@ -458,46 +486,35 @@ __device__ __forceinline__ bool is_poseidon(uint32_t kind) { return kind == SIPP
 template <bool INTERP, bool REDUCE>
 __global__ void __launch_bounds__(64) plonk_witness_level_coop_rows_kernel(LevelArgs a, bool one_lane, bool reduce_one_lane) {
     __shared__ uint64_t sh[4][12];
-    const uint32_t grp = threadIdx.x >> 4, l = threadIdx.x & 15, k = blockIdx.x * 4 + grp, n = a.n;
-    bool ok = k < a.count;
-    uint32_t i = ok ? a.rows[k] : 0;
-    if (ok && i >= n) {
-        if (l == 0) *a.err = 1;
-        ok = false;
-        i = 0;
-    }
+    const CoopRow row = coop_row(a.rows, a.count, a.n, a.err);
+    const uint32_t grp = row.grp, l = row.l, i = row.i, n = a.n;
     int pq = -1, iq = -1, rq = -1;                            // this row's Poseidon-family generator, its sixteen-lane interpolation / reduction
     uint32_t in = 0, out = 0, sb = 0, sw = 0, dl = 0, is = 1, id = 2, inr = 0, rk = 0, rnr = 0;
     bool swp = false, rext = false;
-    if (ok) {
+    if (row.ok) {
         for (uint32_t q = 0; q < a.n_gens; q++) {             // uniform loop: the parameters are picked, never indexed per lane
-            if (is_poseidon(a.g[q].kind) && a.consts[(size_t)a.g[q].selector_index * n + i] == a.g[q].row) {
+            if (is_poseidon(a.g[q].kind) && row_holds(a.consts, n, i, a.g[q])) {
                 pq = (int)q;
                 in = a.g[q].p[0], out = a.g[q].p[1], sb = a.g[q].p[2], sw = a.g[q].p[3], dl = a.g[q].p[4];
                 swp = a.g[q].kind == SIPP_GEN_POSEIDON_SWAP;
             }
-            if (INTERP && !one_lane && a.g[q].kind == SIPP_GEN_COSET_INTERPOLATION &&
-                a.consts[(size_t)a.g[q].selector_index * n + i] == a.g[q].row)
+            if (INTERP && !one_lane && a.g[q].kind == SIPP_GEN_COSET_INTERPOLATION && row_holds(a.consts, n, i, a.g[q]))
                 iq = (int)q, is = a.g[q].p[0], id = a.g[q].p[1], inr = a.g[q].p[2];
             if (REDUCE && !reduce_one_lane && (a.g[q].kind == SIPP_GEN_REDUCING || a.g[q].kind == SIPP_GEN_REDUCING_EXT) &&
-                a.consts[(size_t)a.g[q].selector_index * n + i] == a.g[q].row)
+                row_holds(a.consts, n, i, a.g[q]))
                 rq = (int)q, rk = a.g[q].p[0], rnr = a.g[q].p[1], rext = a.g[q].kind == SIPP_GEN_REDUCING_EXT;
         }
         if (l == 0)
             for (uint32_t q = 0; q < a.n_gens; q++)
-                if ((int)q != pq && (int)q != iq && (int)q != rq && a.consts[(size_t)a.g[q].selector_index * n + i] == a.g[q].row)
+                if ((int)q != pq && (int)q != iq && (int)q != rq && row_holds(a.consts, n, i, a.g[q]))
                     run_generator(a.wires, a.consts, n, i, a.g[q], a.pih);
     }
     if (INTERP && __syncthreads_or(iq >= 0)) interpolation_lanes(a.wires, n, i, l, iq >= 0, is, id, inr);   // block-uniform
     if (REDUCE && __syncthreads_or(rq >= 0)) reducing_lanes(a.wires, n, i, l, rq >= 0, rext, rk, rnr);      // block-uniform
     const bool is_pos = pq >= 0;
     if (!__syncthreads_or(is_pos)) return;                    // block-uniform: no Poseidon row among the four
-    const uint32_t e = l < 12 ? l : 0;                        // lanes 12 .. 15 shadow element 0 and never store
     const bool act = is_pos && l < 12;
-    uint32_t coef[12];                                        // this lane's row of the MDS matrix
-#pragma unroll
-    for (int c = 0; c < 12; c++) coef[c] = w_mds_circ[(c + 12 - e) % 12] + ((e == 0 && c == 0) ? MDS_DIAG0 : 0);
-    uint64_t s = act ? a.wires[(size_t)(in + e) * n + i] : 0;
+    uint64_t s = act ? a.wires[(size_t)(in + l) * n + i] : 0;
     if (swp && l < 8) {                                       // (in[j] + d_j, in[4+j] - d_j), d_j = swap (in[4+j] - in[j])
         const uint32_t j = l & 3;
         const uint64_t lhs = a.wires[(size_t)(in + j) * n + i], rhs = a.wires[(size_t)(in + 4 + j) * n + i];
@@ -505,31 +522,7 @@ __global__ void __launch_bounds__(64) plonk_witness_level_coop_rows_kernel(Level
         s = l < 4 ? gl::add(lhs, d) : gl::sub(rhs, d);
         if (l < 4) a.wires[(size_t)(dl + j) * n + i] = d;
     }
-#pragma unroll 1
-    for (uint32_t rnd = 0; rnd < 30; rnd++) {
-        const bool full = rnd < 4 || rnd >= 26;
-        s = gl::add(s, w_rc[12 * rnd + e]);
-        if (full || e == 0) {
-            if (act && rnd) {
-                const uint32_t w = full ? (rnd < 4 ? sb + 12 * (rnd - 1) : sb + 58 + 12 * (rnd - 26)) + e : sb + 36 + (rnd - 4);
-                a.wires[(size_t)w * n + i] = s;
-            }
-            s = pow7(s);
-        }
-        if (l < 12) sh[grp][l] = s;
-        __syncthreads();
-        uint64_t al = 0, ah = 0;
-#pragma unroll
-        for (int c = 0; c < 12; c++) {
-            const uint64_t v = sh[grp][c];
-            al += (uint64_t)(uint32_t)v * coef[c];
-            ah += (v >> 32) * coef[c];
-        }
-        const uint64_t lo = al + (ah << 32);
-        s = gl::reduce96((uint32_t)(ah >> 32) + (lo < al ? 1u : 0u), lo);
-        __syncthreads();
-    }
-    if (act) a.wires[(size_t)(out + e) * n + i] = s;
+    poseidon_lanes(a.wires, n, i, grp, l, act, s, out, sb, sh);
 }
 
 __global__ void __launch_bounds__(256) plonk_witness_copy_kernel(uint64_t* wires, const uint64_t* src, const uint64_t* dst, uint32_t count,
@@ -600,7 +593,7 @@ static int witness_prepare(sipp_ctx* ctx, const uint64_t* d_wires, const uint64_
         if (!layout_ok(gens[k], num_wires, num_constants))
             return sipp_fail(ctx, SIPP_E_BADARG, "plonk witness: a generator's layout leaves the wire table / the constants, or its family is unknown");
         needs_pih |= gens[k].kind == SIPP_GEN_PUBLIC_INPUT;
-        needs_rc |= gens[k].kind == SIPP_GEN_POSEIDON || gens[k].kind == SIPP_GEN_POSEIDON_SWAP;
+        needs_rc |= is_poseidon(gens[k].kind);
     }
     if (needs_pih && !public_inputs_hash) return sipp_fail(ctx, SIPP_E_BADARG, "plonk witness: a PublicInput generator without the public-inputs hash");
     SIPP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
@@ -665,7 +658,7 @@ extern "C" int sipp_plonk_generate_witness_levels(sipp_ctx* ctx, uint64_t* d_wir
     int pos_gen = -1, n_pos = 0;
     bool any_swap = false, any_interp = false, any_initial = false;
     for (size_t q = 0; q < n_gens; q++) {
-        if (gens[q].kind == SIPP_GEN_POSEIDON || gens[q].kind == SIPP_GEN_POSEIDON_SWAP) pos_gen = (int)q, n_pos++;
+        if (is_poseidon(gens[q].kind)) pos_gen = (int)q, n_pos++;
         any_swap |= gens[q].kind == SIPP_GEN_POSEIDON_SWAP;
         any_interp |= gens[q].kind == SIPP_GEN_COSET_INTERPOLATION;
         any_initial |= gens[q].kind == SIPP_GEN_REDUCING_EXT || gens[q].kind == SIPP_GEN_QUOTIENT_EXT;
@@ -674,26 +667,27 @@ extern "C" int sipp_plonk_generate_witness_levels(sipp_ctx* ctx, uint64_t* d_wir
     const bool one_lane = any_interp && (ctx->kernel_routes & SIPP_ROUTE_WITNESS_INTERP_ONE_LANE);
     // only a circuit of FRI's initial combination takes the sixteen-lane reduction: every other circuit launches what it always did
     const bool reduce_one_lane = any_initial && (ctx->kernel_routes & SIPP_ROUTE_WITNESS_REDUCE_ONE_LANE);
+    // a thin level's per-row kernel at the instantiation the circuit's families need (the one-lane flags are false wherever their code is
+    // compiled out); none: the single-generator kernel
+    const auto rows_kernel = any_initial  ? plonk_witness_level_coop_rows_kernel<true, true>
+                             : any_interp ? plonk_witness_level_coop_rows_kernel<true, false>
+                             : per_row    ? plonk_witness_level_coop_rows_kernel<false, false>
+                                          : nullptr;
+    LevelArgs a;     // the same for every level but for rows and count
+    a.wires = d_wires; a.consts = d_constants; a.n = n; a.n_gens = (uint32_t)n_gens; a.err = d_err;
+    for (int q = 0; q < 4; q++) a.pih[q] = public_inputs_hash ? public_inputs_hash[q] : 0;
+    for (size_t q = 0; q < n_gens; q++) a.g[q] = gens[q];
     auto launch_all = [&]() -> hipError_t {
         (void)hipMemsetAsync(d_err, 0, sizeof(int), ctx->stream);
         for (uint32_t l = 0; l < L; l++) {
             const uint32_t r0 = sched->level_offsets[l], cnt = sched->level_offsets[l + 1] - r0;
             if (cnt) {
-                LevelArgs a;
-                a.wires = d_wires; a.consts = d_constants; a.n = n; a.n_gens = (uint32_t)n_gens; a.rows = sched->d_rows + r0; a.count = cnt; a.err = d_err;
-                for (int q = 0; q < 4; q++) a.pih[q] = public_inputs_hash ? public_inputs_hash[q] : 0;
-                for (size_t q = 0; q < n_gens; q++) a.g[q] = gens[q];
+                a.rows = sched->d_rows + r0;
+                a.count = cnt;
                 if (cnt >= COOP_BELOW_ROWS)      // wide level: throughput, one lane per row
                     hipLaunchKernelGGL(plonk_witness_level_kernel, dim3((cnt + 63) / 64), dim3(64), 0, ctx->stream, a);
-                else if (any_initial)            // thin level: latency, sixteen lanes per row
-                    hipLaunchKernelGGL((plonk_witness_level_coop_rows_kernel<true, true>), dim3((cnt + 3) / 4), dim3(64), 0, ctx->stream, a, one_lane,
-                                       reduce_one_lane);
-                else if (any_interp)
-                    hipLaunchKernelGGL((plonk_witness_level_coop_rows_kernel<true, false>), dim3((cnt + 3) / 4), dim3(64), 0, ctx->stream, a, one_lane,
-                                       false);
-                else if (per_row)
-                    hipLaunchKernelGGL((plonk_witness_level_coop_rows_kernel<false, false>), dim3((cnt + 3) / 4), dim3(64), 0, ctx->stream, a, false,
-                                       false);
+                else if (rows_kernel)            // thin level: latency, sixteen lanes per row
+                    hipLaunchKernelGGL(rows_kernel, dim3((cnt + 3) / 4), dim3(64), 0, ctx->stream, a, one_lane, reduce_one_lane);
                 else
                     hipLaunchKernelGGL(plonk_witness_level_coop_kernel, dim3((cnt + 3) / 4), dim3(64), 0, ctx->stream, a, pos_gen);
             }

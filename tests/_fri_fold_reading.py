@@ -1,19 +1,15 @@
 """A Python reading of the three generators of a FRI fold chain (SIPP_GEN_ARITHMETIC_EXT, SIPP_GEN_EXPONENTIATION,
 SIPP_GEN_COSET_INTERPOLATION) in exact integers, row by row, and of the data a fold-checking circuit is fed: the checker of the device
 witness of sipp_amd/fri_fold.py.  It shares nothing with that module or the kernels: the layouts are restated from include/sipp_hip.h, the
-barycentric weights are computed from their product definition 1 / prod_(j != i) (x_i - x_j).  The families read before come from
-tests/_merkle_reading.py.
+barycentric weights are computed from their product definition 1 / prod_(j != i) (x_i - x_j).  tests/_witness_reading.py runs the row
+functions on the rows that hold their generators.
 
 fold_data(inst, proof) walks a flat opening proof (sipp_fri_prove_openings / oracle/fri.c) the way
 tests/test_oracle_fri_edges.py::python_reading_accepts does and returns what the circuit takes: betas, the final polynomial, per query
 (x_index, the first `old`, the evals of every round)."""
-import numpy as np
-
 from oracle.py import plonky2_generic as g2
-from tests import _merkle_reading as mr
 
 P = 0xFFFFFFFF00000001
-GEN_ARITHMETIC_EXT, GEN_EXPONENTIATION, GEN_COSET_INTERPOLATION = 10, 11, 12
 ROOT32 = 1753635133440165772
 
 
@@ -86,45 +82,6 @@ def coset_interpolation_row(w, s, d, W):
             w[start + 2 * c], w[start + 2 * c + 1] = e
             w[start + 2 * ni + 2 * c], w[start + 2 * ni + 2 * c + 1] = q
     w[3 + 2 * n], w[4 + 2 * n] = e
-
-
-def run_generator(wires, consts, pih, g, rows):
-    """one generator (kind, selector_index, row, p0 .. p4) on the given rows whose selector cell holds its gate index"""
-    kind, si, gate, p = g[0], g[1], g[2], g[3:8]
-    if kind not in (GEN_ARITHMETIC_EXT, GEN_EXPONENTIATION, GEN_COSET_INTERPOLATION):
-        return mr.run_generator(wires, consts, pih, g, rows)
-    rows = np.asarray(rows, dtype=np.int64)
-    for r in rows[consts[si, rows] == np.uint64(gate)]:
-        w = [int(x) for x in wires[:, r]]
-        if kind == GEN_ARITHMETIC_EXT:
-            arithmetic_ext_row(w, int(consts[p[1], r]), int(consts[p[2], r]), p[0], p[3])
-        elif kind == GEN_EXPONENTIATION:
-            exponentiation_row(w, p[0])
-        else:
-            coset_interpolation_row(w, p[0], p[1], p[2])
-        wires[:, r] = np.array(w, dtype=np.uint64)
-
-
-def replay(wires, consts, gens, pih, sched):
-    """sipp_plonk_generate_witness_levels on the CPU: per level the generators of its rows, then the copies its outputs feed"""
-    w = np.ascontiguousarray(wires, dtype=np.uint64).copy()
-    flat = w.reshape(-1)
-    rows, lo, co = sched["rows"].astype(np.int64), sched["level_offsets"], sched["copy_offsets"]
-    src, dst = sched["copy_src"].astype(np.int64), sched["copy_dst"].astype(np.int64)
-    for lv in range(int(sched["n_levels"])):
-        r = rows[lo[lv]:lo[lv + 1]]
-        for g in gens:
-            run_generator(w, consts, pih, g, r)
-        flat[dst[co[lv]:co[lv + 1]]] = flat[src[co[lv]:co[lv + 1]]]
-    return w
-
-
-def row_local(wires, consts, gens, pih):
-    """sipp_plonk_generate_witness on the CPU: every generator on every row of its gate"""
-    w = np.ascontiguousarray(wires, dtype=np.uint64).copy()
-    for g in gens:
-        run_generator(w, consts, pih, g, np.arange(w.shape[1]))
-    return w
 
 
 def fold_data(inst, proof):

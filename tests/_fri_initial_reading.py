@@ -1,7 +1,7 @@
 """A Python reading of the generators of FRI's initial combination (SIPP_GEN_REDUCING, SIPP_GEN_REDUCING_EXT, SIPP_GEN_QUOTIENT_EXT) in
 exact integers, row by row, and of the data a circuit that checks fri_combine_initial is fed: the checker of the device witness of
-sipp_amd/fri_initial.py.  It shares nothing with that module or the kernels: the layouts are restated from include/sipp_hip.h.  The
-families read before come from tests/_fri_fold_reading.py.
+sipp_amd/fri_initial.py.  It shares nothing with that module or the kernels: the layouts are restated from include/sipp_hip.h.
+tests/_witness_reading.py runs the row functions on the rows that hold their generators.
 
 initial_data(inst, proof) walks a flat opening proof (sipp_fri_prove_openings / oracle/fri.c) the way tests/_fri_fold_reading.fold_data
 does and returns what the circuit takes: alpha, per batch the point and the opened values, per query (x_index, the unsalted leaf values
@@ -12,7 +12,6 @@ from oracle.py import plonky2_generic as g2
 from tests import _fri_fold_reading as fr
 
 P = 0xFFFFFFFF00000001
-GEN_REDUCING, GEN_REDUCING_EXT, GEN_QUOTIENT_EXT = 7, 13, 14
 
 
 def ext_inv(x, W):
@@ -46,45 +45,6 @@ def quotient_ext_row(w, c0, c1, n_ops, W):
         num = ((w[b + 6] - c1 * w[b + 4]) % P, (w[b + 7] - c1 * w[b + 5]) % P)
         den = (c0 * w[b] % P, c0 * w[b + 1] % P)
         w[b + 2], w[b + 3] = fr.emul(num, ext_inv(den, W), W)
-
-
-def run_generator(wires, consts, pih, g, rows):
-    """one generator (kind, selector_index, row, p0 .. p4) on the given rows whose selector cell holds its gate index"""
-    kind, si, gate, p = g[0], g[1], g[2], g[3:8]
-    if kind not in (GEN_REDUCING, GEN_REDUCING_EXT, GEN_QUOTIENT_EXT):
-        return fr.run_generator(wires, consts, pih, g, rows)
-    rows = np.asarray(rows, dtype=np.int64)
-    for r in rows[consts[si, rows] == np.uint64(gate)]:
-        w = [int(x) for x in wires[:, r]]
-        if kind == GEN_REDUCING:
-            reducing_row(w, p[0], p[1])
-        elif kind == GEN_REDUCING_EXT:
-            reducing_ext_row(w, p[0], p[1])
-        else:
-            quotient_ext_row(w, int(consts[p[1], r]), int(consts[p[2], r]), p[0], p[3])
-        wires[:, r] = np.array(w, dtype=np.uint64)
-
-
-def replay(wires, consts, gens, pih, sched):
-    """sipp_plonk_generate_witness_levels on the CPU: per level the generators of its rows, then the copies its outputs feed"""
-    w = np.ascontiguousarray(wires, dtype=np.uint64).copy()
-    flat = w.reshape(-1)
-    rows, lo, co = sched["rows"].astype(np.int64), sched["level_offsets"], sched["copy_offsets"]
-    src, dst = sched["copy_src"].astype(np.int64), sched["copy_dst"].astype(np.int64)
-    for lv in range(int(sched["n_levels"])):
-        r = rows[lo[lv]:lo[lv + 1]]
-        for g in gens:
-            run_generator(w, consts, pih, g, r)
-        flat[dst[co[lv]:co[lv + 1]]] = flat[src[co[lv]:co[lv + 1]]]
-    return w
-
-
-def row_local(wires, consts, gens, pih):
-    """sipp_plonk_generate_witness on the CPU: every generator on every row of its gate"""
-    w = np.ascontiguousarray(wires, dtype=np.uint64).copy()
-    for g in gens:
-        run_generator(w, consts, pih, g, np.arange(w.shape[1]))
-    return w
 
 
 def initial_data(inst, proof):

@@ -10,6 +10,7 @@ from sipp_amd import fri_fold as ff
 from tests import _fri_cases as fc
 from tests import _fri_fold_reading as fr
 from tests import _merkle_reading as mr
+from tests import _witness_reading as rd
 from tests import _oracle, _verify
 from tests.test_oracle_plonk import fri
 
@@ -224,7 +225,7 @@ def witness(o, betas=None, final=None, queries=None):
     args = (o["betas"] if betas is None else betas, o["final"] if final is None else final, o["queries"] if queries is None else queries)
     pis = c.public_inputs(*args)
     pih = _oracle.hash_no_pad(np.array(pis, dtype=np.uint64))
-    w = fr.replay(c.partial_witness(*args), o["cs"][:6], c.generators(), pih, c.schedule())
+    w = rd.replay(c.partial_witness(*args), o["cs"][:6], c.generators(), pih, c.schedule())
     return w, pis, pih
 
 

@@ -12,6 +12,7 @@ from tests import _fri_cases as fc
 from tests import _fri_fold_reading as fr
 from tests import _fri_initial_reading as ir
 from tests import _merkle_reading as mr
+from tests import _witness_reading as rd
 from tests import _oracle, _verify
 from tests.test_fri_fold_circuit import CASE_A4, CASE_A16, degree, nonzero, one_gate, rand_row, readers
 from tests.test_oracle_plonk import fri
@@ -182,7 +183,7 @@ def witness(o, args=None):
     args = o["args"] if args is None else args
     pis = c.public_inputs(*args)
     pih = _oracle.hash_no_pad(np.array(pis, dtype=np.uint64))
-    w = ir.replay(c.partial_witness(*args), o["cs"][:5], c.generators(), pih, c.schedule())
+    w = rd.replay(c.partial_witness(*args), o["cs"][:5], c.generators(), pih, c.schedule())
     return w, pis, pih
 
 

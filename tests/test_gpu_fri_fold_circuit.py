@@ -1,6 +1,6 @@
 """FRI fold chains in the outer circuit on the device: the ArithmeticExtension, Exponentiation and CosetInterpolation generators
 (SIPP_GEN_ARITHMETIC_EXT / _EXPONENTIATION / _COSET_INTERPOLATION) on all three launch paths against the Python reading
-(tests/_fri_fold_reading.py) cell for cell, the interpolation on thin levels both as the sixteen-lane scan and on one lane
+(tests/_witness_reading.py, tests/_fri_fold_reading.py) cell for cell, the interpolation on thin levels both as the sixteen-lane scan and on one lane
 (SIPP_ROUTE_WITNESS_INTERP_ONE_LANE); an opening proof made by the device read into FriFoldProver (sipp_amd/fri_fold.py), proved word for
 word as the oracle proves the read witness, accepted by both verifiers, refused when tampered with."""
 import ctypes as C
@@ -13,6 +13,9 @@ from sipp_amd import merkle as mk
 from tests import _fri_cases as fc
 from tests import _fri_fold_reading as fr
 from tests import _oracle
+from tests import _witness_reading as rd
+from tests._device import INTERP_ONE_LANE as ONE_LANE
+from tests._device import NO_GRAPH, dev, first_mismatch, host, levels, run_levels
 from tests.test_fri_fold_circuit import CASE_A4, CASE_A16
 from tests.test_gpu_fri_generic import to_params
 from tests.test_oracle_plonk import fri
@@ -21,7 +24,6 @@ pytestmark = pytest.mark.gpu
 
 P = _oracle.P
 W = 7
-ONE_LANE, NO_GRAPH = 16, 4
 DIGEST = (81, 82, 83, 84)
 NUM_WIRES, NUM_CONSTS = 135, 3
 LAY = mk.SWAP_LAYOUT
@@ -30,27 +32,12 @@ LAY = mk.SWAP_LAYOUT
 INTERP = {10: (1, 2), 11: (2, 2), 12: (3, 4), 13: (3, 8), 14: (4, 2), 15: (4, 4), 16: (4, 7), 17: (4, 16)}
 ARITH, EXPO, SWAP, RACC, OTHER = 20, 21, 22, 23, 30
 N_BITS = 64
-GENS = ([(fr.GEN_COSET_INTERPOLATION, 0, v, s, d, W, 0, 0) for v, (s, d) in INTERP.items()] +
-        [(fr.GEN_ARITHMETIC_EXT, 0, ARITH, 16, 1, 2, W, 0), (fr.GEN_EXPONENTIATION, 0, EXPO, N_BITS, 0, 0, 0, 0),
-         (mk.GEN_POSEIDON_SWAP, 0, SWAP, LAY["in_"], LAY["out"], LAY["sbox"], LAY["swap"], LAY["delta"]),
-         (mk.GEN_RANDOM_ACCESS, 0, RACC, 2, 22, 4, 0, 0)])
+GENS = ([(rd.GEN_COSET_INTERPOLATION, 0, v, s, d, W, 0, 0) for v, (s, d) in INTERP.items()] +
+        [(rd.GEN_ARITHMETIC_EXT, 0, ARITH, 16, 1, 2, W, 0), (rd.GEN_EXPONENTIATION, 0, EXPO, N_BITS, 0, 0, 0, 0),
+         (rd.GEN_POSEIDON_SWAP, 0, SWAP, LAY["in_"], LAY["out"], LAY["sbox"], LAY["swap"], LAY["delta"]),
+         (rd.GEN_RANDOM_ACCESS, 0, RACC, 2, 22, 4, 0, 0)])
 FOLD_GENS = GENS[:10]                       # the three new families alone
 KINDS = list(INTERP) + [ARITH, EXPO, SWAP, RACC]
-
-
-def dev(a):
-    from sipp_amd._lib import to_device
-    return to_device(a)
-
-
-def host(t):
-    from sipp_amd._lib import to_host
-    return to_host(t)
-
-
-def first_mismatch(got, want):
-    bad = np.argwhere(got != want)
-    return None if bad.size == 0 else (int(bad[0][0]), int(bad[0][1]), len(bad))
 
 
 @pytest.fixture(scope="module")
@@ -106,37 +93,12 @@ def test_row_local_generators_match_the_reading(ctx):
     log_n, n = 10, 1 << 10
     rng = np.random.default_rng(51)
     consts, w = table(rng, n, np.flatnonzero(np.arange(n) % 3 != 1), KINDS)
-    want = fr.row_local(w, consts, GENS, None)
+    want = rd.row_local(w, consts, GENS, None)
     other = consts[0] == OTHER
     assert other.sum() >= n // 3 and (want[:, other] == w[:, other]).all() and (want[:, ~other] != w[:, ~other]).any()
     d_w = dev(w)
     ctx.plonk_generate_witness(d_w, dev(consts), log_n, GENS)
     assert first_mismatch(host(d_w), want) is None
-
-
-def _levels(level_rows):
-    rows = np.concatenate([np.asarray(r, dtype=np.uint32) for r in level_rows])
-    lo = np.cumsum([0] + [len(r) for r in level_rows]).astype(np.uint32)
-    z = np.zeros(0, np.uint64)
-    return {"n_levels": len(level_rows), "rows": rows, "level_offsets": lo, "copy_src": z, "copy_dst": z,
-            "copy_offsets": np.zeros(len(level_rows) + 1, dtype=np.uint32)}
-
-
-def _run_levels(ctx, w, consts, log_n, gens, sc, routes):
-    import sipp_amd
-    want = fr.replay(w, consts, gens, None, sc)
-    sched = sipp_amd.PlonkSchedule.from_dict(sc)
-    L = sipp_amd.lib()
-    d_c, d_w = dev(consts), dev(w)
-    try:
-        for route in routes:
-            assert L.sipp_ctx_set_kernel_routes(ctx.h, route) == 0
-            d_w.copy_(dev(w))
-            ctx.plonk_generate_witness_levels(d_w, d_c, log_n, gens, None, sched)
-            assert first_mismatch(host(d_w), want) is None, route
-    finally:
-        assert L.sipp_ctx_set_kernel_routes(ctx.h, 0) == 0
-    return want
 
 
 def test_wide_level_mixing_the_three_families_matches_the_reading(ctx):
@@ -146,7 +108,7 @@ def test_wide_level_mixing_the_three_families_matches_the_reading(ctx):
     rows = np.flatnonzero(np.arange(n) % 2 == 0)
     assert len(rows) >= 16384
     consts, w = table(rng, n, rows, [k for k in KINDS if k not in (SWAP, RACC)])
-    want = _run_levels(ctx, w, consts, log_n, FOLD_GENS, _levels([rows]), (NO_GRAPH, 0, 0))
+    want = run_levels(ctx, w, consts, log_n, FOLD_GENS, levels([rows]), (NO_GRAPH, 0, 0))
     other = consts[0] == OTHER
     assert (want[:, other] == w[:, other]).all()
 
@@ -169,7 +131,7 @@ def test_thin_levels_mixing_interpolation_poseidon_and_short_rows_match_the_read
         held = set(int(v) for v in consts[0, r])
         assert held & set(INTERP) and (c == 1 or held - set(INTERP)), (c, held)
     assert set(int(v) for v in consts[0, level_rows[-1]]) == set(kinds)
-    want = _run_levels(ctx, w, consts, log_n, GENS, _levels(level_rows), (NO_GRAPH, 0, 0, ONE_LANE, ONE_LANE, ONE_LANE | NO_GRAPH, 0))
+    want = run_levels(ctx, w, consts, log_n, GENS, levels(level_rows), (NO_GRAPH, 0, 0, ONE_LANE, ONE_LANE, ONE_LANE | NO_GRAPH, 0))
     other = consts[0] == OTHER
     assert (want[:, other] == w[:, other]).all()
 
@@ -181,7 +143,7 @@ def test_bad_layouts_are_refused_and_the_ctx_still_generates(ctx):
     rng = np.random.default_rng(54)
     consts, w = table(rng, n, np.arange(n), KINDS)
     d_w, d_c = dev(w), dev(consts)
-    I, A, E = fr.GEN_COSET_INTERPOLATION, fr.GEN_ARITHMETIC_EXT, fr.GEN_EXPONENTIATION
+    I, A, E = rd.GEN_COSET_INTERPOLATION, rd.GEN_ARITHMETIC_EXT, rd.GEN_EXPONENTIATION
     bad = [(I, 0, 16, 0, 7, W, 0, 0), (I, 0, 16, 5, 7, W, 0, 0), (I, 0, 16, 4, 1, W, 0, 0), (I, 0, 16, 4, 0, W, 0, 0), (I, 0, 16, 4, 7, 0, 0, 0),
            (E, 0, EXPO, 0, 0, 0, 0, 0), (E, 0, EXPO, 65, 0, 0, 0, 0), (A, 0, ARITH, 0, 1, 2, W, 0), (A, 0, ARITH, 1, 1, 2, 0, 0),
            (A, 0, ARITH, 17, 1, 2, W, 0), (A, 0, ARITH, 1, 3, 2, W, 0), (A, 0, ARITH, 1, 1, 3, W, 0)]
@@ -198,12 +160,12 @@ def test_bad_layouts_are_refused_and_the_ctx_still_generates(ctx):
             ctx.plonk_generate_witness(d_n, d_c, log_n, [g])
         assert e.value.code == -1, g
         assert (host(d_n) == narrow).all()
-    sched = sipp_amd.PlonkSchedule.from_dict(_levels([np.arange(8)]))
+    sched = sipp_amd.PlonkSchedule.from_dict(levels([np.arange(8)]))
     with pytest.raises(sipp_amd.SippError) as e:
         ctx.plonk_generate_witness_levels(d_w, d_c, log_n, [bad[1]], None, sched)
     assert e.value.code == -1 and (host(d_w) == w).all()
     ctx.plonk_generate_witness(d_w, d_c, log_n, GENS)
-    assert first_mismatch(host(d_w), fr.row_local(w, consts, GENS, None)) is None
+    assert first_mismatch(host(d_w), rd.row_local(w, consts, GENS, None)) is None
 
 
 # ---- end to end ----------------------------------------------------------------------------------------------------------------------
@@ -262,7 +224,7 @@ def test_folds_of_a_device_opening_proof_prove_and_verify(ctx, opened, prover):
         pis = fcirc.public_inputs(*args)
         pih = _oracle.hash_no_pad(np.array(pis, dtype=np.uint64))
         pw = fcirc.partial_witness(*args)
-        want = fr.replay(pw, cs[:6], fcirc.generators(), pih, fcirc.schedule())
+        want = rd.replay(pw, cs[:6], fcirc.generators(), pih, fcirc.schedule())
         if round_ == 0:                                            # the device witness (the generation CircuitData.prove runs) = the reading
             sched = sipp_amd.PlonkSchedule.from_dict(fcirc.schedule())
             try:

@@ -1,5 +1,5 @@
 """FRI's initial combination in the outer circuit on the device: the ReducingExtension and quotient generators (SIPP_GEN_REDUCING_EXT /
-_QUOTIENT_EXT) and the base Reducing generator on all three launch paths against the Python reading (tests/_fri_initial_reading.py)
+_QUOTIENT_EXT) and the base Reducing generator on all three launch paths against the Python reading (tests/_witness_reading.py)
 cell for cell, the reducing rows on thin levels both as the sixteen-lane scan and on one lane (SIPP_ROUTE_WITNESS_REDUCE_ONE_LANE); an
 opening proof made by the device read into FriInitialProver (sipp_amd/fri_initial.py), proved word for word as the oracle proves the
 read witness, accepted by both verifiers, refused when tampered with."""
@@ -14,6 +14,8 @@ from tests import _fri_cases as fc
 from tests import _fri_fold_reading as fr
 from tests import _fri_initial_reading as ir
 from tests import _oracle
+from tests import _witness_reading as rd
+from tests._device import INTERP_ONE_LANE, NO_GRAPH, REDUCE_ONE_LANE, dev, first_mismatch, host, levels, run_levels
 from tests.test_fri_fold_circuit import CASE_A4, CASE_A16
 from tests.test_gpu_fri_generic import to_params
 from tests.test_oracle_plonk import fri
@@ -22,7 +24,6 @@ pytestmark = pytest.mark.gpu
 
 P = _oracle.P
 W = 7
-REDUCE_ONE_LANE, INTERP_ONE_LANE, NO_GRAPH = 32, 16, 4
 DIGEST = (95, 96, 97, 98)
 NUM_WIRES, NUM_CONSTS = 135, 3
 LAY = mk.SWAP_LAYOUT
@@ -31,34 +32,19 @@ RED = {40: 1, 41: 2, 42: 15, 43: 16, 44: 17, 45: 25, 46: 43}
 REDX = {50: 1, 51: 16, 52: 17, 53: 19, 54: 32}
 QUOT, QUOT_W4, INTERP, ARITH, EXPO, SWAP, RACC, OTHER = 60, 61, 16, 20, 21, 22, 23, 30
 N_BITS = 64
-RED_GENS = [(ir.GEN_REDUCING, 0, v, K, W, 0, 0, 0) for v, K in RED.items()]
-REDX_GENS = [(ir.GEN_REDUCING_EXT, 0, v, K, W, 0, 0, 0) for v, K in REDX.items()]
-QUOT_GENS = [(ir.GEN_QUOTIENT_EXT, 0, QUOT, 16, 1, 2, W, 0), (ir.GEN_QUOTIENT_EXT, 0, QUOT_W4, 1, 1, 2, 4, 0)]
-OLD_GENS = [(fr.GEN_COSET_INTERPOLATION, 0, INTERP, 4, 7, W, 0, 0),
-            (mk.GEN_POSEIDON_SWAP, 0, SWAP, LAY["in_"], LAY["out"], LAY["sbox"], LAY["swap"], LAY["delta"]),
-            (fr.GEN_ARITHMETIC_EXT, 0, ARITH, 16, 1, 2, W, 0), (fr.GEN_EXPONENTIATION, 0, EXPO, N_BITS, 0, 0, 0, 0),
-            (mk.GEN_RANDOM_ACCESS, 0, RACC, 2, 22, 4, 0, 0)]
+RED_GENS = [(rd.GEN_REDUCING, 0, v, K, W, 0, 0, 0) for v, K in RED.items()]
+REDX_GENS = [(rd.GEN_REDUCING_EXT, 0, v, K, W, 0, 0, 0) for v, K in REDX.items()]
+QUOT_GENS = [(rd.GEN_QUOTIENT_EXT, 0, QUOT, 16, 1, 2, W, 0), (rd.GEN_QUOTIENT_EXT, 0, QUOT_W4, 1, 1, 2, 4, 0)]
+OLD_GENS = [(rd.GEN_COSET_INTERPOLATION, 0, INTERP, 4, 7, W, 0, 0),
+            (rd.GEN_POSEIDON_SWAP, 0, SWAP, LAY["in_"], LAY["out"], LAY["sbox"], LAY["swap"], LAY["delta"]),
+            (rd.GEN_ARITHMETIC_EXT, 0, ARITH, 16, 1, 2, W, 0), (rd.GEN_EXPONENTIATION, 0, EXPO, N_BITS, 0, 0, 0, 0),
+            (rd.GEN_RANDOM_ACCESS, 0, RACC, 2, 22, 4, 0, 0)]
 # the level entry point takes at most 16 generators: the base reductions in one call, the extension reductions in another, both beside
 # the quotient, interpolation and Poseidon-swap rows
 CALL_A = RED_GENS + QUOT_GENS + OLD_GENS                # 7 + 2 + 5
 CALL_B = REDX_GENS + QUOT_GENS + OLD_GENS               # 5 + 2 + 5
 ALL_GENS = RED_GENS + REDX_GENS + QUOT_GENS + OLD_GENS
 KINDS_A, KINDS_B, KINDS_ALL = ([g[2] for g in gs] for gs in (CALL_A, CALL_B, ALL_GENS))
-
-
-def dev(a):
-    from sipp_amd._lib import to_device
-    return to_device(a)
-
-
-def host(t):
-    from sipp_amd._lib import to_host
-    return to_host(t)
-
-
-def first_mismatch(got, want):
-    bad = np.argwhere(got != want)
-    return None if bad.size == 0 else (int(bad[0][0]), int(bad[0][1]), len(bad))
 
 
 @pytest.fixture(scope="module")
@@ -116,38 +102,13 @@ def test_row_local_generators_match_the_reading(ctx):
     log_n, n = 10, 1 << 10
     rng = np.random.default_rng(71)
     consts, w, no_inverse = table(rng, n, np.flatnonzero(np.arange(n) % 3 != 1), KINDS_ALL)
-    want = ir.row_local(w, consts, ALL_GENS, None)
+    want = rd.row_local(w, consts, ALL_GENS, None)
     other = consts[0] == OTHER
     assert other.sum() >= n // 3 and (want[:, other] == w[:, other]).all() and (want[:, ~other] != w[:, ~other]).any()
     assert len(no_inverse) == 3 and (want[2:4, no_inverse] == 0).all() and (w[2:4, no_inverse] != 0).all()
     d_w = dev(w)
     ctx.plonk_generate_witness(d_w, dev(consts), log_n, ALL_GENS)
     assert first_mismatch(host(d_w), want) is None
-
-
-def _levels(level_rows):
-    rows = np.concatenate([np.asarray(r, dtype=np.uint32) for r in level_rows])
-    lo = np.cumsum([0] + [len(r) for r in level_rows]).astype(np.uint32)
-    z = np.zeros(0, np.uint64)
-    return {"n_levels": len(level_rows), "rows": rows, "level_offsets": lo, "copy_src": z, "copy_dst": z,
-            "copy_offsets": np.zeros(len(level_rows) + 1, dtype=np.uint32)}
-
-
-def _run_levels(ctx, w, consts, log_n, gens, sc, routes):
-    import sipp_amd
-    want = ir.replay(w, consts, gens, None, sc)
-    sched = sipp_amd.PlonkSchedule.from_dict(sc)
-    L = sipp_amd.lib()
-    d_c, d_w = dev(consts), dev(w)
-    try:
-        for route in routes:
-            assert L.sipp_ctx_set_kernel_routes(ctx.h, route) == 0
-            d_w.copy_(dev(w))
-            ctx.plonk_generate_witness_levels(d_w, d_c, log_n, gens, None, sched)
-            assert first_mismatch(host(d_w), want) is None, route
-    finally:
-        assert L.sipp_ctx_set_kernel_routes(ctx.h, 0) == 0
-    return want
 
 
 @pytest.mark.parametrize("call", ["base", "ext"])
@@ -160,7 +121,7 @@ def test_wide_level_matches_the_reading(ctx, call):
     assert len(rows) >= 16384
     gens = (RED_GENS if call == "base" else REDX_GENS) + QUOT_GENS + OLD_GENS[2:3]
     consts, w, _ = table(rng, n, rows, [g[2] for g in gens])
-    want = _run_levels(ctx, w, consts, log_n, gens, _levels([rows]), (NO_GRAPH, 0, 0))
+    want = run_levels(ctx, w, consts, log_n, gens, levels([rows]), (NO_GRAPH, 0, 0))
     other = consts[0] == OTHER
     assert (want[:, other] == w[:, other]).all()
 
@@ -190,7 +151,7 @@ def test_thin_levels_mixing_reductions_quotients_interpolation_and_poseidon_matc
         assert held & set(red) and (c == 1 or held - set(red)), (c, held)
     assert set(int(v) for v in consts[0, level_rows[-1]]) == set(kinds)
     routes = (0, NO_GRAPH, REDUCE_ONE_LANE, REDUCE_ONE_LANE | INTERP_ONE_LANE, REDUCE_ONE_LANE | NO_GRAPH, 0)
-    want = _run_levels(ctx, w, consts, log_n, gens, _levels(level_rows), routes)
+    want = run_levels(ctx, w, consts, log_n, gens, levels(level_rows), routes)
     other = consts[0] == OTHER
     assert (want[:, other] == w[:, other]).all()
     assert len(no_inverse) == 3 and (want[2:4, no_inverse] == 0).all() and (w[2:4, no_inverse] != 0).all()
@@ -203,7 +164,7 @@ def test_bad_layouts_are_refused_and_the_ctx_still_generates(ctx):
     rng = np.random.default_rng(74)
     consts, w, _ = table(rng, n, np.arange(n), KINDS_ALL)
     d_w, d_c = dev(w), dev(consts)
-    X, Q = ir.GEN_REDUCING_EXT, ir.GEN_QUOTIENT_EXT
+    X, Q = rd.GEN_REDUCING_EXT, rd.GEN_QUOTIENT_EXT
     bad = [(X, 0, 50, 0, W, 0, 0, 0), (X, 0, 50, 33, W, 0, 0, 0), (X, 0, 50, 1 << 30, W, 0, 0, 0), (X, 0, 50, 19, 0, 0, 0, 0),
            (Q, 0, QUOT, 0, 1, 2, W, 0), (Q, 0, QUOT, 17, 1, 2, W, 0), (Q, 0, QUOT, 1, 3, 2, W, 0), (Q, 0, QUOT, 1, 1, 3, W, 0),
            (Q, 0, QUOT, 1, 1, 2, 0, 0), (X, 3, 50, 1, W, 0, 0, 0)]
@@ -220,12 +181,12 @@ def test_bad_layouts_are_refused_and_the_ctx_still_generates(ctx):
             ctx.plonk_generate_witness(d_n, d_c, log_n, [g])
         assert e.value.code == -1, g
         assert (host(d_n) == narrow).all()
-    sched = sipp_amd.PlonkSchedule.from_dict(_levels([np.arange(8)]))
+    sched = sipp_amd.PlonkSchedule.from_dict(levels([np.arange(8)]))
     with pytest.raises(sipp_amd.SippError) as e:
         ctx.plonk_generate_witness_levels(d_w, d_c, log_n, [bad[0]], None, sched)
     assert e.value.code == -1 and (host(d_w) == w).all()
     ctx.plonk_generate_witness(d_w, d_c, log_n, ALL_GENS)
-    assert first_mismatch(host(d_w), ir.row_local(w, consts, ALL_GENS, None)) is None
+    assert first_mismatch(host(d_w), rd.row_local(w, consts, ALL_GENS, None)) is None
 
 
 def test_the_route_setter_takes_the_new_bit_and_no_unknown_one(ctx):
@@ -300,7 +261,7 @@ def test_the_combination_of_a_device_opening_proof_proves_and_verifies(ctx, open
         pis = circ.public_inputs(*args)
         pih = _oracle.hash_no_pad(np.array(pis, dtype=np.uint64))
         pw = circ.partial_witness(*args)
-        want = ir.replay(pw, cs[:5], circ.generators(), pih, circ.schedule())
+        want = rd.replay(pw, cs[:5], circ.generators(), pih, circ.schedule())
         if round_ == 0:                                            # the device witness (the generation CircuitData.prove runs) = the reading
             sched = sipp_amd.PlonkSchedule.from_dict(circ.schedule())
             try:

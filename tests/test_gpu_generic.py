@@ -3,6 +3,7 @@ import numpy as np
 import pytest
 
 from tests import _oracle
+from tests._device import dev, host
 from tests._oracle import P
 
 pytestmark = pytest.mark.gpu
@@ -14,16 +15,6 @@ def ctx():
     c = sipp_amd.Ctx(workspace_bytes=2 << 30)
     yield c
     c.close()
-
-
-def dev(a):
-    from sipp_amd._lib import to_device
-    return to_device(a)
-
-
-def host(t):
-    from sipp_amd._lib import to_host
-    return to_host(t)
 
 
 def test_poseidon_kats_and_random(ctx):

@@ -1,5 +1,5 @@
 """Merkle openings in the outer circuit on the device: the swap Poseidon generator (SIPP_GEN_POSEIDON_SWAP) on all three launch paths
-against the Python reading (tests/_merkle_reading.py) cell for cell; a commitment made by the library opened through MerkleOpeningProver
+against the Python reading (tests/_witness_reading.py) cell for cell; a commitment made by the library opened through MerkleOpeningProver
 (sipp_amd/merkle.py), proved word for word as the oracle proves the read witness, accepted by both verifiers, refused for every tampering."""
 import ctypes as C
 
@@ -9,6 +9,8 @@ import pytest
 from sipp_amd import merkle as mk
 from tests import _merkle_reading as mr
 from tests import _oracle
+from tests import _witness_reading as rd
+from tests._device import NO_GRAPH, dev, first_mismatch, host, levels, run_levels
 from tests.test_gpu_fri_generic import to_params
 from tests.test_oracle_plonk import fri
 
@@ -20,16 +22,7 @@ SHIFTED = {"in_": 40, "out": 5, "swap": 17, "delta": 0, "sbox": 60}
 DIGEST = (61, 62, 63, 64)
 LEAF_LEN, LOG_N_TREE, CAP_H, N_PATHS = 16, 12, 4, 28
 HEIGHT = LOG_N_TREE + 1 - CAP_H
-
-
-def dev(a):
-    from sipp_amd._lib import to_device
-    return to_device(a)
-
-
-def host(t):
-    from sipp_amd._lib import to_host
-    return to_host(t)
+ROUTES = (NO_GRAPH, 0, 0)                     # launch by launch, then the captured graph and its replay
 
 
 def swap_gen(lay, sel=0, row=5):
@@ -40,11 +33,6 @@ def table(rng, num_wires, n, lay, swap_rows):
     w = _oracle.rand_field(rng, (num_wires, n))
     w[lay["swap"], swap_rows] = rng.integers(0, 2, size=len(swap_rows), dtype=np.uint64)
     return w
-
-
-def first_mismatch(got, want):
-    bad = np.argwhere(got != want)
-    return None if bad.size == 0 else (int(bad[0][0]), int(bad[0][1]), len(bad))
 
 
 @pytest.fixture(scope="module")
@@ -64,40 +52,11 @@ def test_row_local_swap_generator_matches_the_reading(ctx, lay, num_wires):
     sel = np.where(np.arange(n) % 3 == 1, 7, 5).astype(np.uint64).reshape(1, n)
     w = table(rng, num_wires, n, lay, np.flatnonzero(sel[0] == 5))
     gens = [swap_gen(lay)]
-    want = mr.row_local(w, sel, gens, None)
+    want = rd.row_local(w, sel, gens, None)
     assert (want[:, sel[0] == 7] == w[:, sel[0] == 7]).all()
     d_w = dev(w)
     ctx.plonk_generate_witness(d_w, dev(sel), log_n, gens)
     assert first_mismatch(host(d_w), want) is None
-
-
-def _levels(level_rows, copies, n_levels):
-    """schedule dict from per-level row lists and per-level (src, dst) cell lists"""
-    rows = np.concatenate([np.asarray(r, dtype=np.uint32) for r in level_rows])
-    lo = np.cumsum([0] + [len(r) for r in level_rows]).astype(np.uint32)
-    src = np.concatenate([np.asarray([s for s, _ in c], dtype=np.uint64) for c in copies]) if any(copies) else np.zeros(0, np.uint64)
-    dst = np.concatenate([np.asarray([d for _, d in c], dtype=np.uint64) for c in copies]) if any(copies) else np.zeros(0, np.uint64)
-    co = np.cumsum([0] + [len(c) for c in copies]).astype(np.uint32)
-    return {"n_levels": n_levels, "rows": rows, "level_offsets": lo, "copy_src": src, "copy_dst": dst, "copy_offsets": co}
-
-
-def _run_levels(ctx, w, consts, log_n, gens, sc):
-    """both routes (one by one, captured graph + replay) on the device, each against the CPU replay"""
-    import sipp_amd
-    want = mr.replay(w, consts, gens, None, sc)
-    sched = sipp_amd.PlonkSchedule.from_dict(sc)
-    L = sipp_amd.lib()
-    d_c = dev(consts)
-    d_w = dev(w)
-    try:
-        for route in (4, 0, 0):
-            assert L.sipp_ctx_set_kernel_routes(ctx.h, route) == 0
-            d_w.copy_(dev(w))
-            ctx.plonk_generate_witness_levels(d_w, d_c, log_n, gens, None, sched)
-            assert first_mismatch(host(d_w), want) is None, route
-    finally:
-        assert L.sipp_ctx_set_kernel_routes(ctx.h, 0) == 0
-    return want
 
 
 def test_wide_level_of_swap_rows_matches_the_reading(ctx):
@@ -108,7 +67,7 @@ def test_wide_level_of_swap_rows_matches_the_reading(ctx):
     rows = np.flatnonzero(sel[0] == 5)
     assert len(rows) >= 16384
     w = table(rng, 135, n, LAY, rows)
-    _run_levels(ctx, w, sel, log_n, [swap_gen(LAY)], _levels([rows], [[]], 1))
+    run_levels(ctx, w, sel, log_n, [swap_gen(LAY)], levels([rows]), ROUTES)
 
 
 def test_chain_of_thin_swap_levels_matches_the_reading(ctx):
@@ -127,7 +86,7 @@ def test_chain_of_thin_swap_levels_matches_the_reading(ctx):
                 for t in range(4):
                     cj.append(((LAY["out"] + t) * n + int(row[j, c]), (LAY["in_"] + 4 * int(side[j + 1, c]) + t) * n + int(row[j + 1, c])))
         copies.append(cj)
-    want = _run_levels(ctx, w, sel, log_n, [swap_gen(LAY)], _levels(list(row), copies, links))
+    want = run_levels(ctx, w, sel, log_n, [swap_gen(LAY)], levels(list(row), copies), ROUTES)
     k = int(row[links - 1, 0])                                           # the last link read what the chain fed it
     assert (want[LAY["in_"] + 4 * int(side[-1, 0]):LAY["in_"] + 4 * int(side[-1, 0]) + 4, k] == want[LAY["out"]:LAY["out"] + 4, int(row[-2, 0])]).all()
 
@@ -144,7 +103,7 @@ def test_level_mixing_plain_and_swap_poseidon_rows_matches_the_reading(ctx, coun
     sel[0, rows] = np.where(rng.integers(0, 2, size=count) == 1, 5, 4).astype(np.uint64)
     w = table(rng, 136, n, LAY, rows)
     gens = [(8, 0, 4, 100, 0, 30, 0, 0), swap_gen(LAY)]
-    want = _run_levels(ctx, w, sel, log_n, gens, _levels([rows], [[]], 1))
+    want = run_levels(ctx, w, sel, log_n, gens, levels([rows]), ROUTES)
     assert (want[:, sel[0] == 7] == w[:, sel[0] == 7]).all()
 
 
@@ -162,7 +121,7 @@ def test_bad_swap_layouts_are_refused_and_the_ctx_still_generates(ctx):
         assert e.value.code == -1, bad
         assert (host(d_w) == w).all()
     ctx.plonk_generate_witness(d_w, d_c, log_n, [swap_gen(LAY)])
-    assert first_mismatch(host(d_w), mr.row_local(w, sel, [swap_gen(LAY)], None)) is None
+    assert first_mismatch(host(d_w), rd.row_local(w, sel, [swap_gen(LAY)], None)) is None
 
 
 # ---- end to end ----------------------------------------------------------------------------------------------------------------------
@@ -211,7 +170,7 @@ def test_openings_of_a_device_commitment_prove_and_verify(ctx, commitment, prove
         pis = mc.public_inputs(cap, idx, leaves)
         pih = _oracle.hash_no_pad(np.array(pis, dtype=np.uint64))
         pw = mc.partial_witness(cap, idx, leaves, sib)
-        want = mr.replay(pw, cs[:4], mc.generators(), pih, mc.schedule())
+        want = rd.replay(pw, cs[:4], mc.generators(), pih, mc.schedule())
         if round_ == 0:                                            # the device witness (the generation CircuitData.prove runs) = the reading
             d_w = dev(pw)
             ctx.plonk_generate_witness_levels(d_w, dev(cs[:4]), mc.log_n, mc.generators(), pih, sipp_amd.PlonkSchedule.from_dict(mc.schedule()))

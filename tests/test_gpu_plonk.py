@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from tests import _oracle, _verify
+from tests._device import dev, host
 from tests.test_gpu_fri_generic import to_params
 from tests.test_oracle_plonk import fri
 
@@ -31,16 +32,6 @@ def ctx():
     c = sipp_amd.Ctx(workspace_bytes=3 << 30)
     yield c
     c.close()
-
-
-def dev(a):
-    from sipp_amd._lib import to_device
-    return to_device(a)
-
-
-def host(t):
-    from sipp_amd._lib import to_host
-    return to_host(t)
 
 
 @pytest.mark.parametrize("log_n,R,D,C,rate_bits", CONFIGS)

@@ -10,6 +10,7 @@ import pytest
 
 from tests import _gate_edges as ge
 from tests import _oracle
+from tests._device import dev
 from tests.test_gpu_fri_generic import to_params
 from tests.test_oracle_plonk_gate_edges import DIGEST, assert_verdicts, cs_cap
 
@@ -25,11 +26,6 @@ def ctx():
     c = sipp_amd.Ctx(workspace_bytes=1 << 30)
     yield c
     c.close()
-
-
-def dev(a):
-    from sipp_amd._lib import to_device
-    return to_device(a)
 
 
 def oracle_proof(e, circ=None):

@@ -2,25 +2,17 @@
 that takes it -- sipp_plonk_generate_witness (one lane per row), and sipp_plonk_generate_witness_levels with thin levels on
 plonk_witness_level_coop_kernel or plonk_witness_level_coop_rows_kernel and a level of 16384 rows on plonk_witness_level_kernel -- cell
 for cell against the catalogue's exact reference (tests/test_oracle_witness_edges.py holds that reference against the CPU readings).  The
-crafted Poseidon rows make the carry of every output of the first MDS layer fire in each of witness.hip's three copies of that layer."""
+crafted Poseidon rows make the carry of every output of the first MDS layer fire in both of witness.hip's copies of that layer: mds(),
+which one lane walks, and poseidon_lanes(), which both sixteen-lane kernels call."""
 import numpy as np
 import pytest
 
 from tests import _witness_edges as we
+from tests._device import NO_GRAPH, dev, host
 
 pytestmark = pytest.mark.gpu
 
 CASES = we.cases()
-
-
-def dev(a):
-    from sipp_amd._lib import to_device
-    return to_device(a)
-
-
-def host(t):
-    from sipp_amd._lib import to_host
-    return to_host(t)
 
 
 @pytest.fixture(scope="module")
@@ -50,7 +42,7 @@ def test_device_witness_equals_the_reference_cell_for_cell(ctx, name, path):
     d_c = dev(e["consts"])
     sched = sipp_amd.PlonkSchedule.from_dict(sc) if sc is not None else None
     # one entry also launch by launch (SIPP_ROUTE_WITNESS_NO_GRAPH), then the captured graph and its replay
-    routes = (4, 0, 0) if name == we.NO_GRAPH_ENTRY else (0,)
+    routes = (NO_GRAPH, 0, 0) if name == we.NO_GRAPH_ENTRY else (0,)
     try:
         for route in routes:
             assert L.sipp_ctx_set_kernel_routes(ctx.h, route) == 0

@@ -6,6 +6,7 @@ import pytest
 
 from sipp_amd import merkle as mk
 from tests import _merkle_reading as mr
+from tests import _witness_reading as rd
 from tests import _oracle, _verify
 from tests.test_oracle_plonk import fri
 
@@ -107,7 +108,7 @@ def witness(o, cap=None, idx=None, leaves=None, sib=None):
     sib = o["sib"] if sib is None else sib
     pis = mc.public_inputs(cap, idx, leaves)
     pih = _oracle.hash_no_pad(np.array(pis, dtype=np.uint64))
-    w = mr.replay(mc.partial_witness(cap, idx, leaves, sib), o["cs"][:4], mc.generators(), pih, mc.schedule())
+    w = rd.replay(mc.partial_witness(cap, idx, leaves, sib), o["cs"][:4], mc.generators(), pih, mc.schedule())
     return w, pis, pih
 
 

@@ -14,6 +14,7 @@ from sipp_amd import merkle as mk
 from tests import _merkle_reading as mr
 from tests import _oracle
 from tests import _witness_edges as we
+from tests import _witness_reading as rd
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
 import plonk_synth as ps  # noqa: E402
@@ -39,8 +40,8 @@ def c_reading(e, gens, sched):
 
 def merkle_reading(e, gens, sched):
     if sched is None:
-        return mr.row_local(e["wires"], e["consts"], gens, e["pih"])
-    return mr.replay(e["wires"], e["consts"], gens, e["pih"], sched)
+        return rd.row_local(e["wires"], e["consts"], gens, e["pih"])
+    return rd.replay(e["wires"], e["consts"], gens, e["pih"], sched)
 
 
 @pytest.mark.parametrize("name,path", we.cases(), ids=["%s-%s" % c for c in we.cases()])
@@ -53,7 +54,7 @@ def test_reference_equals_the_other_readings_on_every_plan(name, path):
     again, written = we.generate(e["wires"], e["consts"], gens, e["pih"], sched)
     assert we.first_mismatch(e, again) is None and (written == e["written"]).all()
     has_swap = any(g[0] == we.POSEIDON_SWAP and held(e, g) for g in gens)
-    merkle_kinds = {mr.GEN_CONSTANT, mr.GEN_PUBLIC_INPUT, mr.GEN_BASE_SPLIT, mr.GEN_RANDOM_ACCESS, mr.GEN_POSEIDON, mr.GEN_POSEIDON_SWAP}
+    merkle_kinds = {rd.GEN_CONSTANT, rd.GEN_PUBLIC_INPUT, rd.GEN_BASE_SPLIT, rd.GEN_RANDOM_ACCESS, rd.GEN_POSEIDON, rd.GEN_POSEIDON_SWAP}
     if not has_swap:
         assert we.first_mismatch(e, c_reading(e, gens, sched)) is None
     if all(g[0] in merkle_kinds or not held(e, g) for g in gens):
@@ -64,7 +65,7 @@ def test_reference_equals_the_other_readings_on_every_plan(name, path):
         scheduled = np.zeros(1 << e["log_n"], dtype=bool)
         scheduled[sched["rows"]] = True
         c = _oracle.plonk_generate_witness_levels(e["wires"], e["consts"], e["log_n"], [g for g in gens if g[0] != we.POSEIDON_SWAP], e["pih"], sched)
-        m = mr.replay(e["wires"], e["consts"], [g for g in gens if g[0] == we.POSEIDON_SWAP], e["pih"], sched)
+        m = rd.replay(e["wires"], e["consts"], [g for g in gens if g[0] == we.POSEIDON_SWAP], e["pih"], sched)
         assert (c[:, ~swap_row] == e["expected"][:, ~swap_row]).all() and (m[:, swap_row] == e["expected"][:, swap_row]).all()
         assert (swap_row & scheduled).sum() > 1000 and (m[:, ~swap_row] == e["wires"][:, ~swap_row]).all()
 
