@@ -155,6 +155,68 @@ GL_HD uint64_t root_of_unity(unsigned k) {
 // signed integer -> field; the magnitude of a negative v is taken in uint64_t (-v overflows for INT64_MIN)
 GL_HD uint64_t from_i64(int64_t v) { return v >= 0 ? (uint64_t)v : P - (0 - (uint64_t)v); }
 
+// ---- the reduction of the lazy dot products (Acc6 below) as two 64-bit chains ----
+// value = a[0] + a[1] 2^22 + a[2] 2^44 + 2^32 (a[3] + a[4] 2^22 + a[5] 2^44) with a[i] = l_i + 2^32 h_i.  The twelve halves go into
+// two chains L (weight 1) and H (weight 2^32) with weights 1, 2^12 and 2^22 only (2^64 = 2^32 - 1, 2^96 = -1 mod p):
+//   N' = 2^12 h2 + h3 + 2^22 h4 + 2^12 l5          (enters H with +, L with -: each word of weight 2^64 is worth 2^32 - 1)
+//   L  = L0 + l0 + 2^22 l1 - N' - 2^12 h5
+//   H  = H0 + h0 + 2^22 h1 + 2^12 l2 + l3 + 2^22 l4 + N'
+// L0 = 2^56 - 2^32 + 1 and H0 = 2^32 - 2^24 (L0 + 2^32 H0 = p) keep L positive.  Input bound: NONE beyond the words themselves -- the
+// a[i] may be any u64 (Acc6's 1024 products; the hash kernels stay below 2^60): what L loses is below 2^54 + 2^46, L < 2^57, H < 2^56.
+// The fold: L + 2^32 H = L + (H >> 32)(2^32 - 1) + 2^32 lo(H) is one multiply-add (< 2^58) and one addition into the high word, whose
+// carry (2^64) is repaid by + (2^32 - 1); that cannot wrap, the high word after a carry is below 2^26.
+// Thirteen multiply-adds (the fold's among them), a 64-bit addition and subtraction, four instructions for the fold's carry and the
+// moves of L0 and H0: 24 instructions (scripts/count_valu.py scripts/ubench/acc6_reduce.hip).
+// On the device 1, 2^12 and 2^22 are opaque wave-uniform values: as literals the compiler spells the multiply-adds as 64-bit shifts and
+// split additions with zero-extension moves.
+// -> [0, 2^64), congruent to the value, not canonical.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define GL_CHAIN_STEP(x) asm("" : "+v"(x))    /* one multiply-add per term: keeps the compiler from regrouping the chains */
+#else
+#define GL_CHAIN_STEP(x) (void)0
+#endif
+GL_HD uint64_t reduce6(const uint64_t (&a)[6]) {
+    uint32_t z = 0;
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm("" : "+s"(z));
+#endif
+    const uint32_t p1 = 1u + z, p12 = (1u << 12) + z, p22 = (1u << 22) + z;
+    const uint32_t l0 = (uint32_t)a[0], l1 = (uint32_t)a[1], l2 = (uint32_t)a[2], l3 = (uint32_t)a[3], l4 = (uint32_t)a[4], l5 = (uint32_t)a[5];
+    const uint32_t h0 = (uint32_t)(a[0] >> 32), h1 = (uint32_t)(a[1] >> 32), h2 = (uint32_t)(a[2] >> 32);
+    const uint32_t h3 = (uint32_t)(a[3] >> 32), h4 = (uint32_t)(a[4] >> 32), h5 = (uint32_t)(a[5] >> 32);
+    uint64_t n = (uint64_t)h3 * p1;
+    GL_CHAIN_STEP(n);
+    n = (uint64_t)h2 * p12 + n;
+    GL_CHAIN_STEP(n);
+    n = (uint64_t)h4 * p22 + n;
+    GL_CHAIN_STEP(n);
+    n = (uint64_t)l5 * p12 + n;                                     // N' < 2^55
+    GL_CHAIN_STEP(n);
+    uint64_t H = (uint64_t)h0 * p1 + 0xFF000000ULL;                 // H0
+    GL_CHAIN_STEP(H);
+    H = (uint64_t)l3 * p1 + H;
+    GL_CHAIN_STEP(H);
+    H = (uint64_t)l2 * p12 + H;
+    GL_CHAIN_STEP(H);
+    H = (uint64_t)h1 * p22 + H;
+    GL_CHAIN_STEP(H);
+    H = (uint64_t)l4 * p22 + H;
+    GL_CHAIN_STEP(H);
+    H += n;
+    uint64_t L = (uint64_t)l0 * p1 + 0x00FFFFFF00000001ULL;         // L0
+    GL_CHAIN_STEP(L);
+    L = (uint64_t)l1 * p22 + L;
+    GL_CHAIN_STEP(L);
+    uint64_t m = (uint64_t)h5 * p12 + n;
+    GL_CHAIN_STEP(m);
+    L -= m;
+    const uint64_t t = (uint64_t)(uint32_t)(H >> 32) * (uint32_t)EPS + L;
+    const uint32_t th = (uint32_t)(t >> 32), mid = th + (uint32_t)H;
+    const uint64_t r = ((uint64_t)mid << 32) | (uint32_t)t;
+    return mid < th ? r + EPS : r;
+}
+#undef GL_CHAIN_STEP
+
 #if defined(__HIPCC__)
 #define GL_D __device__ __forceinline__
 // ---- lazy dot products on the 32-bit VALU ----
@@ -179,34 +241,8 @@ struct Acc6 {
             a[3 + j] += (uint64_t)xh * c[j];
         }
     }
-    // t[0..3] = a0 + a1 2^22 + a2 2^44 (a's < 2^60: the sum is < 2^105)
-    static GL_D void fold3(uint32_t (&t)[4], uint64_t a0, uint64_t a1, uint64_t a2) {
-        const uint32_t a1l = (uint32_t)a1, a1h = (uint32_t)(a1 >> 32), a2l = (uint32_t)a2, a2h = (uint32_t)(a2 >> 32);
-        uint32_t c = 0;
-        t[0] = __builtin_addc((uint32_t)a0, a1l << 22, c, &c);
-        t[1] = __builtin_addc((uint32_t)(a0 >> 32), (uint32_t)(a1 >> 10), c, &c);
-        t[2] = (a1h >> 10) + c;
-        c = 0;
-        t[1] = __builtin_addc(t[1], a2l << 12, c, &c);
-        t[2] = __builtin_addc(t[2], (uint32_t)(a2 >> 20), c, &c);
-        t[3] = (a2h >> 20) + c;
-    }
-    // -> [0, 2^64), congruent to the value, not canonical
-    GL_D uint64_t reduce() const {
-        uint32_t l[4], h[4], v[5];
-        fold3(l, a[0], a[1], a[2]);
-        fold3(h, a[3], a[4], a[5]);
-        uint32_t c = 0;
-        v[0] = l[0];
-        v[1] = __builtin_addc(l[1], h[0], c, &c);
-        v[2] = __builtin_addc(l[2], h[1], c, &c);
-        v[3] = __builtin_addc(l[3], h[2], c, &c);
-        v[4] = h[3] + c;
-        const uint64_t r = reduce128_nc(((uint64_t)v[3] << 32) | v[2], ((uint64_t)v[1] << 32) | v[0]);
-        const uint64_t t = (uint64_t)v[4] << 32;  // 2^128 = -2^32 (mod p)
-        const uint64_t d = r - t;
-        return r < t ? d - EPS : d;
-    }
+    // -> [0, 2^64), congruent to the value, not canonical; the a[] may be any u64 (reduce6 above)
+    GL_D uint64_t reduce() const { return reduce6(a); }
 };
 
 // sum of full 64 x 64 products (both factors per-lane values) in 160 bits, one reduction at the end

@@ -73,6 +73,9 @@ __device__ __forceinline__ uint64_t sub_nc(uint64_t u, uint64_t w) {
 //   T += b p                           = T - (2^32 - 1) mod 2^64, cannot wrap the other way
 // Measured: 1.41 -> 1.65 T products/s alone (scripts/ubench/mulmod4.hip); the one-state-per-lane leaf hash 1.65 -> 1.85 G permutations/s
 // at 2^17 leaves and 2.01 -> 2.21 G at 2^21 (its S-boxes are 472 of these per permutation); nothing in the transform kernels.
+// (Re-measured after the tree sweeps' rewrite, window v80 .. v89 in ntt_tree.hip: 9 % fewer instructions and the sweeps alone 2 % faster, inside
+// their spread -- but 90 instead of 74 VGPRs, and the lone n = 128 instance, whose sweeps share the SIMDs with the 168-VGPR leaf waves of the
+// other proofs, 4.3 ms SLOWER: profiles/r07_valu_diet.txt.  Not used there.)
 }  // namespace gll
 // GLL_R<i> = "v<GLL_T + i>", GLL_P<i> = "v[<GLL_T + i>:<GLL_T + i + 1>]" (i even).  The product library uses ONE window (v140 .. v149,
 // poseidon.hip); the microbenchmarks' other windows come from their own table (scripts/ubench/gl_lazy_regs.inc via GLL_REGS_INC).

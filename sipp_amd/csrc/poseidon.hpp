@@ -191,7 +191,7 @@ __device__ __forceinline__ void mds_full_mfma(uint64_t s[12], const uint64_t* __
 // dense_tables / dense_model).  x_e: ANY u64, as 8 byte planes (the transposes of mds_full_mfma); the constants: 8 signed base-256 digits;
 // 64 products of (plane a) x (digit b), chained in the accumulator by t = a + b (<= 8 x 12 x 2^14 < 2^21 each), and the fifteen sums D_t
 // folded into two signed 64-bit chains L, H with 2^64 = 2^32 - 1, 2^96 = -1 (mod p): 19 multiply-adds per output instead of 66 (72) and
-// ONE 96-bit reduction (4 instructions) instead of an Acc6 reduction (~50).  The A fragments have the block-diagonal layout of
+// ONE 96-bit reduction (4 instructions) instead of an Acc6 reduction (24).  The A fragments have the block-diagonal layout of
 // mds_a_fragment, so every lane finds its own outputs in accumulator registers 0 .. 11.
 template <bool ADDEND>
 __device__ __forceinline__ void dense_mfma(const uint32_t lo[12], const uint32_t hi[12], uint32_t mat, uint64_t out[12], const uint64_t* __restrict__ addend,

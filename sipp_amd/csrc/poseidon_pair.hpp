@@ -249,22 +249,8 @@ __device__ __forceinline__ uint64_t mul_chain(uint64_t a, uint64_t b) {
     gl::mul_wide(a, b, hi, lo);
     return gll::reduce128_nc(hi, lo);
 }
-// gl::Acc6::reduce with that reduction
-__device__ __forceinline__ uint64_t acc6_reduce(const gl::Acc6& acc) {
-    uint32_t l[4], h[4], v[5];
-    gl::Acc6::fold3(l, acc.a[0], acc.a[1], acc.a[2]);
-    gl::Acc6::fold3(h, acc.a[3], acc.a[4], acc.a[5]);
-    uint32_t c = 0;
-    v[0] = l[0];
-    v[1] = __builtin_addc(l[1], h[0], c, &c);
-    v[2] = __builtin_addc(l[2], h[1], c, &c);
-    v[3] = __builtin_addc(l[3], h[2], c, &c);
-    v[4] = h[3] + c;
-    const uint64_t r = gll::reduce128_nc(((uint64_t)v[3] << 32) | v[2], ((uint64_t)v[1] << 32) | v[0]);
-    const uint64_t t = (uint64_t)v[4] << 32;  // 2^128 = -2^32 (mod p)
-    const uint64_t d = r - t;
-    return r < t ? d - gl::EPS : d;
-}
+// the lazy sums of the partial rounds: the two-chain reduction of gl.hpp (its fold is the 96-bit shape, no 128-bit reduction behind it)
+__device__ __forceinline__ uint64_t acc6_reduce(const gl::Acc6& acc) { return acc.reduce(); }
 
 // The 22 partial rounds, lazily in two blocks of 11 (the algebra: poseidon.hpp::partial_rounds_blocked).  s0: element 0, held by both
 // lanes.  A lane keeps the x_k of its parity (k = 2 m + h): they are its inputs of the V product and its share of the triangular sums.
