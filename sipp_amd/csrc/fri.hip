@@ -274,13 +274,14 @@ int sipp_fri_prove_openings(sipp_ctx* ctx, const sipp_oracle* oracles, size_t n_
     for (size_t b = 0; b < n_batches; b++) {
         d_zp[b] = arena_alloc_t<uint64_t>(ctx, 2 * n);
         if (!d_zp[b]) return SIPP_E_NOMEM;
-        SIPP_TRY(sipp_k_pow_table(ctx, points[b], n, d_zp[b]));
+        SIPP_TRY(sipp_k_pow_tables(ctx, &points[b], &d_zp[b], 1, n));
         // the point zero has no inverse: its table of z^k (1, 0, 0, ...) still opens the constant terms, and the quotient below is
         // the composition shifted down by one coefficient instead of a division (d_zip stays NULL)
         if (gl::canon(points[b].c0) == 0 && gl::canon(points[b].c1) == 0) continue;
         d_zip[b] = arena_alloc_t<uint64_t>(ctx, 2 * n);
         if (!d_zip[b]) return SIPP_E_NOMEM;
-        SIPP_TRY(sipp_k_pow_table(ctx, gl::inv(points[b]), n, d_zip[b]));
+        const gl::E2 inv = gl::inv(points[b]);
+        SIPP_TRY(sipp_k_pow_tables(ctx, &inv, &d_zip[b], 1, n));
     }
     for (size_t b = 0; b < n_batches; b++) {
         const size_t k = batch_len(batches[b]);
@@ -290,7 +291,9 @@ int sipp_fri_prove_openings(sipp_ctx* ctx, const sipp_oracle* oracles, size_t n_
         for (uint32_t r = 0; r < batches[b].n_ranges; r++) {
             const sipp_poly_range& rg = batches[b].ranges[r];
             const size_t cnt = rg.col_end - rg.col_begin;
-            SIPP_TRY(sipp_k_openings(ctx, oracles[rg.oracle].d_coeffs + (size_t)rg.col_begin * n, cnt, n, d_zp[b], nullptr, d_open + 4 * at));
+            const uint64_t* const cf[3] = {oracles[rg.oracle].d_coeffs + (size_t)rg.col_begin * n, nullptr, nullptr};
+            const uint32_t nc3[3] = {(uint32_t)cnt, 0, 0};
+            SIPP_TRY(sipp_k_openings(ctx, cf, nc3, n, d_zp[b], nullptr, d_open + 4 * at, /*stark=*/false));
             at += cnt;
         }
         std::vector<uint64_t> hop(4 * k + 4);

@@ -682,16 +682,8 @@ __global__ void __launch_bounds__(256) quotient_finish_kernel(QuotArgs a) {
 // =====================================================================================================
 // power tables, openings, FRI combine / divide / fold
 // =====================================================================================================
-// tab[k] = base^k (ext), SoA: c0 at [0, n), c1 at [n, 2n)
-__global__ void pow_table_kernel(E2 base, size_t n, uint64_t* __restrict__ tab) {
-    size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= n) return;
-    E2 r = gl::pow(base, (uint64_t)k);
-    tab[k] = r.c0;
-    tab[n + k] = r.c1;
-}
-
-// the four tables of an opening (zeta, g zeta and their inverses) in ONE launch: blockIdx.y selects the base
+// tab[k] = base^k (ext), SoA: c0 at [0, n), c1 at [n, 2n); up to four tables (an opening's zeta, g zeta and their inverses) in ONE
+// launch: blockIdx.y selects the base, the grid's y dimension is the number of tables
 struct Pow4Args {
     E2 base[4];
     uint64_t* tab[4];
@@ -714,7 +706,7 @@ __global__ void pow_table4_kernel(Pow4Args a) {
 // 160 bits (gl::Acc160) and reduced once per lane.
 // (more columns per block would re-use the tables but leave too few waves in flight: measured)
 // (tn = the distance between the two components of a power table: the tables hold [c0[n] | c1[n]]; a block that sums a SEGMENT of
-// the rows -- openings_seg_kernel -- passes pointers to the segment's first row and the whole table's n)
+// the rows passes pointers to the segment's first row and the whole table's n)
 __device__ __forceinline__ void openings_column(const uint64_t* __restrict__ col, size_t n, const uint64_t* __restrict__ t0,
                                                 const uint64_t* __restrict__ t1, size_t tn, uint64_t* __restrict__ out4) {
     __shared__ uint64_t s[4][256];
@@ -764,42 +756,20 @@ __device__ __forceinline__ void openings_column(const uint64_t* __restrict__ col
     if (threadIdx.x < 4) out4[threadIdx.x] = s[threadIdx.x][0];
 }
 
-__global__ void __launch_bounds__(256) openings_kernel(const uint64_t* __restrict__ coeffs, size_t n, uint32_t ncols,
-                                                      const uint64_t* __restrict__ t0, const uint64_t* __restrict__ t1,
-                                                      uint64_t* __restrict__ out) {
-    openings_column(coeffs + (size_t)blockIdx.x * n, n, t0, t1, n, out + (size_t)blockIdx.x * 4);
-}
+// One block per (column of the concatenation of up to three oracles, segment of the rows): block (b, y) sums the gridDim.y-th part of
+// column b's rows into partial[b][y][4]; oracle 2 (a STARK's quotient chunks) is opened at the first point only.  With ONE segment
+// partial[b][0][4] is the layout of the opened values themselves: the launch writes them and nothing follows.
 // Launches of FEW columns (the outer prover's oracles: 84 + 136 + 20 + 16 polynomials of 2^18 .. 2^20 coefficients, one launch per
-// range of a batch) leave most of the 256 CUs idle with one block per column: 2.9 ms of a 37.7-ms proof at 2^18 rows.  Block (column,
-// segment) sums gridDim.y-th of the rows into partial[column][segment][4]; openings_fold_kernel adds the segments (field sums: the
-// result does not depend on the split).
-__global__ void __launch_bounds__(256) openings_seg_kernel(const uint64_t* __restrict__ coeffs, size_t n, size_t seg_len,
-                                                          const uint64_t* __restrict__ t0, const uint64_t* __restrict__ t1,
-                                                          uint64_t* __restrict__ partial) {
-    const size_t lo = (size_t)blockIdx.y * seg_len, len = min(seg_len, n - lo);
-    openings_column(coeffs + (size_t)blockIdx.x * n + lo, len, t0 + lo, t1 ? t1 + lo : nullptr, n,
-                    partial + ((size_t)blockIdx.x * gridDim.y + blockIdx.y) * 4);
-}
-__global__ void __launch_bounds__(256) openings_fold_kernel(const uint64_t* __restrict__ partial, uint32_t ncols, uint32_t segs,
-                                                           uint64_t* __restrict__ out) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;     // (column, component)
-    if (i >= 4 * ncols) return;
-    const uint64_t* p = partial + (size_t)(i >> 2) * segs * 4 + (i & 3);
-    uint64_t acc = 0;
-    for (uint32_t sg = 0; sg < segs; sg++) acc = gl::add(acc, p[4 * sg]);
-    out[i] = acc;
-}
-
-// the three oracles of a STARK (trace, Z, quotient chunks) in ONE launch: block b opens column b of their concatenation; the
-// quotient chunks are opened at the first point only
-struct Open3Args {
+// range of a batch) leave most of the 256 CUs idle with one block per column: 2.9 ms of a 37.7-ms proof at 2^18 rows.  Hence the
+// segments; openings_fold_kernel adds them (field sums: the result does not depend on the split).
+struct OpenArgs {
     const uint64_t* coeffs[3];
     uint32_t ncols[3];
-    size_t n;
+    size_t n, seg_len;
     const uint64_t *t0, *t1;
-    uint64_t* out;
+    uint64_t* partial;     // [total columns][segments][4]
 };
-__global__ void __launch_bounds__(256) openings3_kernel(Open3Args a) {
+__global__ void __launch_bounds__(256) openings_kernel(OpenArgs a) {
     const uint32_t b = blockIdx.x;
     const uint64_t* col;
     const uint64_t* t1 = a.t1;
@@ -811,26 +781,29 @@ __global__ void __launch_bounds__(256) openings3_kernel(Open3Args a) {
         col = a.coeffs[2] + (size_t)(b - a.ncols[0] - a.ncols[1]) * a.n;
         t1 = nullptr;
     }
-    openings_column(col, a.n, a.t0, t1, a.n, a.out + (size_t)b * 4);
+    const size_t lo = (size_t)blockIdx.y * a.seg_len, len = min(a.seg_len, a.n - lo);
+    openings_column(col + lo, len, a.t0 + lo, t1 ? t1 + lo : nullptr, a.n, a.partial + ((size_t)b * gridDim.y + blockIdx.y) * 4);
+}
+__global__ void __launch_bounds__(256) openings_fold_kernel(const uint64_t* __restrict__ partial, uint32_t ncols, uint32_t segs,
+                                                           uint64_t* __restrict__ out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;     // (column, component)
+    if (i >= 4 * ncols) return;
+    const uint64_t* p = partial + (size_t)(i >> 2) * segs * 4 + (i & 3);
+    uint64_t acc = 0;
+    for (uint32_t sg = 0; sg < segs; sg++) acc = gl::add(acc, p[4 * sg]);
+    out[i] = acc;
 }
 
 // The same three oracles with the power tables shared by a GROUP of columns (round 5).  With one block per column every block streams
 // its column AND the four power tables (two points x two components): five words from memory per coefficient, four of them tables --
-// at 2^21 rows the tables (64 MB) fit no cache and openings3_kernel ran at 0.4 of the bandwidth its columns alone need (29.8 ms per
+// at 2^21 rows the tables (64 MB) fit no cache and openings_kernel ran at 0.4 of the bandwidth its columns alone need (29.8 ms per
 // n = 4096 instance against 11.7 ms for 58 GB at 5 TB/s).  Block (group of OG columns of ONE oracle, segment of the rows): a lane loads
 // the four table words of a row once and multiplies them into OG x 4 accumulators; partial[column][segment][4] is folded by
 // openings_fold_kernel.  The quotient chunks (oracle 2) are opened at the first point only.
 // (groups of 2 / 3 / 6 / 8 columns and 1 / 4 rows in flight per lane measured: 4 x 2 is the fastest at n = 128, 1024 and 4096 --
 //  0.75 / 4.4 / 18.3 ms of openings per instance against 1.08 / 7.5 / 29.8 with one block per column; 8 columns: 1.3 / 5.4 / 19.7)
 constexpr int OG = 4;
-struct OpenGArgs {
-    const uint64_t* coeffs[3];
-    uint32_t ncols[3];
-    size_t n, seg_len;
-    const uint64_t *t0, *t1;
-    uint64_t* partial;     // [total columns][segments][4]
-};
-__global__ void __launch_bounds__(256) openings_group_kernel(OpenGArgs a) {
+__global__ void __launch_bounds__(256) openings_group_kernel(OpenArgs a) {
     __shared__ uint64_t s[4][256];
     // which oracle, which columns
     uint32_t g = blockIdx.x, orc = 0, col_base = 0;
@@ -901,40 +874,58 @@ __global__ void __launch_bounds__(256) openings_group_kernel(OpenGArgs a) {
     }
 }
 
-// partial[slice][{0,1}][{c0,c1}][k]: acc over the columns of this slice of alpha^c * coef_c[k];
-// batch 1 (trace | Z) is the same sum restricted to c < n1.
-struct CombArgs {
+// composition F[k] = sum_c alpha^c col_c[k], in slices of the columns: partial[slice][{0,1}][{c0,c1}][k] holds the slice's part of
+// F (slot 0) and, for a STARK, of batch 1 (trace | Z: the same sum restricted to c < n1; slots 2 and 3).  The division kernels read
+// this [slices][4][n] layout.
+// Where column c lives: three oracles back to back (a STARK's trace, Z, quotient chunks) ...
+struct Cols3 {
     const uint64_t* src[3];
     int cnt[3];
+    __device__ __forceinline__ int total() const { return cnt[0] + cnt[1] + cnt[2]; }
+    __device__ __forceinline__ const uint64_t* operator()(int c, size_t n) const {
+        const int cnt0 = cnt[0], cnt01 = cnt[0] + cnt[1];
+        return c < cnt0 ? src[0] + (size_t)c * n : c < cnt01 ? src[1] + (size_t)(c - cnt0) * n : src[2] + (size_t)(c - cnt01) * n;
+    }
+};
+// ... or an arbitrary list of coefficient columns (the generic batches: a pointer table)
+struct ColsTable {
+    const uint64_t* const* cols;
+    int count;
+    __device__ __forceinline__ int total() const { return count; }
+    __device__ __forceinline__ const uint64_t* operator()(int c, size_t) const { return cols[c]; }
+};
+template <class Cols>
+struct CombArgs {
+    Cols cols;
     size_t n;
     const uint32_t* apow3; // [total][2][3]: limbs (gl::limbs3) of alpha^c as (c0, c1)
-    int n1;                // columns in batch 1 (W + P)
+    int n1;                // SPLIT: columns in batch 1 (W + P)
     int slices;
     uint64_t* partial;     // [slices][4][n]
 };
 // the weights alpha^c are wave-uniform (lanes run over the coefficient index k): lazy multiply-accumulate with the limbs
-// of alpha^c (gl::Acc6, six v_mad_u64_u32 per extension component), one reduction per slice.  A column belongs either
+// of alpha^c (gl::Acc6, six v_mad_u64_u32 per extension component), one reduction per slice.  SPLIT: a column belongs either
 // to batch 1 (c < n1) or not, so g (batch 1) and h (the rest) are accumulated separately and f = g + h.
-__global__ void __launch_bounds__(256) fri_combine_kernel(CombArgs a) {
+// CB columns per trip: their coefficients are loaded before the first multiply-add (one load per trip of a rolled loop made the STARK's
+// kernel wait out a memory latency per column: it takes eight; the generic batches' kernel takes one)
+template <bool SPLIT, int CB, class Cols>
+__device__ __forceinline__ void fri_combine(const CombArgs<Cols> a) {
     const size_t k = (size_t)blockIdx.x * 256 + threadIdx.x;
-    const int total = a.cnt[0] + a.cnt[1] + a.cnt[2];
+    const int total = a.cols.total();
     const int per = (total + a.slices - 1) / a.slices;   // <= 1024 terms per accumulator (host checks)
     const int c_lo = blockIdx.y * per, c_hi = min(total, c_lo + per);
     gl::Acc6 G0, G1, H0, H1;
     G0.zero(); G1.zero(); H0.zero(); H1.zero();
-    const uint64_t *src0 = a.src[0], *src1 = a.src[1], *src2 = a.src[2];
-    const int cnt0 = a.cnt[0], cnt01 = a.cnt[0] + a.cnt[1], n1 = a.n1;
+    const int n1 = a.n1;
     const size_t nn = a.n;
     const uint32_t* __restrict__ apow3 = a.apow3;
-    auto col_of = [=](int c) -> const uint64_t* {
-        return c < cnt0 ? src0 + (size_t)c * nn : c < cnt01 ? src1 + (size_t)(c - cnt0) * nn : src2 + (size_t)(c - cnt01) * nn;
-    };
+    // (a macro, not a lambda: behind a by-reference capture the accumulators ended up in scratch memory)
 #define SIPP_COMB_TERM(cc, vv)                                             \
     do {                                                                   \
         const uint64_t v_ = (vv);                                          \
         const uint32_t lo_ = (uint32_t)v_, hi_ = (uint32_t)(v_ >> 32);     \
         const uint32_t* __restrict__ w_ = apow3 + 6 * (cc);                \
-        if ((cc) < n1) { /* wave-uniform */                                \
+        if (!SPLIT || (cc) < n1) { /* wave-uniform */                      \
             G0.mac(lo_, hi_, w_);                                          \
             G1.mac(lo_, hi_, w_ + 3);                                      \
         } else {                                                           \
@@ -942,54 +933,34 @@ __global__ void __launch_bounds__(256) fri_combine_kernel(CombArgs a) {
             H1.mac(lo_, hi_, w_ + 3);                                      \
         }                                                                  \
     } while (0)
-    // eight columns per trip: their coefficients are loaded before the first multiply-add (one load per trip of a rolled
-    // loop made the kernel wait out a memory latency per column)
-    constexpr int CB = 8;
     int c = c_lo;
-    for (; c + CB <= c_hi; c += CB) {
-        uint64_t v[CB];
+    if constexpr (CB > 1)
+        for (; c + CB <= c_hi; c += CB) {
+            uint64_t v[CB];
 #pragma unroll
-        for (int b = 0; b < CB; b++) v[b] = col_of(c + b)[k];
+            for (int b = 0; b < CB; b++) v[b] = a.cols(c + b, nn)[k];
 #pragma unroll
-        for (int b = 0; b < CB; b++) SIPP_COMB_TERM(c + b, v[b]);
-    }
-    for (; c < c_hi; c++) SIPP_COMB_TERM(c, col_of(c)[k]);
+            for (int b = 0; b < CB; b++) SIPP_COMB_TERM(c + b, v[b]);
+        }
+    for (; c < c_hi; c++) SIPP_COMB_TERM(c, a.cols(c, nn)[k]);
 #undef SIPP_COMB_TERM
     const uint64_t g0 = gl::canon(G0.reduce()), g1 = gl::canon(G1.reduce());
     uint64_t* p = a.partial + (size_t)blockIdx.y * 4 * a.n;
-    p[k] = gl::add(g0, gl::canon(H0.reduce()));
-    p[a.n + k] = gl::add(g1, gl::canon(H1.reduce()));
-    p[2 * a.n + k] = g0;
-    p[3 * a.n + k] = g1;
-}
-
-// generic batch composition F[k] = sum_j alpha^j col_j[k] for an arbitrary list of coefficient columns (pointer table):
-// the same lazy accumulation, written in the [slices][4][n] layout the division kernels read (batch slot 0)
-struct GCombArgs {
-    const uint64_t* const* cols;
-    int total;
-    size_t n;
-    const uint32_t* apow3;  // [total][2][3]
-    int slices;
-    uint64_t* partial;      // [slices][4][n]
-};
-__global__ void __launch_bounds__(256) fri_gcombine_kernel(GCombArgs a) {
-    const size_t k = (size_t)blockIdx.x * 256 + threadIdx.x;
-    const int per = (a.total + a.slices - 1) / a.slices;
-    const int c_lo = blockIdx.y * per, c_hi = min(a.total, c_lo + per);
-    gl::Acc6 G0, G1;
-    G0.zero(); G1.zero();
-    for (int c = c_lo; c < c_hi; c++) {
-        const uint64_t v = a.cols[c][k];
-        const uint32_t lo = (uint32_t)v, hi = (uint32_t)(v >> 32);
-        const uint32_t* __restrict__ w = a.apow3 + 6 * c;
-        G0.mac(lo, hi, w);
-        G1.mac(lo, hi, w + 3);
+    if (SPLIT) {
+        p[k] = gl::add(g0, gl::canon(H0.reduce()));
+        p[a.n + k] = gl::add(g1, gl::canon(H1.reduce()));
+        p[2 * a.n + k] = g0;
+        p[3 * a.n + k] = g1;
+    } else {
+        p[k] = g0;
+        p[a.n + k] = g1;
     }
-    uint64_t* p = a.partial + (size_t)blockIdx.y * 4 * a.n;
-    p[k] = gl::canon(G0.reduce());
-    p[a.n + k] = gl::canon(G1.reduce());
 }
+// (two plain kernels over a body that takes its arguments BY VALUE: as instances of a kernel template, or with the body taking a reference,
+// the compiler no longer proves that the column pointers it loads from the table point to global memory and reads the columns with flat
+// loads)
+__global__ void __launch_bounds__(256) fri_combine_kernel(CombArgs<Cols3> a) { fri_combine<true, 8>(a); }
+__global__ void __launch_bounds__(256) fri_gcombine_kernel(CombArgs<ColsTable> a) { fri_combine<false, 1>(a); }
 
 // acc = acc * shift + q   (ext, SoA [2][n])
 __global__ void fri_accum_kernel(uint64_t* __restrict__ acc, const uint64_t* __restrict__ q, size_t n, E2 shift, int first) {
@@ -1449,120 +1420,108 @@ int sipp_k_quotient(sipp_ctx* ctx, const air_spec_t* a, uint32_t log_n, const ui
     return SIPP_OK;
 }
 
-int sipp_k_pow_table(sipp_ctx* ctx, gl::E2 base, size_t n, uint64_t* d_tab) {
+int sipp_k_pow_tables(sipp_ctx* ctx, const gl::E2* base, uint64_t* const* d_tab, int count, size_t n) {
+    if (count < 1 || count > 4) return sipp_fail(ctx, SIPP_E_BADARG, "pow_tables: one to four tables per launch");
     ProfScope ps(ctx, "pow_table");
-    hipLaunchKernelGGL(pow_table_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, base, n, d_tab);
-    SIPP_CHECK_HIP(ctx, hipGetLastError());
-    return SIPP_OK;
-}
-
-int sipp_k_pow_table4(sipp_ctx* ctx, const gl::E2 base[4], size_t n, uint64_t* const d_tab[4]) {
-    ProfScope ps(ctx, "pow_table");
-    Pow4Args a;
-    for (int i = 0; i < 4; i++) {
+    Pow4Args a{};
+    for (int i = 0; i < count; i++) {
         a.base[i] = base[i];
         a.tab[i] = d_tab[i];
     }
     a.n = n;
-    hipLaunchKernelGGL(pow_table4_kernel, dim3((unsigned)((n + 255) / 256), 4), dim3(256), 0, ctx->stream, a);
+    hipLaunchKernelGGL(pow_table4_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)count), dim3(256), 0, ctx->stream, a);
     SIPP_CHECK_HIP(ctx, hipGetLastError());
     return SIPP_OK;
 }
 
-int sipp_k_openings(sipp_ctx* ctx, const uint64_t* d_coeffs, size_t ncols, size_t n, const uint64_t* d_t0,
-                    const uint64_t* d_t1, uint64_t* d_out) {
-    if (!ncols) return SIPP_OK;
-    ProfScope ps(ctx, "openings");
-    // about 2048 blocks whatever the column count; a segment is at least 1024 rows
-    const size_t want = (2048 + ncols - 1) / ncols, segs = std::min<size_t>(std::min<size_t>(64, want), n / 1024);
-    if (segs <= 1) {
-        hipLaunchKernelGGL(openings_kernel, dim3((unsigned)ncols), dim3(256), 0, ctx->stream, d_coeffs, n, (uint32_t)ncols, d_t0, d_t1,
-                           d_out);
-    } else {
-        ArenaScope scope(ctx);   // (the stream is ordered: later users of the block wait)
-        uint64_t* partial = arena_alloc_t<uint64_t>(ctx, ncols * segs * 4);
-        if (!partial) return SIPP_E_NOMEM;
-        const size_t seg_len = (n + segs - 1) / segs;
-        hipLaunchKernelGGL(openings_seg_kernel, dim3((unsigned)ncols, (unsigned)segs), dim3(256), 0, ctx->stream, d_coeffs, n, seg_len,
-                           d_t0, d_t1, partial);
-        hipLaunchKernelGGL(openings_fold_kernel, dim3((unsigned)((4 * ncols + 255) / 256)), dim3(256), 0, ctx->stream, partial,
-                           (uint32_t)ncols, (uint32_t)segs, d_out);
-    }
-    SIPP_CHECK_HIP(ctx, hipGetLastError());
-    return SIPP_OK;
-}
-
-int sipp_k_openings3(sipp_ctx* ctx, const uint64_t* const d_coeffs[3], const uint32_t ncols[3], size_t n, const uint64_t* d_t0,
-                     const uint64_t* d_t1, uint64_t* d_out) {
+int sipp_k_openings(sipp_ctx* ctx, const uint64_t* const d_coeffs[3], const uint32_t ncols[3], size_t n, const uint64_t* d_t0,
+                    const uint64_t* d_t1, uint64_t* d_out, bool stark) {
     const unsigned total = ncols[0] + ncols[1] + ncols[2];
     if (!total) return SIPP_OK;
     ProfScope ps(ctx, "openings");
-    Open3Args a;
+    OpenArgs a;
+    unsigned groups = 0;
     for (int i = 0; i < 3; i++) {
         a.coeffs[i] = d_coeffs[i];
         a.ncols[i] = ncols[i];
-    }
-    a.n = n; a.t0 = d_t0; a.t1 = d_t1; a.out = d_out;
-    const bool grouped = !(ctx->kernel_routes & SIPP_ROUTE_OPENINGS_UNGROUPED);   // the fallback route stays tested (test_gpu_stark.py)
-    if (!grouped || n < 1024) {
-        hipLaunchKernelGGL(openings3_kernel, dim3(total), dim3(256), 0, ctx->stream, a);
-        SIPP_CHECK_HIP(ctx, hipGetLastError());
-        return SIPP_OK;
-    }
-    OpenGArgs g;
-    unsigned groups = 0;
-    for (int i = 0; i < 3; i++) {
-        g.coeffs[i] = d_coeffs[i];
-        g.ncols[i] = ncols[i];
         groups += (ncols[i] + OG - 1) / OG;
     }
-    // about 4096 blocks; a segment is at least 1024 rows and there are at most SIPP_OPENINGS_MAX_SEGS of them (the arena contract)
-    const size_t segs = std::max<size_t>(1, std::min<size_t>(std::min<size_t>(SIPP_OPENINGS_MAX_SEGS, (4096 + groups - 1) / groups), n / 1024));
+    const bool grouped = stark && !(ctx->kernel_routes & SIPP_ROUTE_OPENINGS_UNGROUPED);   // the fallback route stays tested (test_gpu_stark.py)
+    // Segments of the rows, at least 1024 rows each:
+    //   a STARK, grouped     about 4096 blocks, at most SIPP_OPENINGS_MAX_SEGS segments (the arena contract), always folded
+    //   a STARK, ungrouped   one block per column writes the opened values
+    //   generic ranges       about 2048 blocks whatever the column count, at most 64 segments; folded when there is more than one
+    const size_t most = grouped ? std::min<size_t>(SIPP_OPENINGS_MAX_SEGS, (4096 + groups - 1) / groups)
+                        : stark ? 1
+                                : std::min<size_t>(64, (2048 + total - 1) / total);
+    const size_t segs = std::max<size_t>(1, std::min<size_t>(most, n / 1024));
+    const bool fold = grouped || segs > 1;
     ArenaScope scope(ctx);   // (the stream is ordered: later users of the block wait)
-    g.partial = arena_alloc_t<uint64_t>(ctx, (size_t)total * segs * 4);
-    if (!g.partial) return SIPP_E_NOMEM;
-    g.n = n; g.seg_len = (n + segs - 1) / segs; g.t0 = d_t0; g.t1 = d_t1;
-    hipLaunchKernelGGL(openings_group_kernel, dim3(groups, (unsigned)segs), dim3(256), 0, ctx->stream, g);
-    hipLaunchKernelGGL(openings_fold_kernel, dim3((4 * total + 255) / 256), dim3(256), 0, ctx->stream, g.partial, (uint32_t)total,
-                       (uint32_t)segs, d_out);
+    a.partial = fold ? arena_alloc_t<uint64_t>(ctx, (size_t)total * segs * 4) : d_out;
+    if (!a.partial) return SIPP_E_NOMEM;
+    a.n = n; a.seg_len = (n + segs - 1) / segs; a.t0 = d_t0; a.t1 = d_t1;
+    if (grouped)
+        hipLaunchKernelGGL(openings_group_kernel, dim3(groups, (unsigned)segs), dim3(256), 0, ctx->stream, a);
+    else
+        hipLaunchKernelGGL(openings_kernel, dim3(total, (unsigned)segs), dim3(256), 0, ctx->stream, a);
+    if (fold)
+        hipLaunchKernelGGL(openings_fold_kernel, dim3((4 * total + 255) / 256), dim3(256), 0, ctx->stream, a.partial, (uint32_t)total,
+                           (uint32_t)segs, d_out);
     SIPP_CHECK_HIP(ctx, hipGetLastError());
     return SIPP_OK;
+}
+
+// The scratch of a composition and its division, and in how many slices the columns are combined: from `first` on doubled (up to 64)
+// until (block, slice) pairs fill `fill` blocks -- short traces with many columns (Fq12) get more slices -- and no slice is above the
+// accumulators' 1024 columns (MapToG2's 13 631 columns at 2^16 rows).  Every refusal comes before the first launch.
+struct FriScratch {
+    int slices;
+    uint64_t *partial, *q, *scan, *totals;   // [slices][4][n], [2 batches][2][n] twice, [2 batches][n / 1024][2]
+};
+static int fri_scratch(sipp_ctx* ctx, size_t n, int total_cols, int first, size_t fill, const char* too_many, const char* bad_n,
+                       FriScratch* s) {
+    int slices = first;
+    while (slices < 64 && ((n / 256) * (size_t)slices < fill || (total_cols + slices - 1) / slices > 1024)) slices *= 2;
+    if ((total_cols + slices - 1) / slices > 1024) return sipp_fail(ctx, SIPP_E_UNSUPPORTED, too_many);
+    if (n % 1024) return sipp_fail(ctx, SIPP_E_BADARG, bad_n);
+    s->slices = slices;
+    s->partial = arena_alloc_t<uint64_t>(ctx, (size_t)slices * 4 * n);
+    s->q = arena_alloc_t<uint64_t>(ctx, 4 * n);
+    s->scan = arena_alloc_t<uint64_t>(ctx, 4 * n);
+    s->totals = arena_alloc_t<uint64_t>(ctx, (size_t)4 * (n / 1024));
+    return s->partial && s->q && s->scan && s->totals ? SIPP_OK : SIPP_E_NOMEM;
+}
+// s.q[b] = (F - F(z_b)) / (X - z_b) for `batches` (1 or 2) batches: slot b of s.partial, the tables zp[b] of z_b^k and zip[b] of z_b^-k
+// (the profile scope "fri_divide" is the caller's: it has always covered the kernel that consumes s.q as well)
+static void fri_divide(sipp_ctx* ctx, const FriScratch& s, size_t n, unsigned batches, const uint64_t* const zp[2],
+                       const uint64_t* const zip[2]) {
+    DivArgs d{};
+    d.partial = s.partial; d.slices = s.slices; d.n = n;
+    d.zp[0] = zp[0]; d.zp[1] = zp[1]; d.zip[0] = zip[0]; d.zip[1] = zip[1];
+    d.qout = s.q;
+    const unsigned ntiles = (unsigned)(n / 1024);
+    hipLaunchKernelGGL(fri_divide_tiles, dim3(ntiles, batches), dim3(1024), 0, ctx->stream, d, s.scan, s.totals);
+    hipLaunchKernelGGL(fri_divide_carry, dim3(batches), dim3(256), 0, ctx->stream, s.totals, (int)ntiles);
+    hipLaunchKernelGGL(fri_divide_finish, dim3(ntiles, batches), dim3(1024), 0, ctx->stream, d, s.scan, s.totals);
 }
 
 int sipp_k_fri_final(sipp_ctx* ctx, const uint64_t* const src[3], const int cnt[3], size_t n, const uint32_t* d_apow3,
                      int n1, gl::E2 shift1, const uint64_t* d_zp[2], const uint64_t* d_zip[2], uint64_t* d_final) {
     ArenaScope scope(ctx);   // the scratch goes back on EVERY exit path (the stream is ordered: later users of the block wait)
-    // enough (block, slice) pairs to fill the chip: short traces with many columns (Fq12) get more slices
-    // (and no slice above the kernel's 1024 columns: MapToG2's 13 631 columns at 2^16 rows)
-    const int total_cols = cnt[0] + cnt[1] + cnt[2];
-    int slices = 8;
-    while (slices < 64 && ((n / 256) * (size_t)slices < 2048 || (total_cols + slices - 1) / slices > 1024)) slices *= 2;
-    uint64_t* partial = arena_alloc_t<uint64_t>(ctx, (size_t)slices * 4 * n);
-    uint64_t* q = arena_alloc_t<uint64_t>(ctx, 4 * n);
-    if (!partial || !q) return SIPP_E_NOMEM;
-    CombArgs c{};
-    for (int i = 0; i < 3; i++) { c.src[i] = src[i]; c.cnt[i] = cnt[i]; }
-    c.n = n; c.apow3 = d_apow3; c.n1 = n1; c.slices = slices; c.partial = partial;
-    if ((cnt[0] + cnt[1] + cnt[2] + slices - 1) / slices > 1024) return sipp_fail(ctx, SIPP_E_UNSUPPORTED, "fri_combine: more than 1024 columns per slice");
+    FriScratch s;
+    SIPP_TRY(fri_scratch(ctx, n, cnt[0] + cnt[1] + cnt[2], 8, 2048, "fri_combine: more than 1024 columns per slice",
+                         "fri_divide: n must be a multiple of 1024", &s));
+    CombArgs<Cols3> c{};
+    for (int i = 0; i < 3; i++) { c.cols.src[i] = src[i]; c.cols.cnt[i] = cnt[i]; }
+    c.n = n; c.apow3 = d_apow3; c.n1 = n1; c.slices = s.slices; c.partial = s.partial;
     {
         ProfScope ps(ctx, "fri_combine");
-        hipLaunchKernelGGL(fri_combine_kernel, dim3((unsigned)(n / 256), slices), dim3(256), 0, ctx->stream, c);
+        hipLaunchKernelGGL(fri_combine_kernel, dim3((unsigned)(n / 256), s.slices), dim3(256), 0, ctx->stream, c);
     }
-    DivArgs d{};
-    d.partial = partial; d.slices = slices; d.n = n;
-    d.zp[0] = d_zp[0]; d.zp[1] = d_zp[1]; d.zip[0] = d_zip[0]; d.zip[1] = d_zip[1];
-    d.qout = q;
-    const unsigned ntiles = (unsigned)(n / 1024);
-    uint64_t* scan = arena_alloc_t<uint64_t>(ctx, 4 * n);
-    uint64_t* totals = arena_alloc_t<uint64_t>(ctx, (size_t)4 * ntiles);
-    if (!scan || !totals) return SIPP_E_NOMEM;
-    if (n % 1024) return sipp_fail(ctx, SIPP_E_BADARG, "fri_divide: n must be a multiple of 1024");
     {
         ProfScope ps(ctx, "fri_divide");
-        hipLaunchKernelGGL(fri_divide_tiles, dim3(ntiles, 2), dim3(1024), 0, ctx->stream, d, scan, totals);
-        hipLaunchKernelGGL(fri_divide_carry, dim3(2), dim3(256), 0, ctx->stream, totals, (int)ntiles);
-        hipLaunchKernelGGL(fri_divide_finish, dim3(ntiles, 2), dim3(1024), 0, ctx->stream, d, scan, totals);
-        hipLaunchKernelGGL(fri_final_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, q, n, shift1, d_final);
+        fri_divide(ctx, s, n, 2, d_zp, d_zip);
+        hipLaunchKernelGGL(fri_final_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, s.q, n, shift1, d_final);
     }
     SIPP_CHECK_HIP(ctx, hipGetLastError());
     return SIPP_OK;
@@ -1573,36 +1532,24 @@ int sipp_k_fri_final(sipp_ctx* ctx, const uint64_t* const src[3], const int cnt[
 int sipp_k_fri_batch_quotient(sipp_ctx* ctx, const uint64_t* const* d_cols, int total, size_t n, const uint32_t* d_apow3,
                               const uint64_t* d_zp, const uint64_t* d_zip, gl::E2 shift, bool first, uint64_t* d_acc) {
     ArenaScope scope(ctx);   // the scratch goes back on EVERY exit path (the stream is ordered: later users of the block wait)
-    int slices = 1;
-    while (slices < 64 && ((n / 256) * (size_t)slices < 1024 || (total + slices - 1) / slices > 1024)) slices *= 2;
-    if ((total + slices - 1) / slices > 1024) return sipp_fail(ctx, SIPP_E_UNSUPPORTED, "fri: more than 65536 polynomials in one batch");
-    if (n % 1024) return sipp_fail(ctx, SIPP_E_BADARG, "fri: degree must be a multiple of 1024");
-    uint64_t* partial = arena_alloc_t<uint64_t>(ctx, (size_t)slices * 4 * n);
-    uint64_t* q = arena_alloc_t<uint64_t>(ctx, 4 * n);
-    uint64_t* scan = arena_alloc_t<uint64_t>(ctx, 4 * n);
-    const unsigned ntiles = (unsigned)(n / 1024);
-    uint64_t* totals = arena_alloc_t<uint64_t>(ctx, (size_t)4 * ntiles);
-    if (!partial || !q || !scan || !totals) return SIPP_E_NOMEM;
-    GCombArgs c{};
-    c.cols = d_cols; c.total = total; c.n = n; c.apow3 = d_apow3; c.slices = slices; c.partial = partial;
-    DivArgs d{};
-    d.partial = partial; d.slices = slices; d.n = n;
-    d.zp[0] = d_zp; d.zp[1] = d_zp; d.zip[0] = d_zip; d.zip[1] = d_zip;
-    d.qout = q;
+    FriScratch s;
+    SIPP_TRY(fri_scratch(ctx, n, total, 1, 1024, "fri: more than 65536 polynomials in one batch", "fri: degree must be a multiple of 1024", &s));
+    CombArgs<ColsTable> c{};
+    c.cols.cols = d_cols; c.cols.count = total; c.n = n; c.apow3 = d_apow3; c.slices = s.slices; c.partial = s.partial;
     {
         ProfScope ps(ctx, "fri_combine");
-        hipLaunchKernelGGL(fri_gcombine_kernel, dim3((unsigned)(n / 256), slices), dim3(256), 0, ctx->stream, c);
+        hipLaunchKernelGGL(fri_gcombine_kernel, dim3((unsigned)(n / 256), s.slices), dim3(256), 0, ctx->stream, c);
     }
-    if (!d_zip) {   // the point zero (the caller's branch): no division
-        ProfScope ps(ctx, "fri_shift_down");
-        hipLaunchKernelGGL(fri_shift_down_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, partial, slices, n, q);
-        hipLaunchKernelGGL(fri_accum_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_acc, q, n, shift, first ? 1 : 0);
-    } else {
-        ProfScope ps(ctx, "fri_divide");
-        hipLaunchKernelGGL(fri_divide_tiles, dim3(ntiles, 1), dim3(1024), 0, ctx->stream, d, scan, totals);
-        hipLaunchKernelGGL(fri_divide_carry, dim3(1), dim3(256), 0, ctx->stream, totals, (int)ntiles);
-        hipLaunchKernelGGL(fri_divide_finish, dim3(ntiles, 1), dim3(1024), 0, ctx->stream, d, scan, totals);
-        hipLaunchKernelGGL(fri_accum_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_acc, q, n, shift, first ? 1 : 0);
+    {
+        // the point zero (the caller's branch): no division
+        ProfScope ps(ctx, d_zip ? "fri_divide" : "fri_shift_down");
+        if (d_zip) {
+            const uint64_t *const zp[2] = {d_zp, d_zp}, *const zip[2] = {d_zip, d_zip};
+            fri_divide(ctx, s, n, 1, zp, zip);
+        } else {
+            hipLaunchKernelGGL(fri_shift_down_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, s.partial, s.slices, n, s.q);
+        }
+        hipLaunchKernelGGL(fri_accum_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_acc, s.q, n, shift, first ? 1 : 0);
     }
     SIPP_CHECK_HIP(ctx, hipGetLastError());
     return SIPP_OK;

@@ -23,16 +23,16 @@ int sipp_k_z_columns(sipp_ctx* ctx, const air_spec_t* a, const uint64_t* d_trace
 int sipp_k_quotient(sipp_ctx* ctx, const air_spec_t* a, uint32_t log_n, const uint64_t* d_lde, const uint64_t* d_zlde,
                     size_t lde_stride, const uint64_t* d_aux, const uint64_t alpha[2], const uint64_t beta[2],
                     const uint64_t gamma[2], uint64_t* d_out);
-int sipp_k_pow_table(sipp_ctx* ctx, gl::E2 base, size_t n, uint64_t* d_tab);
-int sipp_k_pow_table4(sipp_ctx* ctx, const gl::E2 base[4], size_t n, uint64_t* const d_tab[4]);
-int sipp_k_openings(sipp_ctx* ctx, const uint64_t* d_coeffs, size_t ncols, size_t n, const uint64_t* d_t0,
-                    const uint64_t* d_t1, uint64_t* d_out);
+// count (1 .. 4) tables of base[i]^k, k < n, in one launch
+int sipp_k_pow_tables(sipp_ctx* ctx, const gl::E2* base, uint64_t* const* d_tab, int count, size_t n);
 // (scratch of the grouped form: at most SIPP_OPENINGS_MAX_SEGS x 4 words per column -- sipp_workspace_bytes_cfg counts them)
 constexpr size_t SIPP_OPENINGS_MAX_SEGS = 32;
 // a gadget of more than 64 products is evaluated by up to this many lanes per quotient point (prover.hip: slices of its product list)
 constexpr int SIPP_QUOTIENT_MAX_SLICES = 8;
-int sipp_k_openings3(sipp_ctx* ctx, const uint64_t* const d_coeffs[3], const uint32_t ncols[3], size_t n, const uint64_t* d_t0,
-                     const uint64_t* d_t1, uint64_t* d_out);
+// the columns of up to three oracles, concatenated, at the points of the tables d_t0 and d_t1 (NULL: one point; oracle 2 is opened
+// at the first point only): d_out [column][4].  stark: the launch shape of a STARK's three oracles, else that of a generic range
+int sipp_k_openings(sipp_ctx* ctx, const uint64_t* const d_coeffs[3], const uint32_t ncols[3], size_t n, const uint64_t* d_t0,
+                    const uint64_t* d_t1, uint64_t* d_out, bool stark);
 int sipp_k_fri_final(sipp_ctx* ctx, const uint64_t* const src[3], const int cnt[3], size_t n, const uint32_t* d_apow3,
                      int n1, gl::E2 shift1, const uint64_t* d_zp[2], const uint64_t* d_zip[2], uint64_t* d_final);
 int sipp_k_fri_batch_quotient(sipp_ctx* ctx, const uint64_t* const* d_cols, int total, size_t n, const uint32_t* d_apow3,

@@ -386,12 +386,12 @@ static int prove_impl(sipp_ctx* ctx, int kind, const uint32_t* ios, size_t num_i
     {
         const gl::E2 bases[4] = {zeta, gzeta, gl::inv(zeta), gl::inv(gzeta)};
         uint64_t* const tabs[4] = {d_zp[0], d_zp[1], d_zip[0], d_zip[1]};
-        SIPP_TRY(sipp_k_pow_table4(ctx, bases, n, tabs));
+        SIPP_TRY(sipp_k_pow_tables(ctx, bases, tabs, 4, n));
     }
     {
         const uint64_t* const cf[3] = {T.coeffs, Z.coeffs, Qo.coeffs};
         const uint32_t nc3[3] = {(uint32_t)W, (uint32_t)P, (uint32_t)Q};
-        SIPP_TRY(sipp_k_openings3(ctx, cf, nc3, n, d_zp[0], d_zp[1], d_open));
+        SIPP_TRY(sipp_k_openings(ctx, cf, nc3, n, d_zp[0], d_zp[1], d_open, /*stark=*/true));
     }
     std::vector<uint64_t> hop((size_t)(W + P + Q) * 4);
     SIPP_CHECK_HIP(ctx, hipMemcpyAsync(hop.data(), d_open, hop.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
