@@ -370,14 +370,20 @@ int sipp_fri_prove_openings(sipp_ctx *ctx, const sipp_oracle *oracles, size_t n_
  * are not part of this (the circuit is built by un-vendored crates). */
 typedef struct {
     uint32_t num_routed_wires;   /* CircuitConfig::num_routed_wires (80 in standard_recursion_config) */
-    uint32_t max_degree;         /* quotient_degree_factor = chunk size of the partial products (8); a power of two, 2 .. 64 */
+    uint32_t max_degree;         /* quotient_degree_factor = chunk size of the partial products (8); a power of two, 2 .. 64 for
+                                  * sipp_plonk_zs_partial_products alone: the quotient and the whole argument need
+                                  * 2^rate_bits >= max_degree with rate_bits <= 3, so 2 .. 8 (16 .. 64: SIPP_E_UNSUPPORTED there) */
     uint32_t num_challenges;     /* CircuitConfig::num_challenges (2); 1 .. 8 */
 } sipp_plonk_params;
 /* CommonCircuitData::num_partial_products = ceil(num_routed_wires / max_degree) - 1 */
 uint32_t sipp_plonk_num_partial_products(const sipp_plonk_params *p);
 /* d_wires, d_sigmas: [num_routed_wires][N] VALUES in natural row order (sigma[j][i] = k_col' w^row' of the wire that (j, i) maps to,
  * k_j = 7^j); betas, gammas: num_challenges host words.  d_out [num_challenges (1 + num_partial_products)][N] values in the column order
- * of the zs_partial_products commitment: Z_0 .. Z_{C-1}, then the partial products of challenge 0, of challenge 1, ... */
+ * of the zs_partial_products commitment: Z_0 .. Z_{C-1}, then the partial products of challenge 0, of challenge 1, ...
+ * A chunk whose denominator prod_j (w_j + beta sigma_j + gamma) vanishes is 0 (1 / 0 = 0, chunk by chunk, as plonky2's batch inversion
+ * and oracle/plonk.c have it): that chunk alone -- the row's other chunks, and the other challenges, keep their values.
+ * betas, gammas (and alphas below) and the cells of d_wires may be any u64 congruent to the value; d_sigmas and every LDE handed to the
+ * quotient hold canonical words (< p), as the commitments write them. */
 int sipp_plonk_zs_partial_products(sipp_ctx *ctx, const uint64_t *d_wires, const uint64_t *d_sigmas, uint32_t log_n,
                                    const sipp_plonk_params *p, const uint64_t *betas, const uint64_t *gammas, uint64_t *d_out);
 /* compute_quotient_polys for the permutation terms, from the three committed oracles' LDEs (leaf order, blowup 2^rate_bits >=

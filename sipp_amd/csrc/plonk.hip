@@ -10,8 +10,9 @@
 // 7 <w_(N D)> is simply the FIRST N D leaves of a blowup-2^rate_bits LDE (leaf t = coset index bitrev(t)), and the quotient values are
 // written in leaf order, which is what the coset iNTT (bit-reversed in, natural out) reads.
 // Kernels: one lane per row (chunk quotients with ONE inversion per row and challenge: Montgomery's trick over the <= 32 chunk
-// denominators), a two-level prefix product over the rows for Z, one lane per coset point for the quotient.  All HBM-streaming with
-// O(R) products per cell read -- integer VALU bound like the STARK quotient kernels.
+// denominators; a denominator that is 0 stays out of the trick and makes its own chunk 0, as the oracle's cell-by-cell 1 / 0 = 0), a
+// two-level prefix product over the rows for Z, one lane per coset point for the quotient.  All HBM-streaming with O(R) products per
+// cell read -- integer VALU bound like the STARK quotient kernels.
 #include "ctx.hpp"
 #include "prover.hpp"
 #include <algorithm>
@@ -49,8 +50,9 @@ __global__ void __launch_bounds__(256) plonk_chunk_kernel(ZsArgs a) {
             de = gl::mul(de, gl::add(gl::add(wv, gl::mul(beta, a.sigmas[(size_t)j * n + i])), gamma));
         }
         num[q] = nu;
-        pre[q] = run;                 // product of the denominators before chunk q
-        run = gl::mul(run, de);
+        pre[q] = run;                 // product of the non-zero denominators before chunk q
+        // a vanishing denominator stays out of the product: that chunk alone becomes 0 (1 / 0 = 0 cell by cell, as oracle/plonk.c)
+        run = gl::mul(run, de ? de : 1);
         // keep the denominator itself in `chunk` for the backward sweep
         a.chunk[((size_t)c * a.m + q) * n + i] = de;
     }
@@ -59,8 +61,8 @@ __global__ void __launch_bounds__(256) plonk_chunk_kernel(ZsArgs a) {
     for (uint32_t q = a.m; q-- > 0;) {
         uint64_t* cell = a.chunk + ((size_t)c * a.m + q) * n + i;
         const uint64_t de = *cell;
-        const uint64_t qv = gl::mul(num[q], gl::mul(inv, pre[q]));   // num_q / den_q
-        inv = gl::mul(inv, de);
+        const uint64_t qv = de ? gl::mul(num[q], gl::mul(inv, pre[q])) : 0;   // num_q / den_q
+        inv = gl::mul(inv, de ? de : 1);
         *cell = qv;
         t = gl::mul(t, qv);
     }
