@@ -596,6 +596,18 @@ size_t sipp_circuit_proof_size(const sipp_circuit_data *cd, uint32_t n_public_in
 /* wires: HOST [num_wires][N]; the proof's public inputs are bound through public_inputs_hash (PublicInput generator / gate) */
 int sipp_circuit_prove(sipp_circuit_data *cd, const uint64_t *wires, const uint64_t *public_inputs, uint32_t n_public_inputs,
                        uint64_t *proof_out, size_t proof_cap, size_t *proof_len);
+/* the same proof from the input cells as a list (plonky2's PartialWitness is a set of (target, value)): cells[k] = wire * N + row takes
+ * values[k], every other cell starts 0; all pointers are HOST memory.  On the ctx stream: the data's wire table is zeroed, the pairs are
+ * copied into arena staging and scattered, a second pass compares every pair with what the table holds, then the call goes on as
+ * sipp_circuit_prove does after its upload; the proof is word for word that call's for the dense table with those cells set.
+ * n_inputs = 0 (cells / values may then be NULL) is allowed.  Values are stored as given (any u64, as in the dense call).  A cell
+ * >= num_wires * N: SIPP_E_BADARG, found on the host before anything is launched.  A cell listed twice with one value is accepted; with
+ * two different values: SIPP_E_BADARG, found by the second pass through a device flag read back before witness generation starts, no
+ * proof written.  After either refusal the circuit data proves as before.  SIPP_E_NOMEM, nothing launched, if the staging (16 bytes a
+ * pair) does not fit the arena. */
+int sipp_circuit_prove_inputs(sipp_circuit_data *cd, const uint64_t *cells, const uint64_t *values, size_t n_inputs,
+                              const uint64_t *public_inputs, uint32_t n_public_inputs,
+                              uint64_t *proof_out, size_t proof_cap, size_t *proof_len);
 int sipp_circuit_verify(const sipp_circuit_data *cd, const uint64_t *proof, size_t len, int *reason);
 
 /* ---- verification of the generic proofs (host code like sipp_stark_verify; stages in *reason, may be NULL) -------------------------

@@ -135,6 +135,22 @@ impl CircuitData {
         Ok(out)
     }
 
+    /// `data.prove(pw)` with pw as plonky2 holds it, a set of (target, value): cells[k] = wire * N + row takes values[k], every other
+    /// cell starts 0.  The two slices must be equally long (checked here); the library checks every cell against the table's size.
+    pub fn prove_inputs(&mut self, cells: &[u64], values: &[u64], public_inputs: &[u64]) -> Result<Vec<u64>> {
+        anyhow::ensure!(cells.len() == values.len(), "prove_inputs: {} cells but {} values", cells.len(), values.len());
+        let cap = unsafe { ffi::sipp_circuit_proof_size(self.raw, public_inputs.len() as u32) };
+        let mut out = vec![0u64; cap];
+        let mut len = 0usize;
+        let rc = unsafe {
+            ffi::sipp_circuit_prove_inputs(self.raw, cells.as_ptr(), values.as_ptr(), cells.len(), public_inputs.as_ptr(), public_inputs.len() as u32,
+                                           out.as_mut_ptr(), cap, &mut len)
+        };
+        if rc != 0 { return Err(anyhow::anyhow!("sipp_circuit_prove_inputs: status {}", rc)); }
+        out.truncate(len);
+        Ok(out)
+    }
+
     /// `data.verify(proof)`
     pub fn verify(&self, proof: &[u64]) -> Result<()> {
         let mut reason: std::os::raw::c_int = 0;

@@ -188,6 +188,7 @@ SIGNATURES = {
     "sipp_circuit_verifier_data": (C.c_int, [vp, vp, vp]),
     "sipp_circuit_proof_size": (C.c_size_t, [vp, C.c_uint32]),
     "sipp_circuit_prove": (C.c_int, [vp, vp, u64p, C.c_uint32, vp, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "sipp_circuit_prove_inputs": (C.c_int, [vp, vp, vp, C.c_size_t, u64p, C.c_uint32, vp, C.c_size_t, C.POINTER(C.c_size_t)]),
     "sipp_circuit_verify": (C.c_int, [vp, vp, C.c_size_t, C.POINTER(C.c_int)]),
     "sipp_plonk_perm_prove": (C.c_int, [vp, vp, vp, C.c_uint32, C.POINTER(PlonkParams), C.POINTER(FriParams), u64p, u64p, vp, C.c_size_t,
                                         C.POINTER(C.c_size_t)]),
@@ -801,6 +802,24 @@ class CircuitData:
         n = C.c_size_t()
         self.ctx._ck(self.L.sipp_circuit_prove(self.h, w.ctypes.data, self.ctx._u64(pis) if pis else None, len(pis), out.ctypes.data, cap, C.byref(n)),
                      "circuit_prove")
+        return out[: n.value]
+
+    def prove_inputs(self, cells, values, public_inputs):
+        """prove() from the input cells alone (sipp_circuit_prove_inputs): cells[k] = wire * N + row takes values[k], every other cell
+        starts 0; the proof is prove()'s for that table"""
+        cells = np.ascontiguousarray(cells, dtype=np.uint64).reshape(-1)
+        values = np.ascontiguousarray(values, dtype=np.uint64).reshape(-1)
+        if len(cells) != len(values):
+            raise SippError(-1, "CircuitData.prove_inputs: cells and values differ in length")
+        pis = [int(x) for x in public_inputs]
+        cap = self.L.sipp_circuit_proof_size(self.h, len(pis))
+        if cap == 0:
+            raise SippError(-1, "sipp_circuit_proof_size")
+        out = np.zeros(cap, dtype=np.uint64)
+        n = C.c_size_t()
+        self.ctx._ck(self.L.sipp_circuit_prove_inputs(self.h, cells.ctypes.data if len(cells) else None, values.ctypes.data if len(cells) else None,
+                                                      len(cells), self.ctx._u64(pis) if pis else None, len(pis), out.ctypes.data, cap, C.byref(n)),
+                     "circuit_prove_inputs")
         return out[: n.value]
 
     def verify(self, proof):

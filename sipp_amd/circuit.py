@@ -183,9 +183,15 @@ def pi(t):
     return ("pi", t)
 
 
+def _is_input(s):
+    """a public input or a witness input (CircuitBuilder.witness_input): the partial witness sets every cell tied to it"""
+    return s[0] in ("pi", "in")
+
+
 class CircuitBuilder:
     """Gates, rows and wiring of one circuit.  A cell is (wire, row) until finish() knows N, then wire * N + row.  A source of place()
-    is pi(t) or the cell of a row placed before: a row that reads a cell before a generator can have written it does not build."""
+    is pi(t), a witness input or the cell of a row placed before: a row that reads a cell before a generator can have written it does
+    not build."""
 
     def __init__(self, num_wires, num_routed, gate_names, gate_group, n_constants, n_pi):
         """gate_group: the selector group of every gate, ascending; n_constants: the constant columns behind the selector columns"""
@@ -203,6 +209,7 @@ class CircuitBuilder:
         self._rows, self._level = [], {}                        # row -> (gate, c0, c1); row -> level
         self._uf, self._copies = _Cells(), []                   # copies: (level of the source, src cell, dst cell)
         self._pi_cells = [None] * n_pi                          # one cell of public input t: every cell of its cycle takes its value
+        self._in_cells = []                                     # the same for the witness inputs
 
     # ---- gates ----
     def declare(self, index, degree, gen=None, fill=None, *args):
@@ -235,10 +242,25 @@ class CircuitBuilder:
             self._pi_cells[t] = cell
         self._uf.tie(self._pi_cells[t], cell)
 
+    def witness_input(self):
+        """the next witness input as a source of place(): a value the prover sets and only the constraints bind.  Like a public input
+        it has no level: the partial witness sets every cell tied to it"""
+        self._in_cells.append(None)
+        return ("in", len(self._in_cells) - 1)
+
+    def _input(self, s, cell):
+        if s[0] == "pi":
+            return self.public_input(s[1], cell)
+        if self._in_cells[s[1]] is None:
+            self._in_cells[s[1]] = cell
+        self._uf.tie(self._in_cells[s[1]], cell)
+
     def tie(self, a, b):
         """a copy constraint between source a and cell b without a scheduled copy: generators write both, or b is an input cell"""
-        if a[0] == "pi":
-            self.public_input(a[1], b)
+        if _is_input(a):
+            self._input(a, b)
+        elif _is_input(b):
+            self._input(b, a)
         else:
             self._uf.tie(a, b)
 
@@ -247,8 +269,8 @@ class CircuitBuilder:
         runs one level behind its latest computed source"""
         lv = 0
         for wire, s in feeds:
-            if s[0] == "pi":
-                self.public_input(s[1], (wire, row))
+            if _is_input(s):
+                self._input(s, (wire, row))
             else:
                 at = self._level[s[1]]
                 self._uf.tie(s, (wire, row))
@@ -299,6 +321,7 @@ class CircuitBuilder:
         self.cycles = [sorted(cell(c) for c in g) for g in groups.values() if len(g) > 1]
         self.pi_cells = [cell(c) for c in self._pi_cells]
         self.pi_cycle = [sorted(cell(x) for x in groups[self._uf.find(c)]) for c in self._pi_cells]
+        self.in_cycle = [sorted(cell(x) for x in groups[self._uf.find(c)]) for c in self._in_cells]
         row_level = np.full(n, -1, dtype=np.int64)
         for r, lv in self._level.items():
             row_level[r] = lv

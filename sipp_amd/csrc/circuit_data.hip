@@ -2,7 +2,7 @@
 // src/verifier_circuit.rs:225 (`builder.build::<C>()`: constants_sigmas committed once, the generators ordered once), :253 (`data.prove(pw)`)
 // and :254 (`data.verify(proof)`), for a caller that holds no device memory of its own (the Rust shim; include/sipp_host.hpp's CircuitData).
 // Nothing new is computed here: build = sipp_commit_batch_ex over the uploaded constants_sigmas; prove = upload of the wire table with its
-// input cells, sipp_plonk_generate_witness[_levels], sipp_plonk_prove_gates; verify = sipp_plonk_verify_gates with the data's own cap / digest.
+// input cells (or a scatter of the input cells alone into a zeroed table), sipp_plonk_generate_witness[_levels], sipp_plonk_prove_gates; verify = sipp_plonk_verify_gates with the data's own cap / digest.
 // Device memory of a circuit data is its own (hipMalloc at build: the arena of the ctx is the provers' scratch and empties after each proof).
 #include "ctx.hpp"
 #include "host_challenger.hpp"
@@ -157,15 +157,11 @@ extern "C" size_t sipp_circuit_proof_size(const sipp_circuit_data* cd, uint32_t 
     return cd ? sipp_plonk_gates_proof_size(cd->log_n, &cd->p, &cd->fp, &cd->circ, n_public_inputs) : 0;
 }
 
-extern "C" int sipp_circuit_prove(sipp_circuit_data* cd, const uint64_t* wires, const uint64_t* public_inputs, uint32_t n_public_inputs,
-                                  uint64_t* proof_out, size_t proof_cap, size_t* proof_len) {
-    if (!cd) return SIPP_E_BADARG;
+namespace {
+// what both prove calls do once the device wire table holds the input cells
+int prove_uploaded(sipp_circuit_data* cd, const uint64_t* public_inputs, uint32_t n_public_inputs, uint64_t* proof_out, size_t proof_cap,
+                   size_t* proof_len) {
     sipp_ctx* ctx = cd->ctx;
-    if (!wires || !proof_out || !proof_len || (n_public_inputs && !public_inputs) || n_public_inputs > (1u << 24))
-        return sipp_fail(ctx, SIPP_E_BADARG, "circuit prove: null argument");
-    SIPP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t n = (size_t)1 << cd->log_n;
-    SIPP_CHECK_HIP(ctx, hipMemcpyAsync(cd->d_wires, wires, (size_t)cd->circ.num_wires * n * 8, hipMemcpyHostToDevice, ctx->stream));
     uint64_t pih[4];
     host::Challenger::hash_no_pad(public_inputs, n_public_inputs, pih);
     if (cd->has_sched)
@@ -176,6 +172,71 @@ extern "C" int sipp_circuit_prove(sipp_circuit_data* cd, const uint64_t* wires, 
                                              cd->gens.size(), pih));
     return sipp_plonk_prove_gates(ctx, cd->d_wires, cd->d_cs, nullptr, nullptr, &cd->cs_oracle, cd->log_n, &cd->p, &cd->fp, &cd->circ, cd->digest,
                                   public_inputs, n_public_inputs, proof_out, proof_cap, proof_len);
+}
+
+// the input cells of sipp_circuit_prove_inputs: one lane per pair, grid-stride.  Pairs that name one cell race; whichever store lands,
+// the check pass below sees every pair whose value the table does not hold.
+__global__ void __launch_bounds__(256) circuit_scatter_inputs_kernel(uint64_t* wires, const uint64_t* cells, const uint64_t* values, size_t count) {
+    const size_t step = (size_t)gridDim.x * blockDim.x;
+    for (size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x; k < count; k += step) wires[cells[k]] = values[k];
+}
+__global__ void __launch_bounds__(256) circuit_check_inputs_kernel(const uint64_t* wires, const uint64_t* cells, const uint64_t* values, size_t count,
+                                                                   unsigned int* conflict) {
+    const size_t step = (size_t)gridDim.x * blockDim.x;
+    bool bad = false;
+    for (size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x; k < count; k += step) bad |= wires[cells[k]] != values[k];
+    if (bad) atomicOr(conflict, 1u);
+}
+}  // namespace
+
+extern "C" int sipp_circuit_prove(sipp_circuit_data* cd, const uint64_t* wires, const uint64_t* public_inputs, uint32_t n_public_inputs,
+                                  uint64_t* proof_out, size_t proof_cap, size_t* proof_len) {
+    if (!cd) return SIPP_E_BADARG;
+    sipp_ctx* ctx = cd->ctx;
+    if (!wires || !proof_out || !proof_len || (n_public_inputs && !public_inputs) || n_public_inputs > (1u << 24))
+        return sipp_fail(ctx, SIPP_E_BADARG, "circuit prove: null argument");
+    SIPP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t n = (size_t)1 << cd->log_n;
+    SIPP_CHECK_HIP(ctx, hipMemcpyAsync(cd->d_wires, wires, (size_t)cd->circ.num_wires * n * 8, hipMemcpyHostToDevice, ctx->stream));
+    return prove_uploaded(cd, public_inputs, n_public_inputs, proof_out, proof_cap, proof_len);
+}
+
+extern "C" int sipp_circuit_prove_inputs(sipp_circuit_data* cd, const uint64_t* cells, const uint64_t* values, size_t n_inputs,
+                                         const uint64_t* public_inputs, uint32_t n_public_inputs, uint64_t* proof_out, size_t proof_cap,
+                                         size_t* proof_len) {
+    if (!cd) return SIPP_E_BADARG;
+    sipp_ctx* ctx = cd->ctx;
+    if ((n_inputs && (!cells || !values)) || !proof_out || !proof_len || (n_public_inputs && !public_inputs) || n_public_inputs > (1u << 24))
+        return sipp_fail(ctx, SIPP_E_BADARG, "circuit prove inputs: null argument");
+    const size_t total = (size_t)cd->circ.num_wires << cd->log_n;
+    if (n_inputs > ((size_t)1 << 40)) return sipp_fail(ctx, SIPP_E_BADARG, "circuit prove inputs: too many pairs");
+    for (size_t k = 0; k < n_inputs; k++)
+        if (cells[k] >= total) return sipp_fail(ctx, SIPP_E_BADARG, "circuit prove inputs: a cell outside the wire table");
+    SIPP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    {
+        // the staging goes back before witness generation: the wait for the flag has then ended every kernel that reads it
+        ArenaScope scope(ctx);
+        uint64_t* d_pairs = arena_alloc_t<uint64_t>(ctx, 2 * n_inputs + 1);          // cells, values, the flag's word
+        if (!d_pairs) return SIPP_E_NOMEM;
+        uint64_t *d_cells = d_pairs, *d_values = d_pairs + n_inputs;
+        unsigned int* d_conflict = reinterpret_cast<unsigned int*>(d_pairs + 2 * n_inputs);
+        SIPP_CHECK_HIP(ctx, hipMemsetAsync(cd->d_wires, 0, total * 8, ctx->stream));
+        if (n_inputs) {
+            SIPP_CHECK_HIP(ctx, hipMemsetAsync(d_conflict, 0, 8, ctx->stream));
+            SIPP_CHECK_HIP(ctx, hipMemcpyAsync(d_cells, cells, n_inputs * 8, hipMemcpyHostToDevice, ctx->stream));
+            SIPP_CHECK_HIP(ctx, hipMemcpyAsync(d_values, values, n_inputs * 8, hipMemcpyHostToDevice, ctx->stream));
+            const size_t want = (n_inputs + 255) / 256;
+            const dim3 grid((unsigned)(want < 4096 ? want : 4096));
+            hipLaunchKernelGGL(circuit_scatter_inputs_kernel, grid, dim3(256), 0, ctx->stream, cd->d_wires, d_cells, d_values, n_inputs);
+            hipLaunchKernelGGL(circuit_check_inputs_kernel, grid, dim3(256), 0, ctx->stream, cd->d_wires, d_cells, d_values, n_inputs, d_conflict);
+            SIPP_CHECK_HIP(ctx, hipGetLastError());
+            unsigned int conflict = 0;
+            SIPP_CHECK_HIP(ctx, hipMemcpyAsync(&conflict, d_conflict, sizeof conflict, hipMemcpyDeviceToHost, ctx->stream));
+            SIPP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            if (conflict) return sipp_fail(ctx, SIPP_E_BADARG, "circuit prove inputs: one cell given two different values");
+        }
+    }
+    return prove_uploaded(cd, public_inputs, n_public_inputs, proof_out, proof_cap, proof_len);
 }
 
 extern "C" int sipp_circuit_verify(const sipp_circuit_data* cd, const uint64_t* proof, size_t len, int* reason) {

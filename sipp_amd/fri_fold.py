@@ -7,6 +7,9 @@ and a circuit that proves what fri_verifier_query_round does for every query aft
                             evaluation value -- every constraint expanded into base-field monomials, the domain points x_i = g^i and the
                             barycentric weights w_i = g^i / n folded into the coefficients
   arithmetic_row            an ArithmeticExt row of a circuit under construction (this circuit's and sipp_amd/fri_initial.py's)
+  index_and_x, fold_rounds_into, final_poly_into
+                            the wiring of one query on any builder, its sources given as arguments: this circuit's queries, the x
+                            of sipp_amd/fri_initial.py and the queries of sipp_amd/fri_verifier.py
   FriFoldCircuit            the statement "every query's fold chain leads from its first value to the final polynomial" as calls of
                             sipp_amd/circuit.py's CircuitBuilder, which makes the rows, the copy cycles (sigmas), the generators and
                             the level schedule of it
@@ -176,6 +179,76 @@ def arithmetic_row(b, a, m, c, c0, c1):
     return r, ((6, r), (7, r))
 
 
+def index_and_x(b, exp_gate, index, omega, zero, operands):
+    """One query's reading of its index on builder b: a BaseSum row splits the source `index` into b.log_m bits; an Exponentiation row
+    raises omega_M (the cell `omega`) to rev(index); an arithmetic op multiplies by the coset generator 7.  operands: what the op's unused
+    a and m are fed (None: free cells).  -> (the three rows, the bit cells low first, x as an extension pair of cells)"""
+    M = b.log_m
+    bs = b.new_row(BASE_SUM)
+    b.place(bs, [(0, index)])
+    bits = [(1 + i, bs) for i in range(M)]
+    # omega_M ^ rev(x_index): exponent bit j = index bit M - 1 - j
+    e0 = b.new_row(exp_gate)
+    b.place(e0, [(0, omega)] + [(1 + j, bits[M - 1 - j]) for j in range(M)])
+    # x = 7 (omega_M ^ rev, 0): the c operand
+    xr, x = arithmetic_row(b, operands, operands, ((1 + M, e0), zero), 0, COSET_GEN)
+    return bs, e0, xr, bits, x
+
+
+def fold_rounds_into(b, gates, ra_stride, zero, ginv, bits, x, old, ev, beta, within=None):
+    """The fold chain of one query on builder b (b.n_rounds rounds of arity 2^b.arity_bits).  gates = (RandomAccess with two copies of
+    2^arity_bits items at ra_stride, Exponentiation, CosetInterpolation); bits: the index bit cells, low first; x: the cell of the
+    query's point; old: the two limb sources of the value entering round 0; ev(r, j, l): the source of limb l of evaluation j of round
+    r, natural order; beta(r, l): the source of limb l of round r's challenge; within(r): the source of round r's RandomAccess index
+    (None: the two index cells stay free input cells).
+    -> ((the RandomAccess, exponentiation, shift, interpolation rows, the squaring rows per round), the last x, the last old)"""
+    ra_gate, exp_gate, interp_gate = gates
+    a, A, M, it = b.arity_bits, b.arity, b.log_m, b.interp
+    ras, exs, sfs, its, sqs = [], [], [], [], []
+    for r in range(b.n_rounds):
+        # evals[within] = old, limb by limb; the index is an input, the bit wires are the low limbs of the current index bits
+        # (generators write the claimed element and the bits on both sides: no copies)
+        ra = b.new_row(ra_gate)
+        feeds = []
+        for l in range(2):
+            at = ra_stride * l
+            b.tie(old[l], (at + 1, ra))
+            feeds += ([(at, within(r))] if within else []) + [(at + 2 + j, ev(r, j, l)) for j in range(A)]
+            for t in range(a):
+                b.tie(bits[t], (at + 2 + A + t, ra))
+        b.place(ra, feeds)
+        # (g^-1) ^ rev(within): exponent bit j = index bit a - 1 - j, the bits above are 0
+        ex = b.new_row(exp_gate)
+        b.place(ex, [(0, ginv)] + [(1 + j, bits[a - 1 - j] if j < a else zero) for j in range(M)])
+        # shift = (g^-1)^rev x
+        sf, shift = arithmetic_row(b, ((1 + M, ex), zero), (x, zero), None, 1, 0)
+        # the interpolation at beta_r of the evals in bit-reversed order
+        ir = b.new_row(interp_gate)
+        feeds = [(it["shift"], shift[0])] + [(it["point"] + l, beta(r, l)) for l in range(2)]
+        feeds += [(it["values"] + 2 * k + l, ev(r, reverse_bits(k, a), l)) for k in range(A) for l in range(2)]
+        b.place(ir, feeds)
+        old = [(it["eval"], ir), (it["eval"] + 1, ir)]
+        # x <- x^arity
+        sq = []
+        for _ in range(a):
+            row, (x, _) = arithmetic_row(b, (x, zero), (x, zero), None, 1, 0)
+            sq.append(row)
+        bits = bits[a:]
+        ras.append(ra); exs.append(ex); sfs.append(sf); its.append(ir); sqs.append(sq)
+    return (ras, exs, sfs, its, sqs), x, old
+
+
+def final_poly_into(b, zero, x, coeff):
+    """the final polynomial (b.final_len coefficients, coeff(k, l) = the source of limb l of coefficient k) at (x, 0) by Horner:
+    acc = c_(F-1); acc <- acc (x, 0) + c_k  -> (the rows, the result's two limb sources)"""
+    F = b.final_len
+    acc, rows = [coeff(F - 1, l) for l in range(2)], []
+    for k in range(F - 2, -1, -1):
+        row, acc = arithmetic_row(b, acc, (x, zero), [coeff(k, l) for l in range(2)], 1, 1)
+        rows.append(row)
+    return rows, acc
+
+
 class FriFoldCircuit(CircuitBuilder):
     """The circuit of the fold chains of n_queries queries of a FRI opening proof over an LDE of 2^log_m points: n_rounds rounds of arity
     2^arity_bits, a final polynomial of final_len ext coefficients.  Cells are wire * N + row."""
@@ -221,7 +294,6 @@ class FriFoldCircuit(CircuitBuilder):
         return self.pi_query(q) + 3 + 2 * (self.arity * r + j) + l
 
     def _wiring(self):
-        a, A, M, it = self.arity_bits, self.arity, self.log_m, self.interp
         self.pi_row = self.new_row(PUBLIC_INPUT)
         self.place(self.pi_row)
         self.zero_row, zero = self.constant(0)
@@ -229,56 +301,17 @@ class FriFoldCircuit(CircuitBuilder):
         self.ginv_row, ginv = self.constant(self.g_inv)
         self.bs_row, self.exp0_row, self.x_row, self.ra_row, self.exp_row, self.shift_row, self.interp_row, self.sq_row, self.horner_row = (
             [], [], [], [], [], [], [], [], [])
+        gates = (RANDOM_ACCESS, EXPONENTIATION, COSET_INTERPOLATION)
         for q in range(self.n_queries):
             base = self.pi_query(q)
-            bs = self.new_row(BASE_SUM)
-            self.place(bs, [(0, pi(base))])
-            bits = [(1 + i, bs) for i in range(M)]                          # the current index bits, low first
-            # omega_M ^ rev(x_index): exponent bit j = index bit M - 1 - j
-            e0 = self.new_row(EXPONENTIATION)
-            self.place(e0, [(0, omega)] + [(1 + j, bits[M - 1 - j]) for j in range(M)])
-            # x = 7 (omega_M ^ rev, 0): the c operand
-            xr, (x, _) = arithmetic_row(self, None, None, ((1 + M, e0), zero), 0, COSET_GEN)
+            bs, e0, xr, bits, (x, _) = index_and_x(self, EXPONENTIATION, pi(base), omega, zero, None)
             self.bs_row.append(bs); self.exp0_row.append(e0); self.x_row.append(xr)
-            old = [pi(base + 1), pi(base + 2)]                              # the first old = the claimed element of round 0
-            ras, exs, sfs, its, sqs = [], [], [], [], []
-            for r in range(self.n_rounds):
-                # evals[within] = old, limb by limb; the index is an input, the bit wires are the low limbs of the current index bits
-                # (generators write the claimed element and the bits on both sides: no copies)
-                ra = self.new_row(RANDOM_ACCESS)
-                feeds = []
-                for l in range(2):
-                    b = self.ra_stride * l
-                    self.tie(old[l], (b + 1, ra))
-                    feeds += [(b + 2 + j, pi(self.pi_eval(q, r, j, l))) for j in range(A)]
-                    for t in range(a):
-                        self.tie(bits[t], (b + 2 + A + t, ra))
-                self.place(ra, feeds)
-                # (g^-1) ^ rev(within): exponent bit j = index bit a - 1 - j, the bits above are 0
-                ex = self.new_row(EXPONENTIATION)
-                self.place(ex, [(0, ginv)] + [(1 + j, bits[a - 1 - j] if j < a else zero) for j in range(M)])
-                # shift = (g^-1)^rev x
-                sf, shift = arithmetic_row(self, ((1 + M, ex), zero), (x, zero), None, 1, 0)
-                # the interpolation at beta_r of the evals in bit-reversed order
-                ir = self.new_row(COSET_INTERPOLATION)
-                feeds = [(it["shift"], shift[0])] + [(it["point"] + l, pi(self.pi_beta(r, l))) for l in range(2)]
-                feeds += [(it["values"] + 2 * k + l, pi(self.pi_eval(q, r, reverse_bits(k, a), l))) for k in range(A) for l in range(2)]
-                self.place(ir, feeds)
-                old = [(it["eval"], ir), (it["eval"] + 1, ir)]
-                # x <- x^arity
-                sq = []
-                for _ in range(a):
-                    row, (x, _) = arithmetic_row(self, (x, zero), (x, zero), None, 1, 0)
-                    sq.append(row)
-                bits = bits[a:]
-                ras.append(ra); exs.append(ex); sfs.append(sf); its.append(ir); sqs.append(sq)
-            self.ra_row.append(ras); self.exp_row.append(exs); self.shift_row.append(sfs); self.interp_row.append(its); self.sq_row.append(sqs)
-            # the final polynomial at (x, 0) by Horner: acc = c_(F-1); acc <- acc (x, 0) + c_k; the result is the last old
-            F = self.final_len
-            acc, rows = [pi(self.pi_final(F - 1, l)) for l in range(2)], []
-            for k in range(F - 2, -1, -1):
-                row, acc = arithmetic_row(self, acc, (x, zero), [pi(self.pi_final(k, l)) for l in range(2)], 1, 1)
-                rows.append(row)
+            # the first old = the claimed element of round 0
+            rows, x, old = fold_rounds_into(self, gates, self.ra_stride, zero, ginv, bits, x, [pi(base + 1), pi(base + 2)],
+                                            lambda r, j, l: pi(self.pi_eval(q, r, j, l)), lambda r, l: pi(self.pi_beta(r, l)))
+            for have, got in zip((self.ra_row, self.exp_row, self.shift_row, self.interp_row, self.sq_row), rows):
+                have.append(got)
+            rows, acc = final_poly_into(self, zero, x, lambda k, l: pi(self.pi_final(k, l)))
             self.horner_row.append(rows)
             for l in range(2):
                 self.tie(acc[l], old[l])

@@ -5,6 +5,9 @@ does for every query (fri/recursive_verifier.rs, recalled): the step between the
 
   reducing_gate          2 K constraints:  acc_i - (acc_(i-1) alpha + c_i)  over F[X]/(X^2 - W), limb by limb; base-field coefficients
   reducing_ext_gate      the same with extension coefficients
+  reduce_chain, openings_into, combine_into
+                         the wiring of the combination on any builder, its sources given as arguments: this circuit's and that of
+                         sipp_amd/fri_verifier.py
   FriInitialCircuit      the statement "every query's leaf values and the claimed openings combine into the value that enters its first
                          fold" as calls of sipp_amd/circuit.py's CircuitBuilder, which makes the rows, the copy cycles (sigmas), the
                          generators and the level schedule of it
@@ -25,13 +28,13 @@ denominator (x, 0) - point; the quotient row; total <- total alpha^len + quotien
 Chunking.  A chain takes its coefficients highest index first (the result is sum_j alpha^j v_j), K to a row; the FIRST row carries the
 len mod K remainder behind leading zero coefficients, whose cells are tied to the zero cell: the accumulator stays 0 through them.
 
-Out of scope: joining this circuit with the Merkle and fold circuits into one query round; the proof of work; empty batches; salt
+Out of scope: the Merkle paths and the fold chains (sipp_amd/fri_verifier.py joins the three into one query round); the proof of work; empty batches; salt
 columns (they are not opened); blinding.
 
 numpy only; imports nothing from the test oracle."""
-from .circuit import (BASE_SUM, GEN_EXPONENTIATION, GEN_QUOTIENT_EXT, GEN_REDUCING, GEN_REDUCING_EXT, P, PUBLIC_INPUT, CircuitBuilder,
+from .circuit import (GEN_EXPONENTIATION, GEN_QUOTIENT_EXT, GEN_REDUCING, GEN_REDUCING_EXT, P, PUBLIC_INPUT, CircuitBuilder,
                       CircuitProver, _W, _root_of_unity, _words, pi)
-from .fri_fold import ARITHMETIC_EXT, COSET_GEN, EXT_W, arithmetic_row, declare_arithmetic_ext, exponentiation_into
+from .fri_fold import ARITHMETIC_EXT, EXT_W, arithmetic_row, declare_arithmetic_ext, exponentiation_into, index_and_x
 from .merkle import declare_swap_gate
 
 GATE_NAMES = ["Noop", "PublicInput", "Constant", "BaseSum", "ArithmeticExt", "Reducing", "ReducingExt", "QuotientExt", "Exponentiation",
@@ -71,6 +74,75 @@ def reducing_ext_gate(K, W=EXT_W):
     pr, words = _words(_reducing_into, K, W, True)
     assert pr.count == 2 * K
     return words
+
+
+def reduce_chain(b, gate, ext, alpha, zero, coeffs):
+    """sum_j alpha^j coeffs[j] on builder b by rows of K coefficients (b.k_ext / b.k_base), highest index first
+    -> (the rows, the last accumulator)"""
+    K = b.k_ext if ext else b.k_base
+    lay = reducing_layout(K, ext)
+    seq = [None] * (-len(coeffs) % K) + list(reversed(coeffs))
+    acc, used = (zero, zero), []
+    for at in range(0, len(seq), K):
+        r = b.new_row(gate)
+        feeds = [(0, alpha[0]), (1, alpha[1]), (2, acc[0]), (3, acc[1])]
+        for j, v in enumerate(seq[at:at + K]):
+            if ext:
+                v = (zero, zero) if v is None else v
+                feeds += [(lay["coeffs"] + 2 * j, v[0]), (lay["coeffs"] + 2 * j + 1, v[1])]
+            else:
+                feeds.append((lay["coeffs"] + j, zero if v is None else v))
+        b.place(r, feeds)
+        acc = ((lay["last"], r), (lay["last"] + 1, r))
+        used.append(r)
+    return used, acc
+
+
+def openings_into(b, reducing_ext_gate, alpha, zero, opened):
+    """once per proof and batch of b.batches: the reduced openings sum_j alpha^j opened_j (opened(batch, j, l) = the source of limb l) and
+    alpha^len by square and multiply -> (the ReducingExt rows, the power rows, the reduced openings, alpha^len), each per batch"""
+    ZERO = (zero, zero)
+    opened_row, power_row, acc_o, alpha_len = [], [], [], []
+    for bi, cols in enumerate(b.batches):
+        used, acc = reduce_chain(b, reducing_ext_gate, True, alpha, zero, [(opened(bi, j, 0), opened(bi, j, 1)) for j in range(len(cols))])
+        opened_row.append(used)
+        acc_o.append(acc)
+        pw, used = alpha, []
+        for bit in bin(len(cols))[3:]:                                       # below the top bit: square, multiply on a 1
+            r, pw = arithmetic_row(b, pw, pw, ZERO, 1, 0)
+            used.append(r)
+            if bit == "1":
+                r, pw = arithmetic_row(b, pw, alpha, ZERO, 1, 0)
+                used.append(r)
+        power_row.append(used)
+        alpha_len.append(pw)
+    return opened_row, power_row, acc_o, alpha_len
+
+
+def combine_into(b, gates, alpha, zero, one, x, acc_o, alpha_len, leaf, point):
+    """fri_combine_initial of one query on builder b, times x.  gates = (Reducing, QuotientExt); x: the query's point as an extension
+    pair of cells; acc_o, alpha_len: openings_into's; leaf(c) = the source of column c of the query's row of leaf values;
+    point(batch, l) = the source of limb l of the batch's point.
+    -> ((the Reducing, numerator, denominator, quotient and total rows per batch, the row of old), old as two cells)"""
+    reducing_gate_, quotient_gate = gates
+    ZERO, ONE = (zero, zero), (one, zero)
+    total = ZERO
+    lf, nm, dn, qt, tt = [], [], [], [], []
+    for bi, cols in enumerate(b.batches):
+        used, acc_x = reduce_chain(b, reducing_gate_, False, alpha, zero, [leaf(c) for c in cols])
+        lf.append(used)
+        r, num = arithmetic_row(b, acc_x, ONE, acc_o[bi], 1, -1)                 # acc_x - acc_o
+        nm.append(r)
+        r, den = arithmetic_row(b, x, ONE, (point(bi, 0), point(bi, 1)), 1, -1)  # (x, 0) - point
+        dn.append(r)
+        # the quotient: out = a m, the generator fills m = out inv(a)
+        r = b.new_row(quotient_gate, 1, 0)
+        b.place(r, [(0, den[0]), (1, den[1]), (4, zero), (5, zero), (6, num[0]), (7, num[1])])
+        qt.append(r)
+        r, total = arithmetic_row(b, total, alpha_len[bi], ((2, r), (3, r)), 1, 1)
+        tt.append(r)
+    r, old = arithmetic_row(b, total, x, ZERO, 1, 0)
+    return (lf, nm, dn, qt, tt, r), old
 
 
 class FriInitialCircuit(CircuitBuilder):
@@ -124,78 +196,22 @@ class FriInitialCircuit(CircuitBuilder):
         return self.pi_query(q) + 1 + self.n_columns + l
 
     def _build(self):
-        arith = lambda *args: arithmetic_row(self, *args)       # c0 a m + c1 c
         self.pi_row = self.new_row(PUBLIC_INPUT)
         self.place(self.pi_row)
         self.zero_row, zero = self.constant(0)
         self.one_row, one = self.constant(1)
         self.omega_row, omega = self.constant(self.omega_m)
-        ZERO, ONE, alpha = (zero, zero), (one, zero), (pi(0), pi(1))
-
-        def chain(ext, coeffs):
-            """sum_j alpha^j coeffs[j] by rows of K coefficients, highest index first; -> (the rows, the last accumulator)"""
-            K, gate = (self.k_ext, REDUCING_EXT) if ext else (self.k_base, REDUCING)
-            lay = reducing_layout(K, ext)
-            seq = [None] * (-len(coeffs) % K) + list(reversed(coeffs))
-            acc, used = ZERO, []
-            for at in range(0, len(seq), K):
-                r = self.new_row(gate)
-                feeds = [(0, alpha[0]), (1, alpha[1]), (2, acc[0]), (3, acc[1])]
-                for j, v in enumerate(seq[at:at + K]):
-                    if ext:
-                        v = ZERO if v is None else v
-                        feeds += [(lay["coeffs"] + 2 * j, v[0]), (lay["coeffs"] + 2 * j + 1, v[1])]
-                    else:
-                        feeds.append((lay["coeffs"] + j, zero if v is None else v))
-                self.place(r, feeds)
-                acc = ((lay["last"], r), (lay["last"] + 1, r))
-                used.append(r)
-            return used, acc
-
+        ZERO, alpha = (zero, zero), (pi(0), pi(1))
         # once per proof and batch: the reduced openings, alpha^len
-        self.opened_row, self.power_row, acc_o, alpha_len = [], [], [], []
-        for b, cols in enumerate(self.batches):
-            used, acc = chain(True, [(pi(self.pi_opened(b, j, 0)), pi(self.pi_opened(b, j, 1))) for j in range(len(cols))])
-            self.opened_row.append(used)
-            acc_o.append(acc)
-            pw, used = alpha, []
-            for bit in bin(len(cols))[3:]:                                       # below the top bit: square, multiply on a 1
-                r, pw = arith(pw, pw, ZERO, 1, 0)
-                used.append(r)
-                if bit == "1":
-                    r, pw = arith(pw, alpha, ZERO, 1, 0)
-                    used.append(r)
-            self.power_row.append(used)
-            alpha_len.append(pw)
+        self.opened_row, self.power_row, acc_o, alpha_len = openings_into(self, REDUCING_EXT, alpha, zero, lambda b, j, l: pi(self.pi_opened(b, j, l)))
         # per query
-        M = self.log_m
         self.bs_row, self.exp0_row, self.x_row, self.leaf_row, self.num_row, self.den_row, self.quot_row, self.total_row, self.old_row = (
             [], [], [], [], [], [], [], [], [])
         for q in range(self.n_queries):
-            bs = self.new_row(BASE_SUM)
-            self.place(bs, [(0, pi(self.pi_query(q)))])
-            # omega_M ^ rev(x_index): exponent bit j = index bit M - 1 - j
-            e0 = self.new_row(EXPONENTIATION)
-            self.place(e0, [(0, omega)] + [(1 + j, (1 + (M - 1 - j), bs)) for j in range(M)])
-            # x = 7 (omega_M ^ rev, 0): the c operand
-            xr, x = arith(ZERO, ZERO, ((1 + M, e0), zero), 0, COSET_GEN)
+            bs, e0, xr, _, x = index_and_x(self, EXPONENTIATION, pi(self.pi_query(q)), omega, zero, ZERO)
             self.bs_row.append(bs); self.exp0_row.append(e0); self.x_row.append(xr)
-            total = ZERO
-            lf, nm, dn, qt, tt = [], [], [], [], []
-            for b, cols in enumerate(self.batches):
-                used, acc_x = chain(False, [pi(self.pi_leaf(q, c)) for c in cols])
-                lf.append(used)
-                r, num = arith(acc_x, ONE, acc_o[b], 1, -1)                      # acc_x - acc_o
-                nm.append(r)
-                r, den = arith(x, ONE, (pi(self.pi_point(b, 0)), pi(self.pi_point(b, 1))), 1, -1)      # (x, 0) - point
-                dn.append(r)
-                # the quotient: out = a m, the generator fills m = out inv(a)
-                r = self.new_row(QUOTIENT_EXT, 1, 0)
-                self.place(r, [(0, den[0]), (1, den[1]), (4, zero), (5, zero), (6, num[0]), (7, num[1])])
-                qt.append(r)
-                r, total = arith(total, alpha_len[b], ((2, r), (3, r)), 1, 1)
-                tt.append(r)
-            r, old = arith(total, x, ZERO, 1, 0)
+            (lf, nm, dn, qt, tt, r), old = combine_into(self, (REDUCING, QUOTIENT_EXT), alpha, zero, one, x, acc_o, alpha_len,
+                                                        lambda c: pi(self.pi_leaf(q, c)), lambda b, l: pi(self.pi_point(b, l)))
             for l in range(2):
                 self.tie(pi(self.pi_old(q, l)), old[l])
             self.leaf_row.append(lf); self.num_row.append(nm); self.den_row.append(dn); self.quot_row.append(qt); self.total_row.append(tt)

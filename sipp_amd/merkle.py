@@ -4,6 +4,8 @@ a commitment against its cap (what the recursive verifier does for every FRI que
   poseidon_swap_gate()      the 123 constraints of upstream's PoseidonGate (gates/poseidon.rs, recalled) in the program words of
                             sipp_plonk_circuit (include/sipp_hip.h, "gates as data"), upstream's order and sign
   declare_swap_gate()       that gate in a circuit's gate set, in SWAP_LAYOUT (every circuit hashes its public inputs with it)
+  opening_into()            the wiring of one opening on any builder, its leaf, index bits and cap given as sources: this circuit's
+                            paths and those of sipp_amd/fri_verifier.py
   MerkleOpeningCircuit      the statement "for each path k, leaves[k] sits at index idx[k] of the tree whose cap is `cap`" as calls of
                             sipp_amd/circuit.py's CircuitBuilder, which makes the rows, the copy cycles (sigmas), the generators and
                             the level schedule of it
@@ -130,6 +132,40 @@ def declare_swap_gate(b, index):
               b.s_delta, b.s_sbox)
 
 
+def opening_into(b, ra_shape, swap_gate, zero, leaf, swap_bits, index, cap_word, cap_bits=None, sibling=None):
+    """One Merkle opening on builder b: the leaf (sources) sits under the cap at the index whose low bits are the cells swap_bits, one per
+    level of the path (none: the tree is its cap), and whose high part is the source `index`.  ra_shape = (gate, rows, copies per row,
+    stride, cap entries) of the cap selection; cap_word(j, q) = the source of word q of cap entry j.  cap_bits: the cells the selection's
+    bit wires are tied to (the high bits of a split the caller made; None: the generator's bits stand alone, `index` is bound elsewhere).
+    sibling(l, t): the source of word t of the sibling at level l (None: the cells stay free input cells).
+    -> (the RandomAccess rows, the leaf-hash rows, the path rows)"""
+    s_in, s_out = b.s_in, b.s_out
+    ra_gate, ra_rows, ra_copies, ra_stride, n_cap = ra_shape
+    ra = [b.new_row(ra_gate) for _ in range(ra_rows)]
+    # the leaf hash (hash_or_noop): at most 4 values are their own digest, padded with zero
+    rows = b.hash_rows(swap_gate, zero, leaf) if len(leaf) > 4 else []
+    digest = [(s_out + t, rows[-1]) if rows else leaf[t] if t < len(leaf) else zero for t in range(4)]
+    # the path: digest in 0 .. 3, the sibling (an input) in 4 .. 7, capacity 0, swap = bit l of the low index
+    path = []
+    for l, bit in enumerate(swap_bits):
+        r = b.new_row(swap_gate)
+        sib = [(s_in + 4 + t, sibling(l, t)) for t in range(4)] if sibling else []
+        b.place(r, [(s_in + t, digest[t]) for t in range(4)] + sib + [(s_in + t, zero) for t in range(8, 12)] + [(b.s_swap, bit)])
+        digest = [(s_out + t, r) for t in range(4)]
+        path.append(r)
+    # cap selection: copy q selects digest word q of the cap entry; the root word is the claimed word (both generated: no copy)
+    for i, r in enumerate(ra):
+        feeds = []
+        for cp in range(ra_copies):
+            at, q = ra_stride * cp, ra_copies * i + cp
+            feeds += [(at, index)] + [(at + 2 + j, cap_word(j, q)) for j in range(n_cap)]
+            b.tie(digest[q], (at + 1, r))
+            for l, bit in enumerate(cap_bits or ()):
+                b.tie(bit, (at + 2 + n_cap + l, r))
+        b.place(r, feeds)
+    return ra, rows, path
+
+
 class MerkleOpeningCircuit(CircuitBuilder):
     """The circuit of n_paths openings of leaves of leaf_len values, paths of `height` siblings, under a cap of 2^cap_height digests.
     Cells are wire * N + row; every cell that copy constraints tie together lies on one permutation cycle."""
@@ -157,36 +193,19 @@ class MerkleOpeningCircuit(CircuitBuilder):
         self.sibling_cells = [[[(self.s_in + 4 + t) * self.n + r for t in range(4)] for r in rows] for rows in self.path_row]
 
     def _wiring(self):
-        s_in, s_out = self.s_in, self.s_out
         self.pi_row = self.new_row(PUBLIC_INPUT)
         self.place(self.pi_row)
         self.const_row, zero = self.constant(0)
         self.bs_row, self.ra_row, self.leaf_row, self.path_row = [], [], [], []
+        ra_shape = (RANDOM_ACCESS, self.ra_rows, self.ra_copies, self.ra_stride, self.n_cap)
         for k in range(self.n_paths):
             hi_t = 4 * self.n_cap + k * (2 + self.leaf_len)
             lo_t, leaf_t = hi_t + 1, hi_t + 2
             # the index bits
             bs = self.new_row(BASE_SUM)
             self.place(bs, [(0, pi(lo_t))])
-            ra = [self.new_row(RANDOM_ACCESS) for _ in range(self.ra_rows)]
-            # the leaf hash (hash_or_noop)
-            leaf = self.hash_rows(POSEIDON_SWAP, zero, [pi(leaf_t + t) for t in range(self.leaf_len)]) if self.n_leaf_rows else []
-            digest = [(s_out + t, leaf[-1]) if leaf else pi(leaf_t + t) if t < self.leaf_len else zero for t in range(4)]
-            # the path: digest in 0 .. 3, the sibling (an input) in 4 .. 7, capacity 0, swap = bit l of the low index
-            path = []
-            for l in range(self.height):
-                r = self.new_row(POSEIDON_SWAP)
-                self.place(r, [(s_in + t, digest[t]) for t in range(4)] + [(s_in + t, zero) for t in range(8, 12)] + [(self.s_swap, (1 + l, bs))])
-                digest = [(s_out + t, r) for t in range(4)]
-                path.append(r)
-            # cap selection: copy q selects digest word q of cap[idx >> height]; the root word is the claimed word (both generated: no copy)
-            for i, r in enumerate(ra):
-                feeds = []
-                for cp in range(self.ra_copies):
-                    b, q = self.ra_stride * cp, self.ra_copies * i + cp
-                    feeds += [(b, pi(hi_t))] + [(b + 2 + j, pi(4 * j + q)) for j in range(self.n_cap)]
-                    self.tie(digest[q], (b + 1, r))
-                self.place(r, feeds)
+            ra, leaf, path = opening_into(self, ra_shape, POSEIDON_SWAP, zero, [pi(leaf_t + t) for t in range(self.leaf_len)],
+                                          [(1 + l, bs) for l in range(self.height)], pi(hi_t), lambda j, q: pi(4 * j + q))
             self.bs_row.append(bs); self.ra_row.append(ra); self.leaf_row.append(leaf); self.path_row.append(path)
         self.hash_public_inputs(POSEIDON_SWAP, zero)
 
