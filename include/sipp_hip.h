@@ -518,7 +518,12 @@ int sipp_plonk_prove_gates(sipp_ctx *ctx, const uint64_t *d_wires, const uint64_
  *                                                                       with inv(0) = 0: a = 0, c0 = 0, or an a of zero norm under a residue W
  *                                                                       all write (0, 0).  The constraints, not the generator, refuse such
  *                                                                       rows (they hold only if out = c1 c)               (QuotientGeneratorExtension)
- * The five families above take ANY field value in every input cell; W != 0.
+ *   SIPP_GEN_BASE_SUM       p = n_limbs, bits per limb                  SIPP_GEN_BASE_SPLIT's row read the other way (le_sum): w[0] = sum_l w[1+l]
+ *                                                                       2^(bits l) in the field.  The limbs are taken as field values, whatever
+ *                                                                       they hold (the constraints, not the generator, range-check them); the
+ *                                                                       same limits as kind 2: 1 + n_limbs <= num_wires, bits 1 .. 32,
+ *                                                                       n_limbs bits <= 64                                  (BaseSumGenerator)
+ * The five families from SIPP_GEN_ARITHMETIC_EXT to SIPP_GEN_QUOTIENT_EXT take ANY field value in every input cell; W != 0.
  * Defined behaviour outside a gate's range (the constraints, not the generators, refuse such rows): BASE_SPLIT drops the bits of w[0] at
  * and above n_limbs * bits; U32_MUL_ADD takes the low 32 bits of an operand that is not a u32, and with a stride wider than 5 + 2 limbs
  * the cells behind an op's limbs stay untouched; RANDOM_ACCESS with an index >= 2^bits selects by the low `bits` bits of the index.
@@ -539,6 +544,7 @@ int sipp_plonk_prove_gates(sipp_ctx *ctx, const uint64_t *d_wires, const uint64_
 #define SIPP_GEN_COSET_INTERPOLATION 12
 #define SIPP_GEN_REDUCING_EXT 13
 #define SIPP_GEN_QUOTIENT_EXT 14
+#define SIPP_GEN_BASE_SUM 15
 typedef struct {
     uint32_t kind, selector_index, row;
     uint32_t p[5];

@@ -131,6 +131,7 @@ pub const SIPP_GEN_COSET_INTERPOLATION: u32 = 12;
 /// SIPP_GEN_*: FRI's initial combination: the reduction of extension coefficients and the quotient generator of an ArithmeticExt row
 pub const SIPP_GEN_REDUCING_EXT: u32 = 13;
 pub const SIPP_GEN_QUOTIENT_EXT: u32 = 14;
+pub const SIPP_GEN_BASE_SUM: u32 = 15;
 
 /// one gate family's witness generator with its layout (include/sipp_hip.h, "WITNESS GENERATORS"): kind = SIPP_GEN_*
 #[repr(C)]

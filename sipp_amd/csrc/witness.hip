@@ -268,6 +268,14 @@ __device__ __forceinline__ void run_generator(uint64_t* wires, const uint64_t* c
         }
         break;
     }
+    case SIPP_GEN_BASE_SUM: {
+        // Horner from the top limb: the limbs are field values, whatever they hold (mad takes any 64-bit word)
+        const uint64_t base = 1ull << g.p[1];
+        uint64_t acc = 0;
+        for (uint32_t l = g.p[0]; l-- > 0;) acc = gl::mad(acc, base, W(1 + l));
+        W(0) = acc;
+        break;
+    }
     default: break;
     }
 }
@@ -543,7 +551,8 @@ bool layout_ok(const sipp_plonk_generator& g, uint32_t num_wires, uint32_t num_c
     const uint64_t nw = num_wires;
     switch (g.kind) {
     case SIPP_GEN_ARITHMETIC: return 4ull * g.p[0] <= nw && g.p[1] < num_constants && g.p[2] < num_constants;
-    case SIPP_GEN_BASE_SPLIT: return 1ull + g.p[0] <= nw && g.p[1] >= 1 && g.p[1] <= 32 && (uint64_t)g.p[0] * g.p[1] <= 64;
+    case SIPP_GEN_BASE_SPLIT:
+    case SIPP_GEN_BASE_SUM: return 1ull + g.p[0] <= nw && g.p[1] >= 1 && g.p[1] <= 32 && (uint64_t)g.p[0] * g.p[1] <= 64;
     case SIPP_GEN_CONSTANT: return g.p[0] <= nw && (uint64_t)g.p[1] + g.p[0] <= num_constants;
     case SIPP_GEN_PUBLIC_INPUT: return 4 <= nw;
     case SIPP_GEN_U32_MUL_ADD: return g.p[2] <= 16 && g.p[1] >= 5 + 2 * g.p[2] && (uint64_t)g.p[0] * g.p[1] <= nw;
@@ -577,8 +586,8 @@ const char* gen_name(uint32_t kind) {
     static const char* names[] = {"", "witness_arithmetic", "witness_base_split", "witness_constant", "witness_public_input", "witness_u32",
                                   "witness_random_access", "witness_reducing", "witness_poseidon", "witness_poseidon_swap",
                                   "witness_arithmetic_ext", "witness_exponentiation", "witness_coset_interpolation",
-                                  "witness_reducing_ext", "witness_quotient_ext"};
-    return kind <= SIPP_GEN_QUOTIENT_EXT ? names[kind] : "witness";
+                                  "witness_reducing_ext", "witness_quotient_ext", "witness_base_sum"};
+    return kind <= SIPP_GEN_BASE_SUM ? names[kind] : "witness";
 }
 
 }  // namespace

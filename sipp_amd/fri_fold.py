@@ -7,7 +7,7 @@ and a circuit that proves what fri_verifier_query_round does for every query aft
                             evaluation value -- every constraint expanded into base-field monomials, the domain points x_i = g^i and the
                             barycentric weights w_i = g^i / n folded into the coefficients
   arithmetic_row            an ArithmeticExt row of a circuit under construction (this circuit's and sipp_amd/fri_initial.py's)
-  index_and_x, fold_rounds_into, final_poly_into
+  index_and_x, x_from_bits, fold_rounds_into, final_poly_into
                             the wiring of one query on any builder, its sources given as arguments: this circuit's queries, the x
                             of sipp_amd/fri_initial.py and the queries of sipp_amd/fri_verifier.py
   FriFoldCircuit            the statement "every query's fold chain leads from its first value to the final polynomial" as calls of
@@ -183,16 +183,23 @@ def index_and_x(b, exp_gate, index, omega, zero, operands):
     """One query's reading of its index on builder b: a BaseSum row splits the source `index` into b.log_m bits; an Exponentiation row
     raises omega_M (the cell `omega`) to rev(index); an arithmetic op multiplies by the coset generator 7.  operands: what the op's unused
     a and m are fed (None: free cells).  -> (the three rows, the bit cells low first, x as an extension pair of cells)"""
-    M = b.log_m
     bs = b.new_row(BASE_SUM)
     b.place(bs, [(0, index)])
-    bits = [(1 + i, bs) for i in range(M)]
+    bits = [(1 + i, bs) for i in range(b.log_m)]
+    e0, xr, x = x_from_bits(b, exp_gate, bits, omega, zero, operands)
+    return bs, e0, xr, bits, x
+
+
+def x_from_bits(b, exp_gate, bits, omega, zero, operands):
+    """index_and_x behind the split: the b.log_m bit cells (low first) are the caller's, whatever row split them
+    -> (the Exponentiation row, the arithmetic row, x as an extension pair of cells)"""
+    M = b.log_m
     # omega_M ^ rev(x_index): exponent bit j = index bit M - 1 - j
     e0 = b.new_row(exp_gate)
     b.place(e0, [(0, omega)] + [(1 + j, bits[M - 1 - j]) for j in range(M)])
     # x = 7 (omega_M ^ rev, 0): the c operand
     xr, x = arithmetic_row(b, operands, operands, ((1 + M, e0), zero), 0, COSET_GEN)
-    return bs, e0, xr, bits, x
+    return e0, xr, x
 
 
 def fold_rounds_into(b, gates, ra_stride, zero, ginv, bits, x, old, ev, beta, within=None):

@@ -3,8 +3,10 @@ the fold chain (sipp_amd/fri_fold.py) wired on ONE builder, each handing the nex
 challenges are drawn (fri/recursive_verifier.rs, recalled), for an opening proof of sipp_fri_prove_openings.
 
   FriQueryRoundCircuit   the statement "every query round of this opening proof verifies against these caps" as calls of the three
-                         modules' wiring routines (opening_into; openings_into, combine_into; index_and_x, fold_rounds_into,
+                         modules' wiring routines (opening_into; openings_into, combine_into; x_from_bits, fold_rounds_into,
                          final_poly_into) on sipp_amd/circuit.py's CircuitBuilder
+  query_rounds_into      that wiring with what the challenges decide given as sources (alpha, beta_r, the index bits, the cap index,
+                         within(r)): this class's public and witness inputs, or the cells sipp_amd/fri_proof.py draws in circuit
   proof_arguments        the proof's data as a caller has it -> the argument tuple of public_inputs / partial_witness / input_cells / prove
   FriVerifierProver      the circuit through the library's CircuitData: built once, then prove(arguments) / verify; the proof is made
                          from the input cells alone (sipp_circuit_prove_inputs), not from a dense table
@@ -31,16 +33,17 @@ proof's order, the interpolation row in bit-reversed order, the RandomAccess ite
 Edges.  A leaf of at most 4 values is its own digest, padded with zero: no hash rows (narrow oracles; coset leaves at arity_bits = 1).
 A commit-phase tree with exactly 2^cap_height leaves has no swap row: its leaf digest is the cap selection's claimed words.
 
-Out of scope, refused at build: the proof of work (pow_bits != 0); drawing the challenges in circuit, i.e. the challenger
-(draw_challenges); mixed arities (arity_bits given per round with different values); salted (hiding) oracles (n_salt); empty batches.
+Refused at build: mixed arities (arity_bits given per round with different values); salted (hiding) oracles (n_salt); empty batches;
+and in THIS class the proof of work (pow_bits != 0) and drawing the challenges in circuit (draw_challenges), which
+sipp_amd/fri_proof.py's FriProofCircuit does around the same wiring (query_rounds_into).
 
 numpy only; imports nothing from the test oracle."""
 import numpy as np
 
-from .circuit import (GEN_EXPONENTIATION, GEN_QUOTIENT_EXT, GEN_RANDOM_ACCESS, GEN_REDUCING, GEN_REDUCING_EXT, GEN_COSET_INTERPOLATION, P,
+from .circuit import (BASE_SUM, GEN_EXPONENTIATION, GEN_QUOTIENT_EXT, GEN_RANDOM_ACCESS, GEN_REDUCING, GEN_REDUCING_EXT, GEN_COSET_INTERPOLATION, P,
                       PUBLIC_INPUT, CircuitBuilder, CircuitProver, _root_of_unity, pi, random_access_into)
 from .fri_fold import (ARITHMETIC_EXT, EXT_W, INTERP_DEGREE, coset_interpolation_into, declare_arithmetic_ext, exponentiation_into,
-                       final_poly_into, fold_rounds_into, index_and_x, interpolation_layout)
+                       final_poly_into, fold_rounds_into, interpolation_layout, x_from_bits)
 from .fri_initial import _reducing_into, combine_into, openings_into
 from .merkle import declare_swap_gate, opening_into
 
@@ -58,6 +61,64 @@ def gate_groups(cap_height, arity_bits):
     return (0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 3, 4, 5)
 
 
+ROW_NAMES = ("bs_row", "exp0_row", "x_row", "init_ra_row", "init_hash_row", "init_path_row", "reduce_row", "num_row", "den_row", "quot_row",
+             "total_row", "old_row", "ra_row", "exp_row", "shift_row", "interp_row", "sq_row", "coset_ra_row", "coset_hash_row",
+             "coset_path_row", "horner_row")
+
+
+def query_rounds_into(c, consts, alpha, beta, bits_of, cap_index_of, within_of):
+    """Every query round of circuit c (a FriQueryRoundCircuit, or sipp_amd/fri_proof.py's circuit of the same shape attributes and public-
+    input positions) with what the challenges decide given as arguments.  consts = the cells (zero, one, omega_M, 1 / g); alpha: two limb
+    sources; beta(r, l): the source of limb l of round r's challenge; bits_of(q) -> (the row that split query q's index, its log_m bit
+    cells, low first); cap_index_of(q, bits) -> the source of the index's top cap_height bits as one value; within_of(q, r, bits) -> the
+    source of round r's index within its coset (bits: the arity_bits cells it is made of).  The opened rows, the siblings, the
+    evaluations and the coset siblings are witness inputs made here (c._new_input).  Sets c.opened_row, c.power_row and the per-query
+    row lists ROW_NAMES."""
+    zero, one, omega, ginv = consts
+    a, M, C = c.arity_bits, c.log_m, c.cap_height
+    cap_shape = (RANDOM_ACCESS_CAP, c.cap_rows, c.cap_copies, c.cap_stride, c.n_cap)
+    # once per proof and batch: the reduced openings, alpha^len
+    c.opened_row, c.power_row, acc_o, alpha_len = openings_into(c, REDUCING_EXT, alpha, zero, lambda b, j, l: pi(c.pi_opened(b, j, l)))
+    for name in ROW_NAMES:
+        setattr(c, name, [])
+    for q in range(c.n_queries):
+        # the one reading of the index and of x
+        bs, bits = bits_of(q)
+        e0, xr, x = x_from_bits(c, EXPONENTIATION, bits, omega, zero, None)
+        cap_index, cap_bits = cap_index_of(q, bits[M - C:]), bits[M - C:]
+        # the initial openings: every oracle's row under its cap
+        leaves, ras, hashes, paths = [], [], [], []
+        for o, width in enumerate(c.oracle_widths):
+            row = [c._new_input("row", q, o, k) for k in range(width)]
+            sib = [[c._new_input("sibling", q, o, l, t) for t in range(4)] for l in range(c.height)]
+            ra, hs, path = opening_into(c, cap_shape, POSEIDON_SWAP, zero, row, bits[:c.height], cap_index,
+                                        lambda j, w: pi(c.pi_cap(o, j, w)), cap_bits, lambda l, t: sib[l][t])
+            leaves += row
+            ras.append(ra); hashes.append(hs); paths.append(path)
+        # the combination of those same row cells, times x: the first old
+        (lf, nm, dn, qt, tt, orow), old = combine_into(c, (REDUCING, QUOTIENT_EXT), alpha, zero, one, x, acc_o, alpha_len,
+                                                       lambda k: leaves[k], lambda b, l: pi(c.pi_point(b, l)))
+        # the folds: one cell per evaluation for the RandomAccess items, the interpolation row and (below) the coset leaf
+        ev = [[[c._new_input("eval", q, r, j, l) for l in range(2)] for j in range(c.arity)] for r in range(c.n_rounds)]
+        within = [within_of(q, r, bits[a * r:a * (r + 1)]) for r in range(c.n_rounds)]
+        fold_rows, x_last, last = fold_rounds_into(c, (RANDOM_ACCESS_EVAL, EXPONENTIATION, COSET_INTERPOLATION), c.ra_stride, zero,
+                                                   ginv, bits, x[0], list(old), lambda r, j, l: ev[r][j][l], beta, lambda r: within[r])
+        # every round's evaluations are a leaf under that round's cap, in the proof's order
+        cras, chashes, cpaths = [], [], []
+        for r in range(c.n_rounds):
+            sib = [[c._new_input("coset_sibling", q, r, l, t) for t in range(4)] for l in range(c.round_height[r])]
+            ra, hs, path = opening_into(c, cap_shape, POSEIDON_SWAP, zero, [ev[r][j][l] for j in range(c.arity) for l in range(2)],
+                                        bits[a * (r + 1):M - C], cap_index, lambda j, w: pi(c.pi_round_cap(r, j, w)), cap_bits,
+                                        lambda l, t: sib[l][t])
+            cras.append(ra); chashes.append(hs); cpaths.append(path)
+        # the final polynomial at x is the last old
+        horner, acc = final_poly_into(c, zero, x_last, lambda k, l: pi(c.pi_final(k, l)))
+        for l in range(2):
+            c.tie(acc[l], last[l])
+        for name, got in zip(ROW_NAMES, (bs, e0, xr, ras, hashes, paths, lf, nm, dn, qt, tt, orow) + tuple(fold_rows) + (cras, chashes, cpaths, horner)):
+            getattr(c, name).append(got)
+
+
 class FriQueryRoundCircuit(CircuitBuilder):
     """The circuit of the n_queries query rounds of a FRI opening proof over an LDE of 2^log_m points: initial oracles of
     oracle_widths[o] columns under caps of 2^cap_height digests; batch b combines the columns batches[b] (indices into the row of all
@@ -69,6 +130,28 @@ class FriQueryRoundCircuit(CircuitBuilder):
                  k_base=None, k_ext=None, min_log_n=10, pow_bits=0, draw_challenges=False, n_salt=None):
         assert pow_bits == 0, "the proof of work is out of scope"
         assert not draw_challenges, "drawing the challenges in circuit (the challenger) is out of scope"
+        self._set_shape(log_m, cap_height, oracle_widths, batches, arity_bits, n_rounds, final_len, n_queries, num_wires, num_routed, k_base,
+                        k_ext, n_salt)
+        # public-input positions
+        self.pi_batch, t = [], 2
+        for b in self.batches:
+            self.pi_batch.append(t)
+            t += 2 + 2 * len(b)
+        self.pi_caps = t
+        self.pi_rounds = t + 4 * self.n_cap * len(self.oracle_widths)
+        self.pi_finals = self.pi_rounds + n_rounds * (4 * self.n_cap + 2)
+        self.pi_queries = self.pi_finals + 2 * final_len
+        CircuitBuilder.__init__(self, num_wires, num_routed, GATE_NAMES, gate_groups(cap_height, self.arity_bits), 2, self.pi_queries + n_queries)
+        self._declare_gates()
+        self._in_keys = []                                      # what every witness input is, in the order of their making
+        self._wiring()
+        self.finish(min_log_n)
+        cells = [x for cyc in self.pi_cycle + self.in_cycle for x in cyc]
+        assert len(cells) == len(set(cells))
+
+    def _set_shape(self, log_m, cap_height, oracle_widths, batches, arity_bits, n_rounds, final_len, n_queries, num_wires, num_routed, k_base,
+                   k_ext, n_salt):
+        """the shape's refusals and what the wiring reads of it (sipp_amd/fri_proof.py's circuit takes the same shapes)"""
         if not isinstance(arity_bits, int):
             arity_bits = [int(a) for a in arity_bits]
             assert len(arity_bits) == n_rounds and len(set(arity_bits)) == 1, "mixed arities are out of scope"
@@ -93,16 +176,6 @@ class FriQueryRoundCircuit(CircuitBuilder):
         self.round_height = [self.height - arity_bits * (r + 1) for r in range(n_rounds)]
         self.omega_m = _root_of_unity(log_m)
         self.g_inv = pow(_root_of_unity(arity_bits), P - 2, P)
-        # public-input positions
-        self.pi_batch, t = [], 2
-        for b in batches:
-            self.pi_batch.append(t)
-            t += 2 + 2 * len(b)
-        self.pi_caps = t
-        self.pi_rounds = t + 4 * self.n_cap * len(oracle_widths)
-        self.pi_finals = self.pi_rounds + n_rounds * (4 * self.n_cap + 2)
-        self.pi_queries = self.pi_finals + 2 * final_len
-        super().__init__(num_wires, num_routed, GATE_NAMES, gate_groups(cap_height, arity_bits), 2, self.pi_queries + n_queries)
         # cap selection: per copy index, claimed, 2^cap_height items, cap_height bits, all routed (the bits are tied to the index split);
         # copies per row divide 4 (one digest word per copy)
         self.cap_stride = 2 + self.n_cap + cap_height
@@ -113,6 +186,10 @@ class FriQueryRoundCircuit(CircuitBuilder):
         assert 2 * self.ra_stride <= num_routed
         self.interp = interpolation_layout(arity_bits, INTERP_DEGREE)
         assert self.interp["point"] + 4 <= num_routed and self.interp["num_wires"] <= num_wires
+
+    def _declare_gates(self):
+        """the thirteen gates of GATE_NAMES"""
+        log_m, cap_height, arity_bits, k_base, k_ext = self.log_m, self.cap_height, self.arity_bits, self.k_base, self.k_ext
         self.declare_basic(log_m)
         declare_arithmetic_ext(self, ARITHMETIC_EXT)
         self.declare(REDUCING, 2, (GEN_REDUCING, k_base, EXT_W), _reducing_into, k_base, EXT_W, False)
@@ -126,11 +203,6 @@ class FriQueryRoundCircuit(CircuitBuilder):
         declare_swap_gate(self, POSEIDON_SWAP)
         self.declare(COSET_INTERPOLATION, min(INTERP_DEGREE, self.arity), (GEN_COSET_INTERPOLATION, arity_bits, INTERP_DEGREE, EXT_W),
                      coset_interpolation_into, arity_bits, INTERP_DEGREE, EXT_W)
-        self._in_keys = []                                      # what every witness input is, in the order of their making
-        self._wiring()
-        self.finish(min_log_n)
-        cells = [x for cyc in self.pi_cycle + self.in_cycle for x in cyc]
-        assert len(cells) == len(set(cells))
 
     # public-input positions
     def pi_alpha(self, l):
@@ -163,7 +235,6 @@ class FriQueryRoundCircuit(CircuitBuilder):
         return self.witness_input()
 
     def _wiring(self):
-        a, M, C = self.arity_bits, self.log_m, self.cap_height
         self.pi_row = self.new_row(PUBLIC_INPUT)
         self.place(self.pi_row)
         self.zero_row, zero = self.constant(0)
@@ -171,51 +242,13 @@ class FriQueryRoundCircuit(CircuitBuilder):
         self.omega_row, omega = self.constant(self.omega_m)
         self.ginv_row, ginv = self.constant(self.g_inv)
         alpha = (pi(self.pi_alpha(0)), pi(self.pi_alpha(1)))
-        cap_shape = (RANDOM_ACCESS_CAP, self.cap_rows, self.cap_copies, self.cap_stride, self.n_cap)
-        # once per proof and batch: the reduced openings, alpha^len
-        self.opened_row, self.power_row, acc_o, alpha_len = openings_into(self, REDUCING_EXT, alpha, zero,
-                                                                          lambda b, j, l: pi(self.pi_opened(b, j, l)))
-        names = ("bs_row", "exp0_row", "x_row", "init_ra_row", "init_hash_row", "init_path_row", "reduce_row", "num_row", "den_row", "quot_row",
-                 "total_row", "old_row", "ra_row", "exp_row", "shift_row", "interp_row", "sq_row", "coset_ra_row", "coset_hash_row",
-                 "coset_path_row", "horner_row")
-        for name in names:
-            setattr(self, name, [])
-        for q in range(self.n_queries):
-            # the one reading of the index and of x
-            bs, e0, xr, bits, x = index_and_x(self, EXPONENTIATION, pi(self.pi_x_index(q)), omega, zero, None)
-            cap_index, cap_bits = self._new_input("cap_index", q), bits[M - C:]
-            # the initial openings: every oracle's row under its cap
-            leaves, ras, hashes, paths = [], [], [], []
-            for o, width in enumerate(self.oracle_widths):
-                row = [self._new_input("row", q, o, c) for c in range(width)]
-                sib = [[self._new_input("sibling", q, o, l, t) for t in range(4)] for l in range(self.height)]
-                ra, hs, path = opening_into(self, cap_shape, POSEIDON_SWAP, zero, row, bits[:self.height], cap_index,
-                                            lambda j, w: pi(self.pi_cap(o, j, w)), cap_bits, lambda l, t: sib[l][t])
-                leaves += row
-                ras.append(ra); hashes.append(hs); paths.append(path)
-            # the combination of those same row cells, times x: the first old
-            (lf, nm, dn, qt, tt, orow), old = combine_into(self, (REDUCING, QUOTIENT_EXT), alpha, zero, one, x, acc_o, alpha_len,
-                                                           lambda c: leaves[c], lambda b, l: pi(self.pi_point(b, l)))
-            # the folds: one cell per evaluation for the RandomAccess items, the interpolation row and (below) the coset leaf
-            ev = [[[self._new_input("eval", q, r, j, l) for l in range(2)] for j in range(self.arity)] for r in range(self.n_rounds)]
-            within = [self._new_input("within", q, r) for r in range(self.n_rounds)]
-            fold_rows, x_last, last = fold_rounds_into(self, (RANDOM_ACCESS_EVAL, EXPONENTIATION, COSET_INTERPOLATION), self.ra_stride, zero,
-                                                       ginv, bits, x[0], list(old), lambda r, j, l: ev[r][j][l],
-                                                       lambda r, l: pi(self.pi_beta(r, l)), lambda r: within[r])
-            # every round's evaluations are a leaf under that round's cap, in the proof's order
-            cras, chashes, cpaths = [], [], []
-            for r in range(self.n_rounds):
-                sib = [[self._new_input("coset_sibling", q, r, l, t) for t in range(4)] for l in range(self.round_height[r])]
-                ra, hs, path = opening_into(self, cap_shape, POSEIDON_SWAP, zero, [ev[r][j][l] for j in range(self.arity) for l in range(2)],
-                                            bits[a * (r + 1):M - C], cap_index, lambda j, w: pi(self.pi_round_cap(r, j, w)), cap_bits,
-                                            lambda l, t: sib[l][t])
-                cras.append(ra); chashes.append(hs); cpaths.append(path)
-            # the final polynomial at x is the last old
-            horner, acc = final_poly_into(self, zero, x_last, lambda k, l: pi(self.pi_final(k, l)))
-            for l in range(2):
-                self.tie(acc[l], last[l])
-            for name, got in zip(names, (bs, e0, xr, ras, hashes, paths, lf, nm, dn, qt, tt, orow) + tuple(fold_rows) + (cras, chashes, cpaths, horner)):
-                getattr(self, name).append(got)
+
+        def bits_of(q):                                         # the one reading of the index: a BaseSum row splits the public x_index
+            bs = self.new_row(BASE_SUM)
+            self.place(bs, [(0, pi(self.pi_x_index(q)))])
+            return bs, [(1 + i, bs) for i in range(self.log_m)]
+        query_rounds_into(self, (zero, one, omega, ginv), alpha, lambda r, l: pi(self.pi_beta(r, l)), bits_of,
+                          lambda q, bits: self._new_input("cap_index", q), lambda q, r, bits: self._new_input("within", q, r))
         self.hash_public_inputs(POSEIDON_SWAP, zero)
 
     # ---- the values ----
