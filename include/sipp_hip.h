@@ -614,6 +614,24 @@ int sipp_circuit_prove(sipp_circuit_data *cd, const uint64_t *wires, const uint6
 int sipp_circuit_prove_inputs(sipp_circuit_data *cd, const uint64_t *cells, const uint64_t *values, size_t n_inputs,
                               const uint64_t *public_inputs, uint32_t n_public_inputs,
                               uint64_t *proof_out, size_t proof_cap, size_t *proof_len);
+/* the same proof straight from the words the input cells are copies of (a flat proof the circuit verifies, say): which cell takes
+ * which word is fixed when the circuit is built, so the map goes to the device once and a proof sends the words alone.
+ * sipp_circuit_set_input_map: pair k says cell cells[k] = wire * N + row takes word sources[k] of words || extra, where words are
+ * n_words and extra n_extra u64 (what the words do not carry: a transcript, points, caps).  Both arrays are HOST memory and are copied
+ * to device memory of the circuit data's own, freed by sipp_circuit_destroy; a second call replaces the map; n = 0 is a map.  A cell
+ * >= num_wires * N or a source >= n_words + n_extra: SIPP_E_BADARG, found on the host, and the map set before stays in force.
+ * sipp_circuit_prove_words: words / extra are HOST memory (NULL where their count is 0).  SIPP_E_BADARG when no map is set or when
+ * n_words / n_extra are not the map's; SIPP_E_NOMEM, nothing launched, if the staging (8 bytes a word) does not fit the arena.  On the
+ * ctx stream: words || extra are copied into arena staging, the wire table is zeroed, one kernel stores staged[sources[k]] at cells[k]
+ * (one lane per pair), a second pass compares every pair with the table; a cell that received two different values raises a device flag
+ * read back before witness generation starts: SIPP_E_BADARG, no proof written (two pairs with equal values are accepted).  Then the call
+ * goes on as sipp_circuit_prove_inputs does; the proof is word for word that call's for cells[k], staged[sources[k]].  After any refusal
+ * the circuit data proves as before. */
+int sipp_circuit_set_input_map(sipp_circuit_data *cd, const uint64_t *cells, const uint64_t *sources, size_t n,
+                               size_t n_words, size_t n_extra);
+int sipp_circuit_prove_words(sipp_circuit_data *cd, const uint64_t *words, size_t n_words, const uint64_t *extra, size_t n_extra,
+                             const uint64_t *public_inputs, uint32_t n_public_inputs,
+                             uint64_t *proof_out, size_t proof_cap, size_t *proof_len);
 int sipp_circuit_verify(const sipp_circuit_data *cd, const uint64_t *proof, size_t len, int *reason);
 
 /* ---- verification of the generic proofs (host code like sipp_stark_verify; stages in *reason, may be NULL) -------------------------

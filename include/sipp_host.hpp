@@ -338,6 +338,28 @@ class CircuitData {
         r.public_inputs.assign(r.flat.end() - (std::ptrdiff_t)public_inputs.size(), r.flat.end());
         return r;
     }
+    // which cell (wire * N + row) takes which word of words || extra in every later prove_words: fixed when the circuit is built, so
+    // it goes to the device once.  A second call replaces the map; a refused one (a cell or source out of range) leaves the map before
+    void set_input_map(const std::vector<uint64_t>& cells, const std::vector<uint64_t>& sources, size_t n_words, size_t n_extra) {
+        if (cells.size() != sources.size()) throw Error(SIPP_E_BADARG, "CircuitData::set_input_map: cells and sources differ in length");
+        const int rc = sipp_circuit_set_input_map(data_, cells.data(), sources.data(), cells.size(), n_words, n_extra);
+        if (rc != SIPP_OK) throw Error(rc, std::string("sipp_circuit_set_input_map: ") + sipp_last_error(ctx_));
+    }
+    // `data.prove(pw)` with pw gathered on the device from the words the input cells are copies of (a flat proof, say) and `extra`,
+    // what the words do not carry
+    ProofWithPublicInputs prove_words(const std::vector<uint64_t>& words, const std::vector<uint64_t>& extra,
+                                      const std::vector<uint64_t>& public_inputs) {
+        ProofWithPublicInputs r;
+        const size_t cap = sipp_circuit_proof_size(data_, (uint32_t)public_inputs.size());
+        r.flat.assign(cap, 0);
+        size_t len = 0;
+        const int rc = sipp_circuit_prove_words(data_, words.data(), words.size(), extra.data(), extra.size(), public_inputs.data(),
+                                                (uint32_t)public_inputs.size(), r.flat.data(), cap, &len);
+        if (rc != SIPP_OK) throw Error(rc, std::string("sipp_circuit_prove_words: ") + sipp_last_error(ctx_));
+        r.flat.resize(len);
+        r.public_inputs.assign(r.flat.end() - (std::ptrdiff_t)public_inputs.size(), r.flat.end());
+        return r;
+    }
     // `data.verify(proof)`: throws Error(SIPP_E_VERIFY) naming the refusing stage
     void verify(const ProofWithPublicInputs& proof) const {
         int reason = 0;

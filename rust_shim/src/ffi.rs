@@ -234,6 +234,11 @@ extern "C" {
     pub fn sipp_circuit_prove_inputs(cd: *mut SippCircuitDataOpaque, cells: *const u64, values: *const u64, n_inputs: usize,
                                      public_inputs: *const u64, n_public_inputs: u32, proof_out: *mut u64, proof_cap: usize,
                                      proof_len: *mut usize) -> c_int;
+    pub fn sipp_circuit_set_input_map(cd: *mut SippCircuitDataOpaque, cells: *const u64, sources: *const u64, n: usize, n_words: usize,
+                                      n_extra: usize) -> c_int;
+    pub fn sipp_circuit_prove_words(cd: *mut SippCircuitDataOpaque, words: *const u64, n_words: usize, extra: *const u64, n_extra: usize,
+                                    public_inputs: *const u64, n_public_inputs: u32, proof_out: *mut u64, proof_cap: usize,
+                                    proof_len: *mut usize) -> c_int;
     pub fn sipp_circuit_verify(cd: *const SippCircuitDataOpaque, proof: *const u64, len: usize, reason: *mut c_int) -> c_int;
     pub fn sipp_plonk_verify_gates(proof: *const u64, len: usize, constants_sigmas_cap: *const u64, p: *const SippPlonkParams, fp: *const SippFriParams,
                                    c: *const SippPlonkCircuit, circuit_digest: *const u64, reason: *mut c_int) -> c_int;

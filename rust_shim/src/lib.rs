@@ -151,6 +151,29 @@ impl CircuitData {
         Ok(out)
     }
 
+    /// Which cell takes which word of `words || extra` in every later `prove_words`: fixed when the circuit is built, so it goes to the
+    /// device once.  A second call replaces the map; a refused one (a cell or a source out of range) leaves the map set before.
+    pub fn set_input_map(&mut self, cells: &[u64], sources: &[u64], n_words: usize, n_extra: usize) -> Result<()> {
+        anyhow::ensure!(cells.len() == sources.len(), "set_input_map: {} cells but {} sources", cells.len(), sources.len());
+        let rc = unsafe { ffi::sipp_circuit_set_input_map(self.raw, cells.as_ptr(), sources.as_ptr(), cells.len(), n_words, n_extra) };
+        if rc == 0 { Ok(()) } else { Err(anyhow::anyhow!("sipp_circuit_set_input_map: status {}", rc)) }
+    }
+
+    /// `prove_inputs` with the values gathered on the device: `words` (a flat proof this circuit verifies, say) and `extra` (what the
+    /// words do not carry) go up as they are, the map of `set_input_map` says where each lands.
+    pub fn prove_words(&mut self, words: &[u64], extra: &[u64], public_inputs: &[u64]) -> Result<Vec<u64>> {
+        let cap = unsafe { ffi::sipp_circuit_proof_size(self.raw, public_inputs.len() as u32) };
+        let mut out = vec![0u64; cap];
+        let mut len = 0usize;
+        let rc = unsafe {
+            ffi::sipp_circuit_prove_words(self.raw, words.as_ptr(), words.len(), extra.as_ptr(), extra.len(), public_inputs.as_ptr(),
+                                          public_inputs.len() as u32, out.as_mut_ptr(), cap, &mut len)
+        };
+        if rc != 0 { return Err(anyhow::anyhow!("sipp_circuit_prove_words: status {}", rc)); }
+        out.truncate(len);
+        Ok(out)
+    }
+
     /// `data.verify(proof)`
     pub fn verify(&self, proof: &[u64]) -> Result<()> {
         let mut reason: std::os::raw::c_int = 0;

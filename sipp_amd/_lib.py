@@ -189,6 +189,8 @@ SIGNATURES = {
     "sipp_circuit_proof_size": (C.c_size_t, [vp, C.c_uint32]),
     "sipp_circuit_prove": (C.c_int, [vp, vp, u64p, C.c_uint32, vp, C.c_size_t, C.POINTER(C.c_size_t)]),
     "sipp_circuit_prove_inputs": (C.c_int, [vp, vp, vp, C.c_size_t, u64p, C.c_uint32, vp, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "sipp_circuit_set_input_map": (C.c_int, [vp, vp, vp, C.c_size_t, C.c_size_t, C.c_size_t]),
+    "sipp_circuit_prove_words": (C.c_int, [vp, vp, C.c_size_t, vp, C.c_size_t, u64p, C.c_uint32, vp, C.c_size_t, C.POINTER(C.c_size_t)]),
     "sipp_circuit_verify": (C.c_int, [vp, vp, C.c_size_t, C.POINTER(C.c_int)]),
     "sipp_plonk_perm_prove": (C.c_int, [vp, vp, vp, C.c_uint32, C.POINTER(PlonkParams), C.POINTER(FriParams), u64p, u64p, vp, C.c_size_t,
                                         C.POINTER(C.c_size_t)]),
@@ -789,6 +791,7 @@ class CircuitData:
         dg = np.zeros(4, dtype=np.uint64)
         ctx._ck(self.L.sipp_circuit_verifier_data(self.h, cap.ctypes.data, dg.ctypes.data), "circuit_verifier_data")
         self.cap, self.digest = cap, dg
+        self.input_map = None                              # (n_words, n_extra) once set_input_map has been served
 
     def prove(self, wires, public_inputs):
         w = np.ascontiguousarray(wires, dtype=np.uint64)
@@ -820,6 +823,34 @@ class CircuitData:
         self.ctx._ck(self.L.sipp_circuit_prove_inputs(self.h, cells.ctypes.data if len(cells) else None, values.ctypes.data if len(cells) else None,
                                                       len(cells), self.ctx._u64(pis) if pis else None, len(pis), out.ctypes.data, cap, C.byref(n)),
                      "circuit_prove_inputs")
+        return out[: n.value]
+
+    def set_input_map(self, cells, sources, n_words, n_extra):
+        """sipp_circuit_set_input_map: cells[k] takes word sources[k] of words || extra (n_words, n_extra u64) in every later
+        prove_words; a second call replaces the map, a refused one leaves it"""
+        cells = np.ascontiguousarray(cells, dtype=np.uint64).reshape(-1)
+        sources = np.ascontiguousarray(sources, dtype=np.uint64).reshape(-1)
+        if len(cells) != len(sources):
+            raise SippError(-1, "CircuitData.set_input_map: cells and sources differ in length")
+        self.ctx._ck(self.L.sipp_circuit_set_input_map(self.h, cells.ctypes.data if len(cells) else None, sources.ctypes.data if len(cells) else None,
+                                                       len(cells), int(n_words), int(n_extra)), "circuit_set_input_map")
+        self.input_map = (int(n_words), int(n_extra))
+
+    def prove_words(self, words, extra, public_inputs):
+        """prove_inputs() with the values gathered on the device (sipp_circuit_prove_words): the map of set_input_map says which cell
+        takes which word of words || extra"""
+        words = np.ascontiguousarray(words, dtype=np.uint64).reshape(-1)
+        extra = np.ascontiguousarray(extra, dtype=np.uint64).reshape(-1)
+        pis = np.ascontiguousarray(public_inputs, dtype=np.uint64).reshape(-1)
+        cap = self.L.sipp_circuit_proof_size(self.h, len(pis))
+        if cap == 0:
+            raise SippError(-1, "sipp_circuit_proof_size")
+        out = np.zeros(cap, dtype=np.uint64)
+        n = C.c_size_t()
+        self.ctx._ck(self.L.sipp_circuit_prove_words(self.h, words.ctypes.data if len(words) else None, len(words),
+                                                     extra.ctypes.data if len(extra) else None, len(extra),
+                                                     pis.ctypes.data_as(C.POINTER(C.c_uint64)) if len(pis) else None, len(pis), out.ctypes.data, cap,
+                                                     C.byref(n)), "circuit_prove_words")
         return out[: n.value]
 
     def verify(self, proof):

@@ -11,6 +11,7 @@ gate programs more than one of them uses, the builder that turns rows and feeds 
                             the cells, schedules the copies and gives every row the level behind its latest computed source, and tie();
                             the public-input Poseidon chain; finish(), which fixes N and makes the cycles and the level schedule.  A
                             circuit is a subclass: it declares its gates, writes its statement as builder calls and finishes
+  _Challenger               plonky2's RecursiveChallenger on a builder (sipp_amd/fri_proof.py says how it buffers and duplexes)
   CircuitProver             a built circuit through the library's CircuitData
 
 numpy only; imports nothing from the test oracle."""
@@ -383,6 +384,33 @@ class CircuitBuilder:
         for t, cyc in enumerate(self.pi_cycle):
             flat[np.asarray(cyc, dtype=np.int64)] = np.uint64(pis[t] % P)
         return w, flat
+
+
+class _Challenger:
+    """plonky2's RecursiveChallenger on a builder: sources in, cells out"""
+
+    def __init__(self, b, gate, zero, state, pending):
+        """gate: b's PoseidonSwap gate; state: 12 sources; pending: the buffered input sources"""
+        self.b, self.gate, self.zero, self.sponge, self.inbuf, self.outbuf, self.rows = b, gate, zero, list(state), list(pending), [], []
+
+    def _duplex(self):
+        b = self.b
+        r = b.new_row(self.gate)
+        b.place(r, [(b.s_in + t, self.inbuf[t] if t < len(self.inbuf) else self.sponge[t]) for t in range(12)] + [(b.s_swap, self.zero)])
+        self.sponge = [(b.s_out + t, r) for t in range(12)]
+        self.inbuf, self.outbuf = [], self.sponge[:8]
+        self.rows.append(r)
+
+    def observe(self, source):
+        self.outbuf = []
+        self.inbuf.append(source)
+        if len(self.inbuf) == 8:
+            self._duplex()
+
+    def get(self):
+        if self.inbuf or not self.outbuf:
+            self._duplex()
+        return self.outbuf.pop()
 
 
 class CircuitProver:

@@ -24,9 +24,14 @@ struct sipp_circuit_data {
     sipp_oracle cs_oracle{};
     std::vector<uint64_t> cap;
     uint64_t digest[4] = {0, 0, 0, 0};
+    // the input map of sipp_circuit_set_input_map: cells then sources in one block of its own (replaced as a whole, so not in `dev`)
+    uint64_t* d_map = nullptr;
+    size_t map_n = 0, map_words = 0, map_extra = 0;
+    bool has_map = false;
     ~sipp_circuit_data() {
         if (ctx) (void)hipSetDevice(ctx->device);
         for (void* q : dev) (void)hipFree(q);
+        if (d_map) (void)hipFree(d_map);
     }
 };
 
@@ -187,7 +192,50 @@ __global__ void __launch_bounds__(256) circuit_check_inputs_kernel(const uint64_
     for (size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x; k < count; k += step) bad |= wires[cells[k]] != values[k];
     if (bad) atomicOr(conflict, 1u);
 }
+// the same two passes for sipp_circuit_prove_words: pair k takes its value from the staged words through the data's input map.  Every
+// cell is below the table's size and every source below the staged length: sipp_circuit_set_input_map refuses a map where one is not.
+__global__ void __launch_bounds__(256) circuit_scatter_words_kernel(uint64_t* wires, const uint64_t* cells, const uint64_t* sources,
+                                                                    const uint64_t* staged, size_t count) {
+    const size_t step = (size_t)gridDim.x * blockDim.x;
+    for (size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x; k < count; k += step) wires[cells[k]] = staged[sources[k]];
+}
+__global__ void __launch_bounds__(256) circuit_check_words_kernel(const uint64_t* wires, const uint64_t* cells, const uint64_t* sources,
+                                                                  const uint64_t* staged, size_t count, unsigned int* conflict) {
+    const size_t step = (size_t)gridDim.x * blockDim.x;
+    bool bad = false;
+    for (size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x; k < count; k += step) bad |= wires[cells[k]] != staged[sources[k]];
+    if (bad) atomicOr(conflict, 1u);
+}
 }  // namespace
+
+extern "C" int sipp_circuit_set_input_map(sipp_circuit_data* cd, const uint64_t* cells, const uint64_t* sources, size_t n, size_t n_words,
+                                          size_t n_extra) {
+    if (!cd) return SIPP_E_BADARG;
+    sipp_ctx* ctx = cd->ctx;
+    if ((n && (!cells || !sources)) || n > ((size_t)1 << 40) || n_words > ((size_t)1 << 40) || n_extra > ((size_t)1 << 40))
+        return sipp_fail(ctx, SIPP_E_BADARG, "circuit input map: null argument or a count out of range");
+    const size_t total = (size_t)cd->circ.num_wires << cd->log_n, staged = n_words + n_extra;
+    for (size_t k = 0; k < n; k++) {
+        if (cells[k] >= total) return sipp_fail(ctx, SIPP_E_BADARG, "circuit input map: a cell outside the wire table");
+        if (sources[k] >= staged) return sipp_fail(ctx, SIPP_E_BADARG, "circuit input map: a source outside words || extra");
+    }
+    SIPP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    void* q = nullptr;
+    if (hipMalloc(&q, (n ? 2 * n : 1) * 8) != hipSuccess) return sipp_fail(ctx, SIPP_E_NOMEM, "circuit input map: hipMalloc failed");
+    uint64_t* d_new = reinterpret_cast<uint64_t*>(q);
+    if (n && (hipMemcpy(d_new, cells, n * 8, hipMemcpyHostToDevice) != hipSuccess ||
+              hipMemcpy(d_new + n, sources, n * 8, hipMemcpyHostToDevice) != hipSuccess)) {
+        (void)hipFree(q);
+        return sipp_fail(ctx, SIPP_E_HIP, "circuit input map: upload failed");
+    }
+    // the old map goes only now: every refusal above has left it in force.  No kernel reads it any more: a proof ends on the host
+    if (cd->d_map) {
+        (void)hipStreamSynchronize(ctx->stream);
+        (void)hipFree(cd->d_map);
+    }
+    cd->d_map = d_new; cd->map_n = n; cd->map_words = n_words; cd->map_extra = n_extra; cd->has_map = true;
+    return SIPP_OK;
+}
 
 extern "C" int sipp_circuit_prove(sipp_circuit_data* cd, const uint64_t* wires, const uint64_t* public_inputs, uint32_t n_public_inputs,
                                   uint64_t* proof_out, size_t proof_cap, size_t* proof_len) {
@@ -234,6 +282,44 @@ extern "C" int sipp_circuit_prove_inputs(sipp_circuit_data* cd, const uint64_t* 
             SIPP_CHECK_HIP(ctx, hipMemcpyAsync(&conflict, d_conflict, sizeof conflict, hipMemcpyDeviceToHost, ctx->stream));
             SIPP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
             if (conflict) return sipp_fail(ctx, SIPP_E_BADARG, "circuit prove inputs: one cell given two different values");
+        }
+    }
+    return prove_uploaded(cd, public_inputs, n_public_inputs, proof_out, proof_cap, proof_len);
+}
+
+extern "C" int sipp_circuit_prove_words(sipp_circuit_data* cd, const uint64_t* words, size_t n_words, const uint64_t* extra, size_t n_extra,
+                                        const uint64_t* public_inputs, uint32_t n_public_inputs, uint64_t* proof_out, size_t proof_cap,
+                                        size_t* proof_len) {
+    if (!cd) return SIPP_E_BADARG;
+    sipp_ctx* ctx = cd->ctx;
+    if ((n_words && !words) || (n_extra && !extra) || !proof_out || !proof_len || (n_public_inputs && !public_inputs) || n_public_inputs > (1u << 24))
+        return sipp_fail(ctx, SIPP_E_BADARG, "circuit prove words: null argument");
+    if (!cd->has_map) return sipp_fail(ctx, SIPP_E_BADARG, "circuit prove words: no input map set (sipp_circuit_set_input_map)");
+    if (n_words != cd->map_words || n_extra != cd->map_extra)
+        return sipp_fail(ctx, SIPP_E_BADARG, "circuit prove words: n_words / n_extra differ from the input map's");
+    const size_t total = (size_t)cd->circ.num_wires << cd->log_n, n = cd->map_n;
+    SIPP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    {
+        // as in sipp_circuit_prove_inputs: the staging goes back before witness generation, behind the wait for the flag
+        ArenaScope scope(ctx);
+        uint64_t* d_staged = arena_alloc_t<uint64_t>(ctx, n_words + n_extra + 1);        // words, extra, the flag's word
+        if (!d_staged) return SIPP_E_NOMEM;
+        unsigned int* d_conflict = reinterpret_cast<unsigned int*>(d_staged + n_words + n_extra);
+        SIPP_CHECK_HIP(ctx, hipMemsetAsync(cd->d_wires, 0, total * 8, ctx->stream));
+        if (n) {
+            SIPP_CHECK_HIP(ctx, hipMemsetAsync(d_conflict, 0, 8, ctx->stream));
+            if (n_words) SIPP_CHECK_HIP(ctx, hipMemcpyAsync(d_staged, words, n_words * 8, hipMemcpyHostToDevice, ctx->stream));
+            if (n_extra) SIPP_CHECK_HIP(ctx, hipMemcpyAsync(d_staged + n_words, extra, n_extra * 8, hipMemcpyHostToDevice, ctx->stream));
+            const uint64_t *d_cells = cd->d_map, *d_sources = cd->d_map + n;
+            const size_t want = (n + 255) / 256;
+            const dim3 grid((unsigned)(want < 4096 ? want : 4096));
+            hipLaunchKernelGGL(circuit_scatter_words_kernel, grid, dim3(256), 0, ctx->stream, cd->d_wires, d_cells, d_sources, d_staged, n);
+            hipLaunchKernelGGL(circuit_check_words_kernel, grid, dim3(256), 0, ctx->stream, cd->d_wires, d_cells, d_sources, d_staged, n, d_conflict);
+            SIPP_CHECK_HIP(ctx, hipGetLastError());
+            unsigned int conflict = 0;
+            SIPP_CHECK_HIP(ctx, hipMemcpyAsync(&conflict, d_conflict, sizeof conflict, hipMemcpyDeviceToHost, ctx->stream));
+            SIPP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            if (conflict) return sipp_fail(ctx, SIPP_E_BADARG, "circuit prove words: one cell mapped to two different values");
         }
     }
     return prove_uploaded(cd, public_inputs, n_public_inputs, proof_out, proof_cap, proof_len);

@@ -3,8 +3,9 @@ sipp_amd/fri_verifier.py (query_rounds_into) behind a challenger that runs IN CI
 recalled), with the proof of work.  alpha, every beta_r and every x_index are generated cells: nobody who asks for the proof picks them.
 
   FriProofCircuit   the statement "this opening proof verifies against these caps, behind this transcript"
-  FriProofProver    the circuit through the library's CircuitData: prove_proof(flat proof, caps, points, transcript) gathers the input
-                    cells from the proof's words through a map fixed at build (input_map) and calls sipp_circuit_prove_inputs;
+  FriProofProver    the circuit through the library's CircuitData: the map from the proof's words to the input cells is fixed at build
+                    (words_map) and set on the device once; prove_proof(flat proof, caps, points, transcript) sends the words and
+                    calls sipp_circuit_prove_words (without a device map: a numpy gather and sipp_circuit_prove_inputs);
                     prove(*arguments) with explicit arguments stays, for tests and tampering
 
 Challenger.  observe() buffers sources; eight buffered inputs, or a get() with inputs pending or no output left, make one swap-0
@@ -36,39 +37,13 @@ Refused at build: mixed arities, salted oracles, empty batches (FriQueryRoundCir
 numpy only; imports nothing from the test oracle."""
 import numpy as np
 
-from .circuit import GEN_BASE_SPLIT, GEN_BASE_SUM, P, PUBLIC_INPUT, CircuitBuilder, CircuitProver, _i64, base_sum_into, pi
+from .circuit import GEN_BASE_SPLIT, GEN_BASE_SUM, P, PUBLIC_INPUT, CircuitBuilder, CircuitProver, _Challenger, _i64, base_sum_into, pi
 from .fri_verifier import GATE_NAMES as ROUND_GATE_NAMES
 from .fri_verifier import POSEIDON_SWAP, FriQueryRoundCircuit, gate_groups, query_rounds_into
 
 GATE_NAMES = ROUND_GATE_NAMES + ["BaseSplit64", "BaseSumCap", "BaseSumWithin"]
 BASE_SPLIT64, BASE_SUM_CAP, BASE_SUM_WITHIN = range(len(ROUND_GATE_NAMES), len(ROUND_GATE_NAMES) + 3)
 HEADER_WORDS = 8                                                # of the flat "SIPPFRI1" proof
-
-
-class _Challenger:
-    """plonky2's RecursiveChallenger on a builder: sources in, cells out"""
-
-    def __init__(self, b, zero, state, pending):
-        self.b, self.zero, self.sponge, self.inbuf, self.outbuf, self.rows = b, zero, list(state), list(pending), [], []
-
-    def _duplex(self):
-        b = self.b
-        r = b.new_row(POSEIDON_SWAP)
-        b.place(r, [(b.s_in + t, self.inbuf[t] if t < len(self.inbuf) else self.sponge[t]) for t in range(12)] + [(b.s_swap, self.zero)])
-        self.sponge = [(b.s_out + t, r) for t in range(12)]
-        self.inbuf, self.outbuf = [], self.sponge[:8]
-        self.rows.append(r)
-
-    def observe(self, source):
-        self.outbuf = []
-        self.inbuf.append(source)
-        if len(self.inbuf) == 8:
-            self._duplex()
-
-    def get(self):
-        if self.inbuf or not self.outbuf:
-            self._duplex()
-        return self.outbuf.pop()
 
 
 class FriProofCircuit(FriQueryRoundCircuit):
@@ -137,7 +112,7 @@ class FriProofCircuit(FriQueryRoundCircuit):
         self.one_row, one = self.constant(1)
         self.omega_row, omega = self.constant(self.omega_m)
         self.ginv_row, ginv = self.constant(self.g_inv)
-        ch = _Challenger(self, zero, [pi(self.pi_state(t)) for t in range(12)], [pi(self.pi_pending(t)) for t in range(self.n_in)])
+        ch = _Challenger(self, POSEIDON_SWAP, zero, [pi(self.pi_state(t)) for t in range(12)], [pi(self.pi_pending(t)) for t in range(self.n_in)])
         for b, cols in enumerate(self.batches):
             for j in range(len(cols)):
                 for l in range(2):
@@ -279,9 +254,16 @@ class FriProofCircuit(FriQueryRoundCircuit):
         offset of its value in the flat proof"""
         return self._map
 
-    def proof_inputs(self, proof, caps, points, transcript):
-        """a flat proof with what it does not carry -> (cells, values, public inputs), uint64, by gathers alone: the words are taken
-        as they are (a device proof's are canonical)"""
+    def words_map(self):
+        """(cells, sources, n_words, n_extra) of sipp_circuit_set_input_map: every input cell once, with the offset of its value in
+        flat proof || extra, extra = the inputs that are no proof words in public-input order (transcript || points || caps)"""
+        cells, word = self._map
+        return (np.concatenate([cells, self._other[0]]), np.concatenate([word, self.proof_words + self._other[1]]).astype(np.uint64),
+                self.proof_words, len(self.pi_other))
+
+    def words_of_proof(self, proof, caps, points, transcript):
+        """a flat proof with what it does not carry -> (words, extra, public inputs), uint64: the words are taken as they are (a
+        device proof's are canonical); the public inputs are a gather from both"""
         proof = np.ascontiguousarray(proof, dtype=np.uint64).reshape(-1)
         assert len(proof) == self.proof_words
         other = np.concatenate([np.asarray(transcript[0], dtype=np.uint64).reshape(-1), np.asarray(transcript[1], dtype=np.uint64).reshape(-1),
@@ -290,6 +272,11 @@ class FriProofCircuit(FriQueryRoundCircuit):
         pis = np.empty(self.n_pi, dtype=np.uint64)
         pis[self.pi_other] = other
         pis[self.pi_word >= 0] = proof[self.pi_word[self.pi_word >= 0]]
+        return proof, other, pis
+
+    def proof_inputs(self, proof, caps, points, transcript):
+        """a flat proof with what it does not carry -> (cells, values, public inputs), uint64, by gathers alone"""
+        proof, other, pis = self.words_of_proof(proof, caps, points, transcript)
         cells, word = self._map
         return np.concatenate([cells, self._other[0]]), np.concatenate([proof[word], other[self._other[1]]]), pis
 
@@ -323,10 +310,14 @@ def flat_proof_arguments(circ, proof, caps, points, transcript):
 
 class FriProofProver(CircuitProver):
     """FriProofCircuit through the library's CircuitData: built once, then prove_proof(flat proof, caps, points, transcript) or
-    prove(*arguments), and verify.  Both hand the library (cell, value) pairs (sipp_circuit_prove_inputs)."""
+    prove(*arguments), and verify.  prove hands the library (cell, value) pairs (sipp_circuit_prove_inputs); prove_proof hands it the
+    proof's words and the device gathers them through the map set at build (sipp_circuit_prove_words), unless device_map=False keeps
+    the gather in numpy."""
 
-    def __init__(self, ctx, *shape, fri=None, params=None, digest=None, **kw):
+    def __init__(self, ctx, *shape, fri=None, params=None, digest=None, device_map=True, **kw):
         super().__init__(ctx, FriProofCircuit(*shape, **kw), fri, params, digest)
+        if device_map:
+            self.data.set_input_map(*self.circ.words_map())
 
     def prove(self, *inputs):
         c = self.circ
@@ -336,4 +327,6 @@ class FriProofProver(CircuitProver):
     def prove_proof(self, proof, caps, points, transcript):
         """caps: per initial oracle 2^cap_height digests; points: per batch (c0, c1); transcript: (the 12 state words, the n_in pending
         inputs) the challenger arrives with.  No Python-integer walk of the proof, no host replay of the challenger."""
+        if self.data.input_map is not None:
+            return self.data.prove_words(*self.circ.words_of_proof(proof, caps, points, transcript))
         return self.data.prove_inputs(*self.circ.proof_inputs(proof, caps, points, transcript))
