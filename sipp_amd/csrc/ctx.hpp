@@ -90,8 +90,6 @@ struct sipp_ctx {
         size_t n_in[2] = {0, 0};
     } fold;
 
-    // sipp_exp_outputs: sipp_trace_fill stops after the accumulator chains and writes the outputs into the records
-    bool outputs_only = false;
     // sipp_ctx_set_hardened: kinds 0 / 1 on this ctx mean the hardened G1 / G2 AIRs (kinds 4 / 5)
     bool hardened = false;
     uint32_t kernel_routes = 0;     // sipp_ctx_set_kernel_routes: SIPP_ROUTE_* bits (fallback kernels kept under test)
@@ -210,6 +208,16 @@ enum TableKind {
     TAB_TW_HI = 3,    // w_m^(x * 2^L)             key (logm, inverse)
     TAB_POW_LO = 4,   // base^x * c                key (id, L)
     TAB_POW_HI = 5,   // base^(x * 2^L)            key (id, L)
+    // (20 / 21: ntt.hip, 30 / 31: ntt_tree.hip)
+    TAB_AIR_PROG = 100,        // an AIR's program                                   key (kind + 8 hardened, table_bits)
+    TAB_GADGET_OFF = 101,      // where each of its gadgets starts                   key (kind + 8 hardened, table_bits)
+    TAB_PAIRING = 102,         // schedule, constants and row maps of the pairing    key (0, 0)
+    TAB_VFLAG = 103,           // selector columns [n_vflag][2^log_rows] int8        key (kind, 0)
+    TAB_VPER = 104,            // value-periodic columns on the quotient coset       key (log_n, kind)
+    TAB_WITNESS_ERR = 105,     // witness.hip: the error word a captured graph keeps key (0, 0)
+    TAB_PAIRING_ROWSRC = 106,  // pool index of every cell group of a pairing row    key (0, 0)
+    TAB_PRODUCT_OFF = 107,     // count and offsets of a lone gadget's products      key (kind + 8 hardened, table_bits)
+    TAB_PERIODIC = 200,        // + k: periodic column k on the quotient coset       key (log_n, 0)
 };
 
 uint64_t* sipp_table_get(sipp_ctx* ctx, int kind, uint64_t a, uint64_t b);
@@ -257,14 +265,16 @@ const air_spec_t* sipp_air_get(int kind, uint32_t log_n);
 const int64_t* sipp_air_prog_device(sipp_ctx* ctx, const air_spec_t* a);
 int sipp_trace_fill(sipp_ctx* ctx, const air_spec_t* a, const uint32_t* d_ios, uint32_t num_io, uint32_t log_n,
                     uint64_t* d_trace, int* d_err);
-size_t sipp_curve_rows_bytes(int kind, uint32_t log_n);
+// the output words of every record written into the device records on ctx->stream (sipp_exp_outputs); no trace, no gate
+int sipp_outputs_fill(sipp_ctx* ctx, const air_spec_t* a, uint32_t* d_ios, uint32_t num_io, uint32_t log_n, int* d_err);
 // mapg2.hip: the map Fp2 -> E'(Fp2) (MapToG2 AIR, kind 3): primary witness rows / (x, y) written into the records
 int sipp_mapg2_fill(sipp_ctx* ctx, const air_spec_t* a, const uint32_t* d_ios, uint32_t num_io, uint32_t log_n, uint64_t* d_trace,
                     int* d_err);
 int sipp_mapg2_outputs(sipp_ctx* ctx, uint32_t* d_ios, uint32_t num_io, int* d_err);
-// pairing.hip: the final pairing (pairing AIR, kind 6): primary witness rows, or (ctx->outputs_only) Z written into the records
+// pairing.hip: the final pairing (pairing AIR, kind 6): primary witness rows / Z written into the records
 int sipp_pairing_fill(sipp_ctx* ctx, const air_spec_t* a, const uint32_t* d_ios, uint32_t num_io, uint32_t log_n, uint64_t* d_trace,
                       int* d_err);
+int sipp_pairing_outputs(sipp_ctx* ctx, uint32_t* d_ios, uint32_t num_io, int* d_err);
 // the AIR's selector columns (value-periodic, small integers) on the device: [n_vflag][2^log_rows] int8; nullptr for an AIR without
 const int8_t* sipp_air_vflag_device(sipp_ctx* ctx, const air_spec_t* a);
 // outputs of n1 G1 and n2 G2 obligations, the two accumulator chains on two streams (native.hip's fold of a SIPP round)

@@ -235,20 +235,8 @@ void fold_records(const std::vector<uint32_t>& A, const std::vector<uint32_t>& B
 // and B' = B1 + [1/x] B2; the complete IO records (outputs included) are left in rec1 / rec2
 int fold_round(sipp_ctx* ctx, const std::vector<uint32_t>& A, const std::vector<uint32_t>& B, size_t n, const uint32_t x[8],
                const uint32_t ix[8], std::vector<uint32_t>& rec1, std::vector<uint32_t>& rec2) {
-    const size_t h = n / 2;
-    rec1.assign(h * SIPP_G1_IO_WORDS, 0);
-    rec2.assign(h * SIPP_G2_IO_WORDS, 0);
-    for (size_t i = 0; i < h; i++) {
-        uint32_t* r = &rec1[i * SIPP_G1_IO_WORDS];
-        memcpy(r, &A[(h + i) * G1W], G1W * 4);
-        memcpy(r + 16, &A[i * G1W], G1W * 4);
-        memcpy(r + 32, x, 32);
-        uint32_t* s = &rec2[i * SIPP_G2_IO_WORDS];
-        memcpy(s, &B[(h + i) * G2W], G2W * 4);
-        memcpy(s + 32, &B[i * G2W], G2W * 4);
-        memcpy(s + 64, ix, 32);
-    }
-    return sipp_fold_outputs(ctx, rec1.data(), h, rec2.data(), h);
+    fold_records(A, B, n, x, ix, rec1, rec2);
+    return sipp_fold_outputs(ctx, rec1.data(), n / 2, rec2.data(), n / 2);
 }
 
 void take_outputs(const std::vector<uint32_t>& rec1, const std::vector<uint32_t>& rec2, size_t h, std::vector<uint32_t>& A,

@@ -1113,19 +1113,11 @@ __global__ void __launch_bounds__(256) pairing_expand_kernel(const uint16_t* __r
 
 }  // namespace
 
-// primary witness of the final-pairing AIR: d_ios [num_io][144] (padded: 8192 num_io == n rows).  outputs_only ctx: the records'
-// Z words are written instead (sipp_exp_outputs with kind = SIPP_PAIRING)
-int sipp_pairing_fill(sipp_ctx* ctx, const air_spec_t* a, const uint32_t* d_ios, uint32_t num_io, uint32_t log_n, uint64_t* d_trace,
-                      int* d_err) {
-    const size_t n = (size_t)1 << log_n;
-    const bool outputs = ctx->outputs_only;
-    const int32_t* lay = (a && a->cells_per_limb == 2) ? AIR_PAIRING_LAYOUT_U8 : AIR_PAIRING_LAYOUT_U16;
+// schedule, constants and row maps of the pairing kernels on the device (built once per ctx)
+static int pairing_table(sipp_ctx* ctx, const uint8_t** out) {
     static_assert(AIR_PAIRING_ROWS == 8192 && AIR_PAIRING_OPS == 512 && AIR_PAIRING_NREG == 6 && AIR_PAIRING_NGCONST == 6 && PP_N < 65536,
                   "pairing kernels: table shapes");
-    if (!outputs && (!a || a->kind != 6 || a->log_rows != AIR_PAIRING_LOG_ROWS || a->checked_base != lay[20] || a->pi_per_io != 144 ||
-                     (size_t)num_io * AIR_PAIRING_ROWS != n))
-        return sipp_fail(ctx, SIPP_E_UNSUPPORTED, "pairing AIR: table / shape mismatch");
-    uint64_t* t = sipp_table_get(ctx, 102, 0, 0);
+    uint64_t* t = sipp_table_get(ctx, TAB_PAIRING, 0, 0);
     if (!t) {
         std::vector<uint64_t> packed((PT_BYTES + 7) / 8, 0);
         uint8_t* b = reinterpret_cast<uint8_t*>(packed.data());
@@ -1141,37 +1133,55 @@ int sipp_pairing_fill(sipp_ctx* ctx, const air_spec_t* a, const uint32_t* d_ios,
         uint16_t* rc = reinterpret_cast<uint16_t*>(b + PT_GC);
         for (int g = 0; g < AIR_PAIRING_NGC; g++)
             for (int i = 0; i < 32; i++) rc[g * 32 + i] = (uint16_t)AIR_PAIRING_GC[g][i];
-        SIPP_TRY(sipp_table_put(ctx, 102, 0, 0, packed, &t));
+        SIPP_TRY(sipp_table_put(ctx, TAB_PAIRING, 0, 0, packed, &t));
     }
-    uint32_t* d_pools = nullptr;
-    uint64_t* src = nullptr;
-    if (!outputs) {
-        src = sipp_table_get(ctx, 106, 0, 0);
-        if (!src) {
-            std::vector<uint64_t> packed(((size_t)PE_N * AIR_PAIRING_ROWS * 2 + 7) / 8, 0);
-            if (pairing_row_sources(reinterpret_cast<uint16_t*>(packed.data())) != 0)
-                return sipp_fail(ctx, SIPP_E_UNSUPPORTED, "pairing AIR: the row program reads what the source replay does not know");
-            SIPP_TRY(sipp_table_put(ctx, 106, 0, 0, packed, &src));
-        }
-        d_pools = arena_alloc_t<uint32_t>(ctx, (size_t)num_io * PP_N * 8);
-        if (!d_pools) return sipp_fail(ctx, SIPP_E_NOMEM, "pairing AIR: value pools");
-        SIPP_CHECK_HIP(ctx, hipMemsetAsync(d_pools, 0, (size_t)num_io * PP_N * 32, ctx->stream));
+    *out = reinterpret_cast<const uint8_t*>(t);
+    return SIPP_OK;
+}
+
+// primary witness of the final-pairing AIR: d_ios [num_io][144] (padded: 8192 num_io == n rows)
+int sipp_pairing_fill(sipp_ctx* ctx, const air_spec_t* a, const uint32_t* d_ios, uint32_t num_io, uint32_t log_n, uint64_t* d_trace,
+                      int* d_err) {
+    const size_t n = (size_t)1 << log_n;
+    const int32_t* lay = (a && a->cells_per_limb == 2) ? AIR_PAIRING_LAYOUT_U8 : AIR_PAIRING_LAYOUT_U16;
+    if (!a || a->kind != 6 || a->log_rows != AIR_PAIRING_LOG_ROWS || a->checked_base != lay[20] || a->pi_per_io != 144 ||
+        (size_t)num_io * AIR_PAIRING_ROWS != n)
+        return sipp_fail(ctx, SIPP_E_UNSUPPORTED, "pairing AIR: table / shape mismatch");
+    const uint8_t* t = nullptr;
+    SIPP_TRY(pairing_table(ctx, &t));
+    uint64_t* src = sipp_table_get(ctx, TAB_PAIRING_ROWSRC, 0, 0);
+    if (!src) {
+        std::vector<uint64_t> packed(((size_t)PE_N * AIR_PAIRING_ROWS * 2 + 7) / 8, 0);
+        if (pairing_row_sources(reinterpret_cast<uint16_t*>(packed.data())) != 0)
+            return sipp_fail(ctx, SIPP_E_UNSUPPORTED, "pairing AIR: the row program reads what the source replay does not know");
+        SIPP_TRY(sipp_table_put(ctx, TAB_PAIRING_ROWSRC, 0, 0, packed, &src));
     }
+    uint32_t* d_pools = arena_alloc_t<uint32_t>(ctx, (size_t)num_io * PP_N * 8);
+    if (!d_pools) return sipp_fail(ctx, SIPP_E_NOMEM, "pairing AIR: value pools");
+    SIPP_CHECK_HIP(ctx, hipMemsetAsync(d_pools, 0, (size_t)num_io * PP_N * 32, ctx->stream));
     {
         ProfScope ps(ctx, "trace_pairing");
-        hipLaunchKernelGGL(pairing_values_kernel, dim3(num_io), dim3(64), 0, ctx->stream, const_cast<uint32_t*>(d_ios), num_io,
-                           reinterpret_cast<const uint8_t*>(t), d_pools, outputs ? 1 : 0, d_err);
+        hipLaunchKernelGGL(pairing_values_kernel, dim3(num_io), dim3(64), 0, ctx->stream, const_cast<uint32_t*>(d_ios), num_io, t, d_pools, 0,
+                           d_err);
         SIPP_CHECK_HIP(ctx, hipGetLastError());
     }
-    if (!outputs) {
-        ProfScope ps(ctx, "trace_pairing_cells");
-        PairElemCols k;
-        for (int e = 0; e < PE_N; e++) k.col[e] = pairing_elem_col(lay, e);
-        k.cpl = a->cells_per_limb;
-        hipLaunchKernelGGL(pairing_expand_kernel, dim3((unsigned)((n + 255) / 256), PE_N), dim3(256), 0, ctx->stream,
-                           reinterpret_cast<const uint16_t*>(src), d_pools, k, d_trace, n);
-        SIPP_CHECK_HIP(ctx, hipGetLastError());
-    }
+    ProfScope ps(ctx, "trace_pairing_cells");
+    PairElemCols k;
+    for (int e = 0; e < PE_N; e++) k.col[e] = pairing_elem_col(lay, e);
+    k.cpl = a->cells_per_limb;
+    hipLaunchKernelGGL(pairing_expand_kernel, dim3((unsigned)((n + 255) / 256), PE_N), dim3(256), 0, ctx->stream,
+                       reinterpret_cast<const uint16_t*>(src), d_pools, k, d_trace, n);
+    SIPP_CHECK_HIP(ctx, hipGetLastError());
+    return SIPP_OK;
+}
+
+// the records' Z words written instead (sipp_exp_outputs with kind = SIPP_PAIRING): no pools, no cells
+int sipp_pairing_outputs(sipp_ctx* ctx, uint32_t* d_ios, uint32_t num_io, int* d_err) {
+    const uint8_t* t = nullptr;
+    SIPP_TRY(pairing_table(ctx, &t));
+    ProfScope ps(ctx, "trace_pairing");
+    hipLaunchKernelGGL(pairing_values_kernel, dim3(num_io), dim3(64), 0, ctx->stream, d_ios, num_io, t, (uint32_t*)nullptr, 1, d_err);
+    SIPP_CHECK_HIP(ctx, hipGetLastError());
     return SIPP_OK;
 }
 

@@ -7,6 +7,7 @@
 // All arithmetic is Goldilocks u64 / quadratic extension; nothing here is GEMM shaped.
 #include <map>
 
+#include "air_prog.hpp"
 #include "ctx.hpp"
 #include "prover.hpp"
 
@@ -1218,7 +1219,7 @@ int sipp_k_quotient(sipp_ctx* ctx, const air_spec_t* a, uint32_t log_n, const ui
     // periodic tables over natural LDE index i mod 2 m_k
     for (int k = 0; k < AIR_N_PERIODIC; k++) {
         const uint64_t mk = (uint64_t)AIR_PERIODIC[k][0], r0 = (uint64_t)AIR_PERIODIC[k][1];
-        uint64_t* t = sipp_table_get(ctx, 200 + k, log_n, 0);
+        uint64_t* t = sipp_table_get(ctx, TAB_PERIODIC + k, log_n, 0);
         if (!t) {
             const uint64_t K = n / mk;
             std::vector<uint64_t> v(2 * mk);
@@ -1229,7 +1230,7 @@ int sipp_k_quotient(sipp_ctx* ctx, const air_spec_t* a, uint32_t log_n, const ui
                 uint64_t num = gl::sub(gl::pow(y, n), 1), den = gl::sub(gl::pow(y, K), 1);
                 v[i] = gl::mul(gl::mul(num, gl::inv(den)), scale);
             }
-            SIPP_TRY(sipp_table_put(ctx, 200 + k, log_n, 0, v, &t));
+            SIPP_TRY(sipp_table_put(ctx, TAB_PERIODIC + k, log_n, 0, v, &t));
         }
         q.per_tab[k] = t;
         q.per_mask[k] = (uint32_t)(2 * mk - 1);
@@ -1242,7 +1243,7 @@ int sipp_k_quotient(sipp_ctx* ctx, const air_spec_t* a, uint32_t log_n, const ui
         const uint32_t lr = (uint32_t)a->log_rows;
         const size_t R = (size_t)1 << lr, R2 = 2 * R;
         const int nv = a->n_vflag + a->n_vconst;
-        uint64_t* t = sipp_table_get(ctx, 104, log_n, (uint64_t)a->kind);
+        uint64_t* t = sipp_table_get(ctx, TAB_VPER, log_n, (uint64_t)a->kind);
         if (!t) {
             std::vector<uint64_t> tab((size_t)nv * R2), col(R2);
             const uint64_t shift = gl::pow(gl::GEN, (uint64_t)1 << (log_n - lr));
@@ -1267,7 +1268,7 @@ int sipp_k_quotient(sipp_ctx* ctx, const air_spec_t* a, uint32_t log_n, const ui
                 sipp_host_ntt(col.data(), lr + 1, false);
                 memcpy(&tab[(size_t)k * R2], col.data(), R2 * 8);
             }
-            SIPP_TRY(sipp_table_put(ctx, 104, log_n, (uint64_t)a->kind, tab, &t));
+            SIPP_TRY(sipp_table_put(ctx, TAB_VPER, log_n, (uint64_t)a->kind, tab, &t));
         }
         q.vper_tab = t;
         q.vper_mask = (uint32_t)(R2 - 1);
@@ -1300,29 +1301,15 @@ int sipp_k_quotient(sipp_ctx* ctx, const air_spec_t* a, uint32_t log_n, const ui
     {
         std::vector<uint32_t> off, cnt;
         std::vector<int> ncons;
-        const int64_t* w = a->prog;
-        const int64_t* end = a->prog + a->prog_len;
-        while (w < end && w[0] == 1) {
-            off.push_back((uint32_t)(w - a->prog));
+        const AirGadgets ag = air_read_gadgets(a->prog, a->prog_len);
+        for (const AirGadget& gd : ag.gadgets) {
+            off.push_back(gd.off);
             cnt.push_back(0);
-            if (w[6] != 2) return sipp_fail(ctx, SIPP_E_UNSUPPORTED, "quotient: gadgets must pair their limbs (group 2)");
-            ncons.push_back(32 / (int)w[6] + 1);
-            w += 7;
-            w += 2 + 5 * w[1];
-            int64_t np = *w++;
-            for (int64_t p = 0; p < np; p++) {
-                w += 1;
-                w += 2 + 5 * w[1];
-                w += 2 + 5 * w[1];
-            }
-            int64_t nl = *w++;
-            for (int64_t p = 0; p < nl; p++) {
-                w += 1;
-                w += 2 + 5 * w[1];
-            }
+            if (gd.group != 2) return sipp_fail(ctx, SIPP_E_UNSUPPORTED, "quotient: gadgets must pair their limbs (group 2)");
+            ncons.push_back(32 / (int)gd.group + 1);
             // many products: slices of about 40 (at most SIPP_QUOTIENT_MAX_SLICES), entries of the same offset with no constraints of their own
-            if (np > 64) {
-                const uint32_t nsl = (uint32_t)std::min<int64_t>(SIPP_QUOTIENT_MAX_SLICES, (np + 39) / 40);
+            if (gd.np > 64) {
+                const uint32_t nsl = (uint32_t)std::min<int64_t>(SIPP_QUOTIENT_MAX_SLICES, (gd.np + 39) / 40);
                 cnt.back() = 0x80000000u | (nsl << 8);
                 for (uint32_t k = 1; k < nsl; k++) {
                     off.push_back(off.back());
@@ -1331,6 +1318,8 @@ int sipp_k_quotient(sipp_ctx* ctx, const air_spec_t* a, uint32_t log_n, const ui
                 }
             }
         }
+        const int64_t* w = a->prog + ag.poly_off;
+        const int64_t* end = a->prog + a->prog_len;
         while (w < end) {  // runs of POLY ops
             off.push_back((uint32_t)(w - a->prog));
             uint32_t k = 0;

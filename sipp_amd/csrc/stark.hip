@@ -82,6 +82,22 @@ static int upload_ios(sipp_ctx* ctx, int kind, const uint32_t* ios, size_t num_i
     return SIPP_OK;
 }
 
+// the record-run sequence of prove_impl, sipp_trace_build and sipp_exp_outputs behind the upload of the records: zero the error
+// word, run(), read the error word, synchronise with `sync` (each site keeps its own call), name the failure
+static int stream_sync(sipp_ctx* ctx) {
+    SIPP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return SIPP_OK;
+}
+template <class Run>
+static int run_checked(sipp_ctx* ctx, int* d_err, int (*sync)(sipp_ctx*), const char* failure, Run run) {
+    SIPP_CHECK_HIP(ctx, hipMemsetAsync(d_err, 0, sizeof(int), ctx->stream));
+    SIPP_TRY(run());
+    int h_err = 0;
+    SIPP_CHECK_HIP(ctx, hipMemcpyAsync(&h_err, d_err, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    SIPP_TRY(sync(ctx));
+    return h_err ? sipp_fail(ctx, h_err, failure) : SIPP_OK;
+}
+
 // ---- BN254 Fq on the host, only for the public basis change of Fq12 public inputs (tools/air_gen.py build_fq12):
 // tower component t of the MyFq12 value c[0..11] (8 x u32 LE each): t = 2i -> (c_i + 9 c_{i+6}) mod p, t = 2i+1 -> c_{i+6}
 static void fq12_tower_limbs(const uint32_t* c96, int t, uint16_t limbs[16]) {
@@ -253,14 +269,9 @@ static int prove_impl(sipp_ctx* ctx, int kind, const uint32_t* ios, size_t num_i
         return SIPP_E_NOMEM;
     if (!pis_canonical(kind, pis.data(), s.num_io))
         return sipp_fail(ctx, SIPP_E_WITNESS, "IO record holds a non-canonical field element (>= p)");
-    SIPP_CHECK_HIP(ctx, hipMemsetAsync(d_err, 0, sizeof(int), ctx->stream));
-    SIPP_TRY(sipp_trace_fill(ctx, a, d_ios, s.num_io, log_n, d_trace, d_err));
-    {
-        int h_err = 0;
-        SIPP_CHECK_HIP(ctx, hipMemcpyAsync(&h_err, d_err, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-        SIPP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (h_err) return sipp_fail(ctx, h_err, "trace fill: IO record not provable (claimed output wrong, degenerate point or non-canonical limbs)");
-    }
+    SIPP_TRY(run_checked(ctx, d_err, stream_sync,
+                         "trace fill: IO record not provable (claimed output wrong, degenerate point or non-canonical limbs)",
+                         [&] { return sipp_trace_fill(ctx, a, d_ios, s.num_io, log_n, d_trace, d_err); }));
 
     tick("trace fill");
     if (ctx->gate_release) {
@@ -518,20 +529,11 @@ int sipp_trace_build(sipp_ctx* ctx, int kind, const uint32_t* ios, size_t num_io
     SIPP_TRY(shape_of(kind, num_io, &s));
     ArenaScope scope(ctx);
     uint32_t* d_ios = nullptr;
-    int rc = upload_ios(ctx, kind, ios, num_io, s, &d_ios, nullptr);
+    SIPP_TRY(upload_ios(ctx, kind, ios, num_io, s, &d_ios, nullptr));
     int* d_err = arena_alloc_t<int>(ctx, 1);
-    if (rc == SIPP_OK && !d_err) rc = SIPP_E_NOMEM;
-    if (rc == SIPP_OK) {
-        SIPP_CHECK_HIP(ctx, hipMemsetAsync(d_err, 0, sizeof(int), ctx->stream));
-        rc = sipp_trace_fill(ctx, s.air, d_ios, s.num_io, s.log_n, d_trace, d_err);
-    }
-    if (rc == SIPP_OK) {
-        int h_err = 0;
-        SIPP_CHECK_HIP(ctx, hipMemcpyAsync(&h_err, d_err, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-        rc = sipp_sync(ctx);
-        if (rc == SIPP_OK && h_err) rc = sipp_fail(ctx, h_err, "trace fill: IO record not provable");
-    }
-    return rc;
+    if (!d_err) return SIPP_E_NOMEM;
+    return run_checked(ctx, d_err, sipp_sync, "trace fill: IO record not provable",
+                       [&] { return sipp_trace_fill(ctx, s.air, d_ios, s.num_io, s.log_n, d_trace, d_err); });
 }
 
 int sipp_exp_outputs(sipp_ctx* ctx, int kind, uint32_t* ios, size_t num_io) {
@@ -543,29 +545,17 @@ int sipp_exp_outputs(sipp_ctx* ctx, int kind, uint32_t* ios, size_t num_io) {
     const size_t ppi = IO_WORDS[kind], out_words = kind == SIPP_G1_EXP ? 16 : (kind == SIPP_FQ12_EXP || kind == SIPP_PAIRING) ? 96 : 32;
     ArenaScope scope(ctx);
     uint32_t* d_ios = nullptr;
-    int rc = upload_ios(ctx, kind, ios, num_io, s, &d_ios, nullptr);
+    SIPP_TRY(upload_ios(ctx, kind, ios, num_io, s, &d_ios, nullptr));
     int* d_err = arena_alloc_t<int>(ctx, 1);
-    // the curves' outputs come straight from the accumulator chains (no trace rows); the Fq12 chain writes its cells
-    uint64_t* d_trace = kind == SIPP_FQ12_EXP ? arena_alloc_t<uint64_t>(ctx, (size_t)s.W << s.log_n) : nullptr;
-    if (rc == SIPP_OK && (!d_err || (kind == SIPP_FQ12_EXP && !d_trace))) rc = SIPP_E_NOMEM;
-    if (rc == SIPP_OK) {
-        SIPP_CHECK_HIP(ctx, hipMemsetAsync(d_err, 0, sizeof(int), ctx->stream));
-        ctx->outputs_only = true;
-        rc = sipp_trace_fill(ctx, s.air, d_ios, s.num_io, s.log_n, d_trace, d_err);
-        ctx->outputs_only = false;
-    }
-    if (rc == SIPP_OK) {
-        int h_err = 0;
-        uint32_t* h = reinterpret_cast<uint32_t*>(ctx->h_pinned);
+    if (!d_err) return SIPP_E_NOMEM;
+    uint32_t* h = reinterpret_cast<uint32_t*>(ctx->h_pinned);
+    SIPP_TRY(run_checked(ctx, d_err, sipp_sync, "exp_outputs: IO record not provable", [&]() -> int {
+        SIPP_TRY(sipp_outputs_fill(ctx, s.air, d_ios, s.num_io, s.log_n, d_err));
         SIPP_CHECK_HIP(ctx, hipMemcpyAsync(h, d_ios, num_io * ppi * 4, hipMemcpyDeviceToHost, ctx->stream));
-        SIPP_CHECK_HIP(ctx, hipMemcpyAsync(&h_err, d_err, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-        rc = sipp_sync(ctx);
-        if (rc == SIPP_OK && h_err) rc = sipp_fail(ctx, h_err, "exp_outputs: IO record not provable");
-        if (rc == SIPP_OK)
-            for (size_t io = 0; io < num_io; io++)
-                memcpy(ios + io * ppi + (ppi - out_words), h + io * ppi + (ppi - out_words), out_words * 4);
-    }
-    return rc;
+        return SIPP_OK;
+    }));
+    for (size_t io = 0; io < num_io; io++) memcpy(ios + io * ppi + (ppi - out_words), h + io * ppi + (ppi - out_words), out_words * 4);
+    return SIPP_OK;
 }
 
 }  // extern "C"
@@ -592,7 +582,7 @@ int sipp_fold_outputs(sipp_ctx* ctx, uint32_t* g1_ios, size_t n1, uint32_t* g2_i
     if (!d_err) return SIPP_E_NOMEM;
     int rc = SIPP_OK;
     for (int k = 0; k < 2 && rc == SIPP_OK; k++) rc = upload_ios(ctx, k, ios[k], num[k], s[k], &d_ios[k], nullptr);
-    hipStream_t main_stream = ctx->stream;
+    hipStream_t st[2] = {ctx->aux_stream, ctx->stream};   // G1 beside G2
     uint32_t* h = reinterpret_cast<uint32_t*>(ctx->h_pinned);
     const size_t h_off[2] = {0, ctx->h_pinned_words};  // u32 offsets: the two halves of the pinned buffer
     // the error words land in pinned memory too: a device-to-host copy into pageable memory would block the host until the
@@ -600,23 +590,20 @@ int sipp_fold_outputs(sipp_ctx* ctx, uint32_t* g1_ios, size_t n1, uint32_t* g2_i
     volatile int* h_err = reinterpret_cast<volatile int*>(h + 2 * ctx->h_pinned_words - 2);
     h_err[0] = h_err[1] = 0;
     if (rc == SIPP_OK) {
-        SIPP_CHECK_HIP(ctx, hipMemsetAsync(d_err, 0, 2 * sizeof(int), main_stream));
-        SIPP_CHECK_HIP(ctx, hipStreamSynchronize(main_stream));
-        ctx->outputs_only = true;
+        SIPP_CHECK_HIP(ctx, hipMemsetAsync(d_err, 0, 2 * sizeof(int), ctx->stream));
+        SIPP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
         for (int k = 0; k < 2 && rc == SIPP_OK; k++) {
-            ctx->stream = k == 0 ? ctx->aux_stream : main_stream;
-            rc = sipp_trace_fill(ctx, s[k].air, d_ios[k], s[k].num_io, s[k].log_n, nullptr, d_err + k);
-            // sipp_trace_fill has handed its row scratch back, but on another stream the kernels are still using it:
-            // take exactly that block again so that the next chain gets its own
-            if (rc == SIPP_OK && !arena_alloc(ctx, sipp_curve_rows_bytes(k, s[k].log_n))) rc = SIPP_E_NOMEM;
+            // each chain has its own Jacobian rows: both are in flight at once
+            void* rows = arena_alloc(ctx, sipp_fold_rows_bytes(k, s[k].num_io));
+            if (!rows) rc = SIPP_E_NOMEM;
+            if (rc == SIPP_OK) rc = sipp_fold_chain_begin(ctx, k, d_ios[k], s[k].num_io, (uint32_t)ppi[k], rows, st[k]);
+            if (rc == SIPP_OK) rc = sipp_fold_chain_finish(ctx, k, d_ios[k], s[k].num_io, (uint32_t)ppi[k], rows, d_err + k, st[k]);
             if (rc == SIPP_OK) {
-                (void)hipMemcpyAsync(h + h_off[k], d_ios[k], num[k] * ppi[k] * 4, hipMemcpyDeviceToHost, ctx->stream);
-                (void)hipMemcpyAsync(const_cast<int*>(h_err) + k, d_err + k, sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
+                (void)hipMemcpyAsync(h + h_off[k], d_ios[k], num[k] * ppi[k] * 4, hipMemcpyDeviceToHost, st[k]);
+                (void)hipMemcpyAsync(const_cast<int*>(h_err) + k, d_err + k, sizeof(int), hipMemcpyDeviceToHost, st[k]);
             }
         }
-        ctx->outputs_only = false;
-        ctx->stream = main_stream;
-        const hipError_t e0 = hipStreamSynchronize(ctx->aux_stream), e1 = hipStreamSynchronize(main_stream);
+        const hipError_t e0 = hipStreamSynchronize(st[0]), e1 = hipStreamSynchronize(st[1]);
         if (rc == SIPP_OK && (e0 != hipSuccess || e1 != hipSuccess)) rc = sipp_fail(ctx, SIPP_E_HIP, "fold_outputs: stream synchronisation failed");
     }
     if (rc == SIPP_OK && (h_err[0] || h_err[1])) rc = sipp_fail(ctx, h_err[0] ? h_err[0] : h_err[1], "fold_outputs: obligation not provable");

@@ -15,6 +15,7 @@
 //   table / lookups  range table column; per checked column histogram -> scan -> permuted columns
 #include <algorithm>
 
+#include "air_prog.hpp"
 #include "air_tables.h"
 #include "ctx.hpp"
 #include "fq.hpp"
@@ -1280,31 +1281,46 @@ const air_spec_t* sipp_air_get(int kind, uint32_t log_n) {
 }
 
 static int64_t* prog_on_device(sipp_ctx* ctx, const air_spec_t* a) {
-    uint64_t* t = sipp_table_get(ctx, 100, (uint64_t)(a->kind + 8 * a->hardened), (uint64_t)a->table_bits);
+    uint64_t* t = sipp_table_get(ctx, TAB_AIR_PROG, (uint64_t)(a->kind + 8 * a->hardened), (uint64_t)a->table_bits);
     if (t) return (int64_t*)t;
     std::vector<uint64_t> v(a->prog_len);
     memcpy(v.data(), a->prog, (size_t)a->prog_len * 8);
-    if (sipp_table_put(ctx, 100, (uint64_t)(a->kind + 8 * a->hardened), (uint64_t)a->table_bits, v, &t) != SIPP_OK) return nullptr;
+    if (sipp_table_put(ctx, TAB_AIR_PROG, (uint64_t)(a->kind + 8 * a->hardened), (uint64_t)a->table_bits, v, &t) != SIPP_OK) return nullptr;
     return (int64_t*)t;
 }
 const int64_t* sipp_air_prog_device(sipp_ctx* ctx, const air_spec_t* a) { return prog_on_device(ctx, a); }
 const int8_t* sipp_air_vflag_device(sipp_ctx* ctx, const air_spec_t* a) {
     if (a->n_vflag == 0) return nullptr;
-    uint64_t* t = sipp_table_get(ctx, 103, (uint64_t)a->kind, 0);
+    uint64_t* t = sipp_table_get(ctx, TAB_VFLAG, (uint64_t)a->kind, 0);
     if (!t) {
         const size_t bytes = (size_t)a->n_vflag << a->log_rows;
         std::vector<uint64_t> v((bytes + 7) / 8, 0);
         int8_t* f = reinterpret_cast<int8_t*>(v.data());       // flag k on row r: the weights of its terms the row descriptor meets
         for (int k = 0; k < a->n_vflag; k++)
             for (int r = 0; r < (1 << a->log_rows); r++) f[((size_t)k << a->log_rows) + (size_t)r] = (int8_t)air_vper_value(a, k, r);
-        if (sipp_table_put(ctx, 103, (uint64_t)a->kind, 0, v, &t) != SIPP_OK) return nullptr;
+        if (sipp_table_put(ctx, TAB_VFLAG, (uint64_t)a->kind, 0, v, &t) != SIPP_OK) return nullptr;
     }
     return reinterpret_cast<const int8_t*>(t);
 }
 
-// bytes of the Jacobian row scratch sipp_trace_fill takes from the arena FIRST for a curve AIR (kind 0 / 1) of 2^log_n rows
-size_t sipp_curve_rows_bytes(int kind, uint32_t log_n) {
-    return ((size_t)1 << log_n) * (kind == 0 ? sizeof(RowPts<1>) : sizeof(RowPts<2>));
+// ---- the accumulator chain of a curve AIR (EXT 1: G1, 2: G2) on stream st; `rows`: RowPts<EXT> for every row -----------------
+// the 255 doublings of every record's point x
+template <int EXT>
+static void curve_dbl(hipStream_t st, const uint32_t* d_ios, uint32_t num_io, uint32_t ppi, void* rows) {
+    constexpr uint32_t PER = 16 / EXT;   // records per block
+    hipLaunchKernelGGL((curve_dbl_par_kernel<EXT, 4 * EXT>), dim3((num_io + PER - 1) / PER), dim3(64), 0, st, d_ios, num_io, ppi,
+                       reinterpret_cast<RowPts<EXT>*>(rows));
+}
+// the scan over the exponent bits: selects and sums the powers
+template <int EXT>
+static void curve_scan(hipStream_t st, const uint32_t* d_ios, uint32_t num_io, uint32_t ppi, void* rows) {
+    hipLaunchKernelGGL(curve_scan_kernel<EXT>, dim3(num_io), dim3(256), 0, st, d_ios, num_io, ppi, reinterpret_cast<RowPts<EXT>*>(rows));
+}
+// the outputs of the scanned chains into the records; refuses (d_err) infinity and points off the curve
+template <int EXT>
+static void curve_outputs(hipStream_t st, void* rows, uint32_t* d_ios, uint32_t num_io, uint32_t ppi, int* d_err) {
+    hipLaunchKernelGGL(curve_outputs_kernel<EXT>, dim3((num_io + 63) / 64), dim3(64), 0, st, reinterpret_cast<RowPts<EXT>*>(rows), d_ios,
+                       num_io, ppi, d_err);
 }
 
 // ---- the folds of a native SIPP round in two phases (native.hip) ----------------------------------------------------------
@@ -1316,25 +1332,18 @@ size_t sipp_fold_rows_bytes(int kind, uint32_t num_io) {
 }
 int sipp_fold_chain_begin(sipp_ctx* ctx, int kind, const uint32_t* d_ios, uint32_t num_io, uint32_t ppi, void* rows, hipStream_t st) {
     // (no ProfScope: these launches go to a side stream, the event brackets belong to the main one)
-    if (kind == 0)
-        hipLaunchKernelGGL((curve_dbl_par_kernel<1, 4>), dim3((num_io + 15) / 16), dim3(64), 0, st, d_ios, num_io, ppi,
-                           reinterpret_cast<RowPts<1>*>(rows));
-    else
-        hipLaunchKernelGGL((curve_dbl_par_kernel<2, 8>), dim3((num_io + 7) / 8), dim3(64), 0, st, d_ios, num_io, ppi,
-                           reinterpret_cast<RowPts<2>*>(rows));
+    (kind == 0 ? curve_dbl<1> : curve_dbl<2>)(st, d_ios, num_io, ppi, rows);
     SIPP_CHECK_HIP(ctx, hipGetLastError());
     return SIPP_OK;
 }
 int sipp_fold_chain_finish(sipp_ctx* ctx, int kind, uint32_t* d_ios, uint32_t num_io, uint32_t ppi, void* rows, int* d_err,
                            hipStream_t st) {
     if (kind == 0) {
-        hipLaunchKernelGGL(curve_scan_kernel<1>, dim3(num_io), dim3(256), 0, st, d_ios, num_io, ppi, reinterpret_cast<RowPts<1>*>(rows));
-        hipLaunchKernelGGL(curve_outputs_kernel<1>, dim3((num_io + 63) / 64), dim3(64), 0, st, reinterpret_cast<RowPts<1>*>(rows), d_ios,
-                           num_io, ppi, d_err);
+        curve_scan<1>(st, d_ios, num_io, ppi, rows);
+        curve_outputs<1>(st, rows, d_ios, num_io, ppi, d_err);
     } else {
-        hipLaunchKernelGGL(curve_scan_kernel<2>, dim3(num_io), dim3(256), 0, st, d_ios, num_io, ppi, reinterpret_cast<RowPts<2>*>(rows));
-        hipLaunchKernelGGL(curve_outputs_kernel<2>, dim3((num_io + 63) / 64), dim3(64), 0, st, reinterpret_cast<RowPts<2>*>(rows), d_ios,
-                           num_io, ppi, d_err);
+        curve_scan<2>(st, d_ios, num_io, ppi, rows);
+        curve_outputs<2>(st, rows, d_ios, num_io, ppi, d_err);
     }
     SIPP_CHECK_HIP(ctx, hipGetLastError());
     return SIPP_OK;
@@ -1351,6 +1360,72 @@ static void gate_after_chain(sipp_ctx* ctx) {
     }
 }
 
+// the hardened curve AIRs' column layout (nullptr: not one of them)
+static const int32_t* hard_layout(const air_spec_t* a) {
+    if (!a->hardened || a->kind > 1) return nullptr;
+    return a->kind == 0 ? (a->cells_per_limb == 1 ? AIR_HARD_LAYOUT_G1H_U16 : AIR_HARD_LAYOUT_G1H_U8)
+                        : (a->cells_per_limb == 1 ? AIR_HARD_LAYOUT_G2H_U16 : AIR_HARD_LAYOUT_G2H_U8);
+}
+
+static int fq12_chain(sipp_ctx* ctx, const air_spec_t* a, const uint32_t* d_ios, uint32_t num_io, uint64_t* d_trace, size_t n) {
+    Fq12Cols c{1, 1 + 192, a->checked_base, a->cells_per_limb};
+    ProfScope ps(ctx, "trace_fq12_chain");
+    hipLaunchKernelGGL(fq12_chain_kernel, dim3(num_io), dim3(384), 0, ctx->stream, d_ios, num_io, d_trace, n, c);
+    SIPP_CHECK_HIP(ctx, hipGetLastError());
+    return SIPP_OK;
+}
+
+// the curve AIRs' state cells: the chain into Jacobian row scratch, the gate, then every row's cells from its points
+template <int EXT>
+static int curve_trace(sipp_ctx* ctx, const air_spec_t* a, const uint32_t* d_ios, uint32_t num_io, size_t n, int hard_inf_col,
+                       uint64_t* d_trace, int* d_err) {
+    const int ncl = 16 * EXT, cpl = a->cells_per_limb;
+    CurveCols c{1, 1 + ncl, 1 + 2 * ncl, 1 + 3 * ncl, a->checked_base, a->checked_base + ncl * cpl, a->checked_base + 2 * ncl * cpl, cpl};
+    RowPts<EXT>* rows = arena_alloc_t<RowPts<EXT>>(ctx, n);
+    if (!rows) return SIPP_E_NOMEM;
+    {
+        ProfScope ps(ctx, "trace_curve_chain");
+        curve_dbl<EXT>(ctx->stream, d_ios, num_io, (uint32_t)a->pi_per_io, rows);
+        curve_scan<EXT>(ctx->stream, d_ios, num_io, (uint32_t)a->pi_per_io, rows);
+    }
+    SIPP_CHECK_HIP(ctx, hipGetLastError());
+    gate_after_chain(ctx);
+    ProfScope ps(ctx, "trace_curve_rows");
+    hipLaunchKernelGGL(curve_rows_kernel<EXT>, dim3((unsigned)(n / ROWS_BLOCK)), dim3(ROWS_BLOCK), 0, ctx->stream, rows, d_trace, n, c,
+                       a->hardened, hard_inf_col, d_err);
+    SIPP_CHECK_HIP(ctx, hipGetLastError());
+    return SIPP_OK;
+}
+
+// sipp_exp_outputs: the accumulator chains alone, their results written into the records.  The claimed output words are never read.
+int sipp_outputs_fill(sipp_ctx* ctx, const air_spec_t* a, uint32_t* d_ios, uint32_t num_io, uint32_t log_n, int* d_err) {
+    const size_t n = (size_t)1 << log_n;
+    const uint32_t ppi = (uint32_t)a->pi_per_io;
+    if (a->kind == 3) return sipp_mapg2_outputs(ctx, d_ios, num_io, d_err);
+    if (a->kind == 6) return sipp_pairing_outputs(ctx, d_ios, num_io, d_err);
+    ArenaScope scope(ctx);   // the scratch goes back on every exit path (the caller's read-back is ordered behind its users)
+    if (a->kind == 2) {
+        // the Fq12 chain writes its cells: the accumulator cells of every block's last row are the outputs
+        uint64_t* d_trace = arena_alloc_t<uint64_t>(ctx, (size_t)(a->n_main + 2 * a->n_checked) << log_n);
+        if (!d_trace) return SIPP_E_NOMEM;
+        SIPP_TRY(fq12_chain(ctx, a, d_ios, num_io, d_trace, n));
+        hipLaunchKernelGGL(write_outputs_kernel, dim3((num_io + 63) / 64), dim3(64), 0, ctx->stream, d_ios, num_io, ppi, a->kind, d_trace, n, 1);
+    } else {
+        // the curves' outputs come straight from the Jacobian rows of the chains (no trace)
+        void* rows = arena_alloc(ctx, n * (a->kind == 0 ? sizeof(RowPts<1>) : sizeof(RowPts<2>)));
+        if (!rows) return SIPP_E_NOMEM;
+        {
+            ProfScope ps(ctx, "trace_curve_chain");
+            (a->kind == 0 ? curve_dbl<1> : curve_dbl<2>)(ctx->stream, d_ios, num_io, ppi, rows);
+            (a->kind == 0 ? curve_scan<1> : curve_scan<2>)(ctx->stream, d_ios, num_io, ppi, rows);
+        }
+        SIPP_CHECK_HIP(ctx, hipGetLastError());
+        (a->kind == 0 ? curve_outputs<1> : curve_outputs<2>)(ctx->stream, rows, d_ios, num_io, ppi, d_err);
+    }
+    SIPP_CHECK_HIP(ctx, hipGetLastError());
+    return SIPP_OK;
+}
+
 int sipp_trace_fill(sipp_ctx* ctx, const air_spec_t* a, const uint32_t* d_ios, uint32_t num_io, uint32_t log_n,
                     uint64_t* d_trace, int* d_err) {
     const size_t n = (size_t)1 << log_n;
@@ -1358,88 +1433,24 @@ int sipp_trace_fill(sipp_ctx* ctx, const air_spec_t* a, const uint32_t* d_ios, u
     ArenaScope scope(ctx);   // the row scratch and the lookup tables go back on EVERY exit path
     int col_bit = 0, col_e = 0, exp_off = 0;
     const bool exp_air = a->kind != 3 && a->kind != 6;   // the exponentiation AIRs: exponent cells, an accumulator compared with the record
+    const int32_t* lay = hard_layout(a);   // nullptr: not a hardened curve AIR
     if (a->kind == 3) {
         // MapToG2: eight rows per message, no exponent / accumulator cells (mapg2.hip); the claimed point is compared there
-        if (ctx->outputs_only) {
-            SIPP_TRY(sipp_mapg2_outputs(ctx, const_cast<uint32_t*>(d_ios), num_io, d_err));
-            return SIPP_OK;
-        }
         SIPP_TRY(sipp_mapg2_fill(ctx, a, d_ios, num_io, log_n, d_trace, d_err));
     } else if (a->kind == 6) {
         // the final pairing: one wave per record walks the schedule (pairing.hip); the claimed value is compared there
         SIPP_TRY(sipp_pairing_fill(ctx, a, d_ios, num_io, log_n, d_trace, d_err));
-        if (ctx->outputs_only) return SIPP_OK;
     } else if (a->kind == 2) {
-        Fq12Cols c{1, 1 + 192, a->checked_base, cpl};
         col_bit = 1 + 384;
         col_e = col_bit + 1;
         exp_off = 192;
-        ProfScope ps(ctx, "trace_fq12_chain");
-        hipLaunchKernelGGL(fq12_chain_kernel, dim3(num_io), dim3(384), 0, ctx->stream, d_ios, num_io, d_trace, n, c);
-        SIPP_CHECK_HIP(ctx, hipGetLastError());
+        SIPP_TRY(fq12_chain(ctx, a, d_ios, num_io, d_trace, n));
     } else {
-        const int ext = a->kind == 0 ? 1 : 2, ncl = 16 * ext;
-        const int32_t* hard_lay = !a->hardened ? nullptr
-                                  : a->kind == 0 ? (cpl == 1 ? AIR_HARD_LAYOUT_G1H_U16 : AIR_HARD_LAYOUT_G1H_U8)
-                                                 : (cpl == 1 ? AIR_HARD_LAYOUT_G2H_U16 : AIR_HARD_LAYOUT_G2H_U8);
-        const int hard_inf_col = hard_lay ? hard_lay[7] : 0;
-        CurveCols c{1, 1 + ncl, 1 + 2 * ncl, 1 + 3 * ncl, a->checked_base, a->checked_base + ncl * cpl,
-                    a->checked_base + 2 * ncl * cpl, cpl};
-        col_bit = 1 + 4 * ncl;
+        const int ext = a->kind == 0 ? 1 : 2;
+        col_bit = 1 + 4 * 16 * ext;
         col_e = col_bit + 1;
         exp_off = 32 * ext;
-        if (ext == 1) {
-            RowPts<1>* rows = arena_alloc_t<RowPts<1>>(ctx, n);
-            if (!rows) return SIPP_E_NOMEM;
-            {
-                ProfScope ps(ctx, "trace_curve_chain");
-                hipLaunchKernelGGL((curve_dbl_par_kernel<1, 4>), dim3((num_io + 15) / 16), dim3(64), 0, ctx->stream, d_ios, num_io,
-                                   (uint32_t)a->pi_per_io, rows);
-                hipLaunchKernelGGL(curve_scan_kernel<1>, dim3(num_io), dim3(256), 0, ctx->stream, d_ios, num_io,
-                                   (uint32_t)a->pi_per_io, rows);
-            }
-            SIPP_CHECK_HIP(ctx, hipGetLastError());
-            gate_after_chain(ctx);
-            if (ctx->outputs_only) {
-                hipLaunchKernelGGL(curve_outputs_kernel<1>, dim3((num_io + 63) / 64), dim3(64), 0, ctx->stream, rows,
-                                   const_cast<uint32_t*>(d_ios), num_io, (uint32_t)a->pi_per_io, d_err);
-                SIPP_CHECK_HIP(ctx, hipGetLastError());
-                return SIPP_OK;
-            }
-            ProfScope ps(ctx, "trace_curve_rows");
-            hipLaunchKernelGGL(curve_rows_kernel<1>, dim3((unsigned)(n / ROWS_BLOCK)), dim3(ROWS_BLOCK), 0, ctx->stream, rows,
-                               d_trace, n, c, a->hardened, hard_inf_col, d_err);
-            SIPP_CHECK_HIP(ctx, hipGetLastError());
-        } else {
-            RowPts<2>* rows = arena_alloc_t<RowPts<2>>(ctx, n);
-            if (!rows) return SIPP_E_NOMEM;
-            {
-                ProfScope ps(ctx, "trace_curve_chain");
-                hipLaunchKernelGGL((curve_dbl_par_kernel<2, 8>), dim3((num_io + 7) / 8), dim3(64), 0, ctx->stream, d_ios, num_io,
-                                   (uint32_t)a->pi_per_io, rows);
-                hipLaunchKernelGGL(curve_scan_kernel<2>, dim3(num_io), dim3(256), 0, ctx->stream, d_ios, num_io,
-                                   (uint32_t)a->pi_per_io, rows);
-            }
-            SIPP_CHECK_HIP(ctx, hipGetLastError());
-            gate_after_chain(ctx);
-            if (ctx->outputs_only) {
-                hipLaunchKernelGGL(curve_outputs_kernel<2>, dim3((num_io + 63) / 64), dim3(64), 0, ctx->stream, rows,
-                                   const_cast<uint32_t*>(d_ios), num_io, (uint32_t)a->pi_per_io, d_err);
-                SIPP_CHECK_HIP(ctx, hipGetLastError());
-                return SIPP_OK;
-            }
-            ProfScope ps(ctx, "trace_curve_rows");
-            hipLaunchKernelGGL(curve_rows_kernel<2>, dim3((unsigned)(n / ROWS_BLOCK)), dim3(ROWS_BLOCK), 0, ctx->stream, rows,
-                               d_trace, n, c, a->hardened, hard_inf_col, d_err);
-            SIPP_CHECK_HIP(ctx, hipGetLastError());
-        }
-    }
-    if (ctx->outputs_only) {
-        // sipp_exp_outputs: the accumulator cells of every block's last row are the outputs; nothing else is needed
-        hipLaunchKernelGGL(write_outputs_kernel, dim3((num_io + 63) / 64), dim3(64), 0, ctx->stream, const_cast<uint32_t*>(d_ios),
-                           num_io, (uint32_t)a->pi_per_io, a->kind, d_trace, n, 1);
-        SIPP_CHECK_HIP(ctx, hipGetLastError());
-        return SIPP_OK;
+        SIPP_TRY((ext == 1 ? curve_trace<1> : curve_trace<2>)(ctx, a, d_ios, num_io, n, lay ? lay[7] : 0, d_trace, d_err));
     }
     if (exp_air) {
         // accumulator state columns: R (curves, column 1) or acc (Fq12, column 1)
@@ -1458,10 +1469,8 @@ int sipp_trace_fill(sipp_ctx* ctx, const air_spec_t* a, const uint32_t* d_ios, u
         SIPP_CHECK_HIP(ctx, hipGetLastError());
     }
     if (a->hardened) {
-        if (a->kind > 1) return sipp_fail(ctx, SIPP_E_UNSUPPORTED, "hardened AIR: curves only");
+        if (!lay) return sipp_fail(ctx, SIPP_E_UNSUPPORTED, "hardened AIR: curves only");   // (hard_layout knows kinds 0 / 1 alone)
         const int ext = a->kind + 1, ncl = 16 * ext;
-        const int32_t* lay = a->kind == 0 ? (cpl == 1 ? AIR_HARD_LAYOUT_G1H_U16 : AIR_HARD_LAYOUT_G1H_U8)
-                                          : (cpl == 1 ? AIR_HARD_LAYOUT_G2H_U16 : AIR_HARD_LAYOUT_G2H_U8);
         SippBnP pl;
         for (int i = 0; i < 16; i++) pl.l[i] = AIR_BN_P_LIMBS[i];
         ProfScope ps(ctx, "trace_harden");
@@ -1474,36 +1483,23 @@ int sipp_trace_fill(sipp_ctx* ctx, const air_spec_t* a, const uint32_t* d_ios, u
         GadgetArgs g;
         g.prog = prog_on_device(ctx, a);
         if (!g.prog) return SIPP_E_HIP;
-        {
-            uint64_t* t = sipp_table_get(ctx, 101, (uint64_t)(a->kind + 8 * a->hardened), (uint64_t)a->table_bits);
-            if (!t) {
-                // gadgets come first in the program: record where each one starts
-                std::vector<uint32_t> off;
-                const int64_t* w = a->prog;
-                const int64_t* end = a->prog + a->prog_len;
-                while (w < end && w[0] == 1) {
-                    off.push_back((uint32_t)(w - a->prog));
-                    w += 7;
-                    w += 2 + 5 * w[1];
-                    int64_t np = *w++;
-                    for (int64_t p = 0; p < np; p++) {
-                        w += 1;
-                        w += 2 + 5 * w[1];
-                        w += 2 + 5 * w[1];
-                    }
-                    int64_t nl = *w++;
-                    for (int64_t p = 0; p < nl; p++) {
-                        w += 1;
-                        w += 2 + 5 * w[1];
-                    }
-                }
-                if ((int)off.size() != a->n_gadgets) return sipp_fail(ctx, SIPP_E_UNSUPPORTED, "AIR program: gadget count mismatch");
-                std::vector<uint64_t> packed((off.size() + 1) / 2 + 1, 0);
-                memcpy(packed.data(), off.data(), off.size() * 4);
-                SIPP_TRY(sipp_table_put(ctx, 101, (uint64_t)(a->kind + 8 * a->hardened), (uint64_t)a->table_bits, packed, &t));
-            }
-            g.gadget_off = reinterpret_cast<const uint32_t*>(t);
+        const uint64_t key = (uint64_t)(a->kind + 8 * a->hardened), tbits = (uint64_t)a->table_bits;
+        const bool lone = a->n_gadgets == 1;   // its product count is needed on every fill
+        uint64_t* t = sipp_table_get(ctx, TAB_GADGET_OFF, key, tbits);
+        AirGadgets ag;
+        if (!t || lone) {
+            ag = air_read_gadgets(a->prog, a->prog_len);
+            if ((int)ag.gadgets.size() != a->n_gadgets) return sipp_fail(ctx, SIPP_E_UNSUPPORTED, "AIR program: gadget count mismatch");
         }
+        if (!t) {
+            // gadgets come first in the program: record where each one starts
+            std::vector<uint32_t> off;
+            for (const AirGadget& gd : ag.gadgets) off.push_back(gd.off);
+            std::vector<uint64_t> packed((off.size() + 1) / 2 + 1, 0);
+            memcpy(packed.data(), off.data(), off.size() * 4);
+            SIPP_TRY(sipp_table_put(ctx, TAB_GADGET_OFF, key, tbits, packed, &t));
+        }
+        g.gadget_off = reinterpret_cast<const uint32_t*>(t);
         g.prog_len = a->prog_len;
         g.cpl = cpl;
         for (int i = 0; i < 16; i++) g.p_limbs[i] = AIR_BN_P_LIMBS[i];
@@ -1518,35 +1514,21 @@ int sipp_trace_fill(sipp_ctx* ctx, const air_spec_t* a, const uint32_t* d_ios, u
         g.prod_off = nullptr;
         g.esum = nullptr;
         g.np = 0;
-        if (a->n_gadgets == 1) {
-            // the one gadget's product offsets (table 107); more than 64 products: a wave per row sums them first
-            uint64_t* pt = sipp_table_get(ctx, 107, (uint64_t)(a->kind + 8 * a->hardened), (uint64_t)a->table_bits);
+        if (lone) {
+            // the one gadget's product count and offsets; more than 64 products: a wave per row sums them first
+            const AirGadget& g0 = ag.gadgets[0];
+            uint64_t* pt = sipp_table_get(ctx, TAB_PRODUCT_OFF, key, tbits);
             if (!pt) {
-                std::vector<uint32_t> po;
-                const int64_t* w = a->prog + 7;
-                w += 2 + 5 * w[1];
-                const int64_t np = *w++;
-                for (int64_t p = 0; p < np; p++) {
-                    po.push_back((uint32_t)(w - a->prog));
-                    w += 1;
-                    w += 2 + 5 * w[1];
-                    w += 2 + 5 * w[1];
-                }
-                po.push_back((uint32_t)(w - a->prog));
-                std::vector<uint64_t> packed(po.size() / 2 + 2, 0);
-                packed[0] = (uint64_t)np;
-                memcpy(packed.data() + 1, po.data(), po.size() * 4);
-                SIPP_TRY(sipp_table_put(ctx, 107, (uint64_t)(a->kind + 8 * a->hardened), (uint64_t)a->table_bits, packed, &pt));
+                std::vector<uint64_t> packed(g0.prod_off.size() / 2 + 2, 0);
+                packed[0] = (uint64_t)g0.np;
+                memcpy(packed.data() + 1, g0.prod_off.data(), g0.prod_off.size() * 4);
+                SIPP_TRY(sipp_table_put(ctx, TAB_PRODUCT_OFF, key, tbits, packed, &pt));
             }
-            // (the count sits in the device table; re-derive it on the host from the program: cheap)
-            const int64_t* w = a->prog + 7;
-            w += 2 + 5 * w[1];
-            const int np = (int)*w;
-            if (np > 64) {
+            if (g0.np > 64) {
                 g.esum = arena_alloc_t<int64_t>(ctx, n * 32);
                 if (!g.esum) return SIPP_E_NOMEM;
                 g.prod_off = reinterpret_cast<const uint32_t*>(pt + 1);
-                g.np = np;
+                g.np = (int)g0.np;
                 hipLaunchKernelGGL(gadget_products_kernel, dim3((unsigned)n), dim3(64), 0, ctx->stream, g, d_trace, n, d_err);
             }
         }

@@ -658,10 +658,10 @@ extern "C" int sipp_plonk_generate_witness_levels(sipp_ctx* ctx, uint64_t* d_wir
     if (sched->level_offsets[L] > n || (sched->copy_offsets[L] && (!sched->d_copy_src || !sched->d_copy_dst)))
         return sipp_fail(ctx, SIPP_E_BADARG, "plonk witness: more scheduled rows than the table has, or copies without their cell lists");
     // the error flag lives in a persistent one-word table of the ctx (the captured graph keeps its address)
-    int* d_err = reinterpret_cast<int*>(sipp_table_get(ctx, 101, 0, 0));
+    int* d_err = reinterpret_cast<int*>(sipp_table_get(ctx, TAB_WITNESS_ERR, 0, 0));
     if (!d_err) {
         uint64_t* t = nullptr;
-        SIPP_TRY(sipp_table_put(ctx, 101, 0, 0, std::vector<uint64_t>{0}, &t));
+        SIPP_TRY(sipp_table_put(ctx, TAB_WITNESS_ERR, 0, 0, std::vector<uint64_t>{0}, &t));
         d_err = reinterpret_cast<int*>(t);
     }
     int pos_gen = -1, n_pos = 0;
