@@ -523,6 +523,12 @@ int sipp_plonk_prove_gates(sipp_ctx *ctx, const uint64_t *d_wires, const uint64_
  *                                                                       they hold (the constraints, not the generator, range-check them); the
  *                                                                       same limits as kind 2: 1 + n_limbs <= num_wires, bits 1 .. 32,
  *                                                                       n_limbs bits <= 64                                  (BaseSumGenerator)
+ *   SIPP_GEN_POSEIDON_MDS   p = in, out                                 the permutation's linear layer on twelve EXTENSION elements, element c
+ *                                                                       limb l at in + 2c + l and out + 2c + l: out = M in limb by limb (M is
+ *                                                                       over the base field: two independent products), M the MDS matrix of
+ *                                                                       the Poseidon kinds.  The inputs are field values, whatever word they
+ *                                                                       hold; the outputs are canonical.  in + 24 <= num_wires, out + 24 <=
+ *                                                                       num_wires, and the two ranges must not meet         (PoseidonMdsGenerator)
  * The five families from SIPP_GEN_ARITHMETIC_EXT to SIPP_GEN_QUOTIENT_EXT take ANY field value in every input cell; W != 0.
  * Defined behaviour outside a gate's range (the constraints, not the generators, refuse such rows): BASE_SPLIT drops the bits of w[0] at
  * and above n_limbs * bits; U32_MUL_ADD takes the low 32 bits of an operand that is not a u32, and with a stride wider than 5 + 2 limbs
@@ -545,6 +551,7 @@ int sipp_plonk_prove_gates(sipp_ctx *ctx, const uint64_t *d_wires, const uint64_
 #define SIPP_GEN_REDUCING_EXT 13
 #define SIPP_GEN_QUOTIENT_EXT 14
 #define SIPP_GEN_BASE_SUM 15
+#define SIPP_GEN_POSEIDON_MDS 16
 typedef struct {
     uint32_t kind, selector_index, row;
     uint32_t p[5];

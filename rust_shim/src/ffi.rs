@@ -132,6 +132,8 @@ pub const SIPP_GEN_COSET_INTERPOLATION: u32 = 12;
 pub const SIPP_GEN_REDUCING_EXT: u32 = 13;
 pub const SIPP_GEN_QUOTIENT_EXT: u32 = 14;
 pub const SIPP_GEN_BASE_SUM: u32 = 15;
+/// SIPP_GEN_*: the Poseidon linear layer on twelve extension elements (p = in, out; two limbs per element)
+pub const SIPP_GEN_POSEIDON_MDS: u32 = 16;
 
 /// one gate family's witness generator with its layout (include/sipp_hip.h, "WITNESS GENERATORS"): kind = SIPP_GEN_*
 #[repr(C)]

@@ -1,17 +1,21 @@
 #!/usr/bin/env python3
 """Both halves of plonky2's verify through the outer prover (sipp_amd/plonk_vanishing.py PlonkProofVerifier) for an inner proof of the
 Poseidon kind at recursion-shaped parameters: the inner circuit is MerkleOpeningCircuit(16, 9, 4, 28) proved with
-sipp_amd.circuit.fri_params (blowup 8, cap height 4, arity 16, `queries` queries, 16 bits of proof of work).  Run by hand.  Every GPU
-step is a child process under its own `timeout`, the steps are chained, and nothing starts after a failure:
+sipp_amd.circuit.fri_params (blowup 8, cap height 4, arity 16, `queries` queries, 16 bits of proof of work).  The vanishing circuit is
+taken in its four VARIANTS in one interleaved run: today's (every inner gate from its monomials), the inner Poseidon gate through MDS
+rows (poseidon_mds), the closing Horner in chunks of 8 (alpha_chunk), and both.  Run by hand.  Every GPU step is a child process under
+its own `timeout`, the steps are chained, and nothing starts after a failure:
 
     inner     the device's inner proof; kept in a work file with its constants_sigmas cap and digest
-    witness   witness generation alone (sipp_plonk_generate_witness_levels) of both outer circuits, interleaved
-    prove     PlonkProofVerifier.prove_proof's two proofs and their verification, interleaved in one run; and for the vanishing
-              circuit sipp_circuit_prove_words against sipp_circuit_prove_inputs, interleaved
+    witness   witness generation alone (sipp_plonk_generate_witness_levels) of every variant's vanishing circuit and of the FRI
+              circuit, interleaved
+    prove     per variant PlonkProofVerifier.prove_proof's two proofs and their verification, the variants interleaved in one run; and
+              for today's vanishing circuit sipp_circuit_prove_words against sipp_circuit_prove_inputs, interleaved
 
-Prints one JSON line per step: the shapes (rows, levels, public and witness inputs of both circuits), then best, median and spread
-(max - min) of `reps`.  prove_words may be called faster than prove_inputs only where the difference exceeds the spread of
-prove_inputs' own repeats.  Needs the oracle for the Merkle tree and the public-input hash (tests/_oracle.py; built by build())."""
+Prints one JSON line per step: the shapes (rows, levels, public and witness inputs of the circuits), then best, median and spread
+(max - min) of `reps`.  One variant may be called faster than another, and prove_words faster than prove_inputs, only where the
+difference exceeds the spread of their repeats.  Needs the oracle for the Merkle tree and the public-input hash (tests/_oracle.py;
+built by build())."""
 import argparse
 import ctypes as C
 import json
@@ -30,6 +34,7 @@ sys.path.insert(0, ROOT)
 INNER_SHAPE = (16, 9, 4, 28)                                        # MerkleOpeningCircuit: leaf_len, height, cap_height, n_paths
 INNER_DIGEST = (21, 22, 23, 24)
 LIMITS = {"inner": 600, "witness": 600, "prove": 600}               # seconds, per step
+VARIANTS = {"monomials": {}, "mds": {"poseidon_mds": True}, "chunks": {"alpha_chunk": 8}, "mds_chunks": {"poseidon_mds": True, "alpha_chunk": 8}}
 
 
 def stats(v):
@@ -77,16 +82,22 @@ def inner(a):
 def circuits_of(a):
     from sipp_amd import plonk_vanishing as pv
     o = pickle.load(open(a.work, "rb"))
-    ver = pv.PlonkProofVerifier(None, o["log_n"], (80, 8, 2), o["circuit"], inner_fri(a, o["log_n"]), o["n_pi"], fri=(0, 0), verifier_data=[(0, (0,) * 4)] * 2)
-    return o, ver.vc, ver.fc
+    vcs, fc = {}, None
+    for name, kw in VARIANTS.items():
+        ver = pv.PlonkProofVerifier(None, o["log_n"], (80, 8, 2), o["circuit"], inner_fri(a, o["log_n"]), o["n_pi"], fri=(0, 0),
+                                    verifier_data=[(0, (0,) * 4)] * 2, **kw)
+        vcs[name], fc = ver.vc, ver.fc
+    return o, vcs, fc
 
 
 def describe(a):
-    o, vc, fc = circuits_of(a)
+    o, vcs, fc = circuits_of(a)
     line = {"step": "shape"}
-    for name, c in (("vanishing", vc), ("fri_proof", fc)):
+    for name, c in [("vanishing_" + v, vc) for v, vc in vcs.items()] + [("fri_proof", fc)]:
         line[name] = {"rows_used": c.rows_used, "log_n": c.log_n, "levels": c.n_levels, "public_inputs": c.n_pi, "witness_inputs": len(c.in_cycle)}
-    line["vanishing"].update({"arithmetic_ops": vc.ops.count, "arithmetic_rows": len(vc.ops.rows), "ops_per_inner_gate": vc.gate_ops})
+    for v, vc in vcs.items():
+        line["vanishing_" + v].update({"arithmetic_ops": vc.ops.count, "arithmetic_rows": len(vc.ops.rows), "mds_rows": len(vc.mds_rows),
+                                       "ops_per_inner_gate": vc.gate_ops})
     print(json.dumps(line))
 
 
@@ -106,17 +117,17 @@ def witness(a):
     import sipp_amd
     from sipp_amd._lib import to_device
     from tests import _oracle
-    o, vc, fc = circuits_of(a)
-    v_args, f_args = arguments(o, vc, fc)
+    o, vcs, fc = circuits_of(a)
+    v_args, f_args = arguments(o, vcs["monomials"], fc)             # the arguments do not depend on the variant
     ctx = sipp_amd.Ctx(workspace_bytes=2 << 30)
     runs = {}
-    for name, c, args, n_pub in (("vanishing", vc, v_args, 4), ("fri_proof", fc, f_args, 6)):
+    for name, c, args, n_pub in [("vanishing_" + v, vc, v_args, 4) for v, vc in vcs.items()] + [("fri_proof", fc, f_args, 6)]:
         pih = _oracle.hash_no_pad(np.array(c.public_inputs(*args[:n_pub]), dtype=np.uint64))
         runs[name] = (c, to_device(c.partial_witness(*args)), to_device(c.constants_sigmas()[:c.num_constants]),
                       sipp_amd.PlonkSchedule.from_dict(c.schedule()), pih)
     wit = {name: [] for name in runs}
     for _ in range(a.reps + 1):
-        for name, (c, d_w, d_k, sched, pih) in runs.items():       # interleaved: both circuits see the same clocks
+        for name, (c, d_w, d_k, sched, pih) in runs.items():       # interleaved: every circuit sees the same clocks
             ctx.plonk_generate_witness_levels(d_w, d_k, c.log_n, c.generators(), pih, sched)       # captures this circuit's graph
             t0 = time.perf_counter()
             ctx.plonk_generate_witness_levels(d_w, d_k, c.log_n, c.generators(), pih, sched)
@@ -129,25 +140,31 @@ def prove(a):
     import sipp_amd
     from sipp_amd import circuit as ci
     from sipp_amd import plonk_vanishing as pv
-    o, vc, fc = circuits_of(a)
+    o, vcs, fc = circuits_of(a)
     gp = sipp_amd.PlonkParams(80, 8, 2)
-    fris = (ci.fri_params(vc.log_n), ci.fri_params(fc.log_n))
-    ctxs = [ctx_for(c.log_n, gp, f, c.circuit()) for c, f in zip((vc, fc), fris)]
-    ver = pv.PlonkProofVerifier(ctxs[0], o["log_n"], (80, 8, 2), o["circuit"], inner_fri(a, o["log_n"]), o["n_pi"], fri_ctx=ctxs[1], fri=fris,
-                                outer_params=gp)
-    van = ver.vanishing
-    v_args, _ = arguments(o, vc, fc)
+    ctxs, vers = [], {}
+    for v, vc in vcs.items():                                       # one verifier per variant, each with its own two ctxs
+        fris = (ci.fri_params(vc.log_n), ci.fri_params(fc.log_n))
+        pair_ctxs = [ctx_for(c.log_n, gp, f, c.circuit()) for c, f in zip((vc, fc), fris)]
+        ctxs += pair_ctxs
+        vers[v] = pv.PlonkProofVerifier(pair_ctxs[0], o["log_n"], (80, 8, 2), o["circuit"], inner_fri(a, o["log_n"]), o["n_pi"],
+                                        fri_ctx=pair_ctxs[1], fri=fris, outer_params=gp, **VARIANTS[v])
+    van = vers["monomials"].vanishing
+    v_args, _ = arguments(o, vcs["monomials"], fc)
     cells, values = van.circ.input_cells(*v_args)
     pis = van.circ.public_inputs(*v_args)
-    t = {k: [] for k in ("prove_pair", "verify_pair", "prove_words", "prove_inputs")}
+    t = {k: [] for k in [x + "_" + v for v in vers for x in ("prove_pair", "verify_pair")] + ["prove_words", "prove_inputs"]}
+    words = {}
     for _ in range(a.reps + 1):
-        t0 = time.perf_counter()
-        pair = ver.prove_proof(o["proof"], o["cap"], INNER_DIGEST)
-        t["prove_pair"].append(time.perf_counter() - t0)
-        t0 = time.perf_counter()
-        got = ver.verify(pair, o["cap"], INNER_DIGEST)
-        t["verify_pair"].append(time.perf_counter() - t0)
-        assert got == [int(v) for v in o["proof"][len(o["proof"]) - o["n_pi"]:]]
+        for v, ver in vers.items():                                 # interleaved: every variant sees the same clocks
+            t0 = time.perf_counter()
+            pair = ver.prove_proof(o["proof"], o["cap"], INNER_DIGEST)
+            t["prove_pair_" + v].append(time.perf_counter() - t0)
+            t0 = time.perf_counter()
+            got = ver.verify(pair, o["cap"], INNER_DIGEST)
+            t["verify_pair_" + v].append(time.perf_counter() - t0)
+            assert got == [int(x) for x in o["proof"][len(o["proof"]) - o["n_pi"]:]]
+            words[v] = [int(len(p)) for p in pair]
         # the two entry points on the vanishing circuit, interleaved: both see the same clocks
         t0 = time.perf_counter()
         pf_w = van.prove_proof(o["proof"], INNER_DIGEST)
@@ -156,8 +173,9 @@ def prove(a):
         pf_i = van.data.prove_inputs(cells, values, pis)
         t["prove_inputs"].append(time.perf_counter() - t0)
         assert (pf_w == pf_i).all()
-    print(json.dumps({"step": "prove", **{k: stats(v) for k, v in t.items()}, "proof_words": [int(len(p)) for p in pair]}))
-    ver.close()
+    print(json.dumps({"step": "prove", **{k: stats(v) for k, v in t.items()}, "proof_words": words}))
+    for ver in vers.values():
+        ver.close()
     for ctx in ctxs:
         ctx.close()
 

@@ -27,6 +27,7 @@ UNUSED = 0xFFFFFFFF
 GEN_BASE_SPLIT, GEN_CONSTANT, GEN_PUBLIC_INPUT, GEN_RANDOM_ACCESS, GEN_REDUCING, GEN_POSEIDON_SWAP = 2, 3, 4, 6, 7, 9
 GEN_ARITHMETIC_EXT, GEN_EXPONENTIATION, GEN_COSET_INTERPOLATION, GEN_REDUCING_EXT, GEN_QUOTIENT_EXT = 10, 11, 12, 13, 14
 GEN_BASE_SUM = 15
+GEN_POSEIDON_MDS = 16
 # program factor kinds
 _W, _K, _PIH = 0, 1, 2
 # upstream's PoseidonGate layout (SIPP_GEN_POSEIDON_SWAP): 135 wires

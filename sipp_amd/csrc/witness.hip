@@ -20,6 +20,8 @@
 // FRI's initial combination (recalled gates/reducing_extension.rs, and gadgets/arithmetic_extension.rs div_add_extension with its
 // QuotientGeneratorExtension) adds SIPP_GEN_REDUCING_EXT, the reduction of extension coefficients, and SIPP_GEN_QUOTIENT_EXT, which fills
 // the multiplicand of an ArithmeticExtension-shaped row from its output: the one generator here that inverts.
+// The recursive evaluation of the Poseidon gate (recalled gates/poseidon_mds.rs) adds SIPP_GEN_POSEIDON_MDS, the linear layer on twelve
+// extension elements: a case of run_generator on one lane, wherever the row runs.
 #include "ctx.hpp"
 #include "poseidon_constants.h"
 #include <mutex>
@@ -115,6 +117,33 @@ __device__ __forceinline__ void poseidon_rounds(WireRef& W, uint64_t (&s)[12], u
     }
 #pragma unroll
     for (int l = 0; l < 12; l++) W(out + l) = s[l];
+}
+
+// SIPP_GEN_POSEIDON_MDS on row i: twelve extension elements, element c limb l at p + 2 c + l; M is over the base field, so each limb is one
+// product.  The limbs are field values, whatever word they hold (the exact half sums take any 64-bit word); the outputs are canonical.
+// Every kernel here inlines it, and mds() with its twelve outputs live cost the row-local kernel a wave per SIMD inlined (76 VGPRs) and
+// more out of line (102): so the outputs are taken ONE AT A TIME, in a loop the compiler must not unroll, the coefficients of row r read
+// from constant memory by a wave-uniform index (scalar loads).  The same exact half-product sum as mds(): the 24 written cells never
+// meet the 24 read ones (layout_ok), so an output is stored as soon as it is reduced.
+__device__ __forceinline__ void poseidon_mds_row(uint64_t* wires, uint32_t n, uint32_t i, uint32_t in, uint32_t out) {
+#pragma unroll 1
+    for (uint32_t l = 0; l < 2; l++) {
+        uint64_t s[12];
+#pragma unroll
+        for (int c = 0; c < 12; c++) s[c] = wires[(size_t)(in + 2 * c + l) * n + i];
+#pragma unroll 1
+        for (uint32_t r = 0; r < 12; r++) {
+            uint64_t al = 0, ah = 0;
+#pragma unroll
+            for (uint32_t c = 0; c < 12; c++) {
+                const uint32_t at = c + 12 - r, k = w_mds_circ[at >= 12 ? at - 12 : at] + ((r == 0 && c == 0) ? MDS_DIAG0 : 0);
+                al += (uint64_t)(uint32_t)s[c] * k;
+                ah += (s[c] >> 32) * k;
+            }
+            const uint64_t lo = al + (ah << 32);
+            wires[(size_t)(out + 2 * r + l) * n + i] = gl::reduce96((uint32_t)(ah >> 32) + (lo < al ? 1u : 0u), lo);
+        }
+    }
 }
 
 // one generator on one row
@@ -276,6 +305,9 @@ __device__ __forceinline__ void run_generator(uint64_t* wires, const uint64_t* c
         W(0) = acc;
         break;
     }
+    case SIPP_GEN_POSEIDON_MDS:
+        poseidon_mds_row(wires, n, i, g.p[0], g.p[1]);
+        break;
     default: break;
     }
 }
@@ -429,7 +461,7 @@ __device__ __forceinline__ CoopRow coop_row(const uint32_t* rows, uint32_t count
 // the 30 rounds on the sixteen lanes of row i, the one copy both kernels below run (all lanes of the block call it; act = the row is a
 // Poseidon row and l < 12): lane l starts from s, state element l behind the row's prelude, and stores its S-box inputs (the wires of
 // poseidon_rounds) and its output; lanes 12 .. 15 shadow element 0 and never store.  sh: the block's LDS tile, twelve words per group.
-// The exact half-product sum is written here and in mds(), nowhere else: one helper for both changed mds()'s register allocation.
+// The exact half-product sum is written here, in mds() and in poseidon_mds_row(): one helper for all changed mds()'s register allocation.
 __device__ __forceinline__ void poseidon_lanes(uint64_t* wires, uint32_t n, uint32_t i, uint32_t grp, uint32_t l, bool act, uint64_t s,
                                                uint32_t out, uint32_t sb, uint64_t (&sh)[4][12]) {
     const uint32_t e = l < 12 ? l : 0;
@@ -568,6 +600,10 @@ bool layout_ok(const sipp_plonk_generator& g, uint32_t num_wires, uint32_t num_c
     }
     case SIPP_GEN_REDUCING_EXT: return g.p[0] >= 1 && 4ull + 4ull * g.p[0] <= nw && g.p[1] != 0;
     case SIPP_GEN_QUOTIENT_EXT: return g.p[0] >= 1 && 8ull * g.p[0] <= nw && g.p[1] < num_constants && g.p[2] < num_constants && g.p[3] != 0;
+    case SIPP_GEN_POSEIDON_MDS: {
+        const uint64_t in = g.p[0], out = g.p[1];
+        return in + 24 <= nw && out + 24 <= nw && (in + 24 <= out || out + 24 <= in);
+    }
     case SIPP_GEN_POSEIDON_SWAP: {
         // written cells (out, sbox, delta) must not meet the read cells (in, swap): the two launch paths read and write in different orders
         const uint64_t in = g.p[0], out = g.p[1], sb = g.p[2], sw = g.p[3], dl = g.p[4];
@@ -586,8 +622,8 @@ const char* gen_name(uint32_t kind) {
     static const char* names[] = {"", "witness_arithmetic", "witness_base_split", "witness_constant", "witness_public_input", "witness_u32",
                                   "witness_random_access", "witness_reducing", "witness_poseidon", "witness_poseidon_swap",
                                   "witness_arithmetic_ext", "witness_exponentiation", "witness_coset_interpolation",
-                                  "witness_reducing_ext", "witness_quotient_ext", "witness_base_sum"};
-    return kind <= SIPP_GEN_BASE_SUM ? names[kind] : "witness";
+                                  "witness_reducing_ext", "witness_quotient_ext", "witness_base_sum", "witness_poseidon_mds"};
+    return kind <= SIPP_GEN_POSEIDON_MDS ? names[kind] : "witness";
 }
 
 }  // namespace

@@ -4,6 +4,8 @@ a commitment against its cap (what the recursive verifier does for every FRI que
   poseidon_swap_gate()      the 123 constraints of upstream's PoseidonGate (gates/poseidon.rs, recalled) in the program words of
                             sipp_plonk_circuit (include/sipp_hip.h, "gates as data"), upstream's order and sign
   declare_swap_gate()       that gate in a circuit's gate set, in SWAP_LAYOUT (every circuit hashes its public inputs with it)
+  poseidon_mds_gate()       upstream's PoseidonMdsGate (gates/poseidon_mds.rs, recalled): the linear layer on twelve extension elements, 24
+                            constraints of degree 1; declare_mds_gate() puts it into a gate set (sipp_amd/plonk_vanishing.py's route)
   opening_into()            the wiring of one opening on any builder, its leaf, index bits and cap given as sources: this circuit's
                             paths and those of sipp_amd/fri_verifier.py
   MerkleOpeningCircuit      the statement "for each path k, leaves[k] sits at index idx[k] of the tree whose cap is `cap`" as calls of
@@ -24,8 +26,8 @@ import os
 import numpy as np
 
 from .circuit import SWAP_LAYOUT, fri_params  # noqa: F401 (used from here by tests and scripts)
-from .circuit import (BASE_SUM, GEN_POSEIDON_SWAP, GEN_RANDOM_ACCESS, P, PUBLIC_INPUT, CircuitBuilder, CircuitProver, _Prog, _W, pi,
-                      random_access_into)
+from .circuit import (BASE_SUM, GEN_POSEIDON_MDS, GEN_POSEIDON_SWAP, GEN_RANDOM_ACCESS, P, PUBLIC_INPUT, CircuitBuilder, CircuitProver, _Prog,
+                      _W, pi, random_access_into)
 
 GATE_NAMES = ["Noop", "PublicInput", "Constant", "BaseSum", "RandomAccess", "PoseidonSwap"]
 GATE_GROUP = (0, 0, 0, 0, 1, 2)                 # RandomAccess (degree cap_height + 1) and PoseidonSwap (degree 7) alone in their groups
@@ -130,6 +132,29 @@ def declare_swap_gate(b, index):
     """the swap gate as gate `index` of builder b, in SWAP_LAYOUT"""
     b.declare(index, 7, (GEN_POSEIDON_SWAP, b.s_in, b.s_out, b.s_sbox, b.s_swap, b.s_delta), swap_gate_into, b.s_in, b.s_out, b.s_swap,
               b.s_delta, b.s_sbox)
+
+
+def mds_gate_into(pr, in_, out):
+    _, MDS = poseidon_tables()
+    for r in range(12):
+        for l in range(2):
+            pr.constraint([(MDS[r][c], [(_W, in_ + 2 * c + l)]) for c in range(12)] + [(-1, [(_W, out + 2 * r + l)])])
+
+
+def poseidon_mds_gate(in_=0, out=24):
+    """upstream PoseidonMdsGate's constraints as program words (np.int64): twelve extension elements, element c limb l at in_ + 2 c + l,
+    and their image under the permutation's MDS matrix at out + 2 r + l -- 24 constraints of degree 1, constraint 2 r + l =
+    sum_c M[r][c] in[2 c + l] - out[2 r + l]  (the matrix is over the base field: the limbs do not mix)"""
+    pr = _Prog()
+    mds_gate_into(pr, in_, out)
+    assert pr.count == 24
+    return np.array(pr.words, dtype=np.int64)
+
+
+def declare_mds_gate(b, index, in_=0, out=24):
+    """the MDS gate as gate `index` of builder b (SIPP_GEN_POSEIDON_MDS): all 48 cells are routed"""
+    assert in_ + 24 <= b.num_routed and out + 24 <= b.num_routed and (in_ + 24 <= out or out + 24 <= in_)
+    b.declare(index, 1, (GEN_POSEIDON_MDS, in_, out), mds_gate_into, in_, out)
 
 
 def opening_into(b, ra_shape, swap_gate, zero, leaf, swap_bits, index, cap_word, cap_bits=None, sibling=None):

@@ -20,24 +20,37 @@ Rows.  An op is written down when it is asked for and placed later (_Ops.flush):
 those that read them, and so on; within one such round ops with equal (c0, c1) share rows, num_routed // 8 to a row.  place() derives
 every level from the sources.
 
+The Poseidon gate through MDS rows (poseidon_mds=True).  The inner gate whose program words are merkle.poseidon_swap_gate() at
+SWAP_LAYOUT is not compiled from its 5365 monomials: its 123 constraint values, the same field elements in the same order, come from
+walking the permutation on the opened wires (_poseidon_constraints), the linear layers as rows of a PoseidonMds gate (plonky2's
+PoseidonMdsGate; SIPP_GEN_POSEIDON_MDS) that joins the two extension gates' selector group: 30 rows, of which only the 22 partial
+rounds' chain.  alpha_chunk=K cuts the closing Horner in alpha, the longest chain left, into chunks of K terms and runs Horner in
+alpha^K over the chunk sums.  Both are part of the circuit's shape; the defaults build the circuit that was built without them.
+
 Public inputs = the inner circuit digest (4) || the inner public inputs || the wires, Z and quotient caps || the opened values in the
 proof's order (constants, sigmas, wires, Z and partial products, quotient chunks, then Z at g zeta), each (c0, c1) || zeta (2) ||
 g zeta (2) || the departing sponge state (12).  The last 16 are generated cells: the partial witness does not set them, the prover
 passes their values (transcript(), by the library's host permutation) as public inputs.
 
-Refused at build: no inner public input, more than 8 challenges, a max_degree that is no power of two, a gate set circuit_ok refuses.
+Refused at build: no inner public input, more than 8 challenges, a max_degree that is no power of two, a gate set circuit_ok refuses,
+poseidon_mds without an inner gate of exactly that program, an alpha_chunk below 2.
 
 numpy only; imports nothing from the test oracle."""
 import numpy as np
 
-from .circuit import (GEN_ARITHMETIC_EXT, GEN_QUOTIENT_EXT, P, PUBLIC_INPUT, UNUSED, CircuitBuilder, CircuitProver, _Challenger, _root_of_unity,
-                      pi)
+from .circuit import (GEN_ARITHMETIC_EXT, GEN_QUOTIENT_EXT, P, PUBLIC_INPUT, SWAP_LAYOUT, UNUSED, CircuitBuilder, CircuitProver, _Challenger,
+                      _root_of_unity, pi)
 from .fri_fold import EXT_W, arithmetic_ext_into
-from .merkle import declare_swap_gate
+from .merkle import declare_mds_gate, declare_swap_gate, poseidon_swap_gate, poseidon_tables, sbox_wire
 
 GATE_NAMES = ["Noop", "PublicInput", "Constant", "BaseSum", "ArithmeticExt", "QuotientExt", "PoseidonSwap"]
 GATE_GROUP = (0, 0, 0, 0, 1, 1, 2)
 ARITHMETIC_EXT, QUOTIENT_EXT, POSEIDON_SWAP = 4, 5, 6
+# with poseidon_mds the gate set gains PoseidonMds in the group of the two extension gates; PoseidonSwap moves up by one
+MDS_GATE_NAMES = GATE_NAMES[:6] + ["PoseidonMds", "PoseidonSwap"]
+MDS_GATE_GROUP = (0, 0, 0, 0, 1, 1, 1, 2)
+POSEIDON_MDS = 6
+MDS_IN, MDS_OUT = 0, 24                                         # the MDS rows' layout: 24 cells in, 24 cells out, all routed
 HEADER_WORDS, FRI_HEADER_WORDS = 16, 8                          # of the flat "SIPPPLK3" proof and of its opening section
 
 
@@ -87,33 +100,70 @@ def gate_constraints(circ, gate):
     return out
 
 
+def gate_words(circ, gate):
+    """the program words of one gate, by walking them (circuit_ok has accepted the circuit)"""
+    prog, (_, _, _, _, off, ncons) = circ["programs"], circ["gates"][gate]
+    w = off
+    for _ in range(ncons):
+        nm, w = int(prog[w]), w + 1
+        for _ in range(nm):
+            w += 2 + 2 * int(prog[w + 1])
+    return np.asarray(prog[off:w], dtype=np.int64)
+
+
 class _V:
-    """an extension value: a pair of sources once it is placed (src), the op that makes it until then"""
+    """an extension value: a pair of sources once it is placed (src), the op that makes it until then (an ArithmeticExtension op's
+    tuple, or ("mds", row) for an output of a PoseidonMds row)"""
     __slots__ = ("src", "op", "depth")
 
     def __init__(self, src=None, op=None, depth=0):
         self.src, self.op, self.depth = src, op, depth
 
 
+class _Mds:
+    """a PoseidonMds row until it is placed: twelve values in, twelve out"""
+    __slots__ = ("ins", "outs", "depth")
+
+    def __init__(self, ins):
+        self.ins, self.outs, self.depth = list(ins), [], 0
+
+
 class _Ops:
-    """ArithmeticExtension ops of a builder, written down first and placed in rounds (the module's note on rows)"""
+    """ArithmeticExtension ops of a builder, written down first and placed in rounds (the module's note on rows); with mds_gate also
+    PoseidonMds rows, each a row of its own one round behind its latest operand"""
 
     SLACK = 0                                                   # rounds an op may wait for a row of its constants: 0 keeps every op at its depth
 
-    def __init__(self, b, gate, n_ops):
+    def __init__(self, b, gate, n_ops, mds_gate=None):
         self.b, self.gate, self.n_ops, self.pending, self.rows, self.count = b, gate, n_ops, [], [], 0
+        self.mds_gate, self.mds_rows, self.made = mds_gate, [], 0
 
     def op(self, c0, c1, a, m, c=None):
         """c0 a m + c1 c"""
         v = _V(op=(c0 % P, c1 % P, a, m, c))
         self.pending.append(v)
+        self.made += 1
         return v
+
+    def mds(self, ins):
+        """M ins, element by element: the twelve outputs of a PoseidonMds row"""
+        row = _Mds(ins)
+        assert self.mds_gate is not None and len(row.ins) == 12
+        row.outs = [_V(op=("mds", row)) for _ in range(12)]
+        self.pending.append(row)
+        return list(row.outs)
 
     def flush(self):
         """rounds: an op goes behind its operands, and into a row of its constants that still has room there or later (within SLACK
         rounds: waiting packs the rows, and delays only what reads the op), else into a new row at its earliest round"""
         b, rounds, open_rows = self.b, {}, {}
         for v in self.pending:                                  # in the order of their making: operands first
+            if isinstance(v, _Mds):
+                v.depth = 1 + max((x.depth for x in v.ins if x.op is not None), default=0)
+                for o in v.outs:
+                    o.depth = v.depth
+                rounds.setdefault(v.depth, []).append(v)
+                continue
             first = 1 + max((x.depth for x in v.op[2:] if x is not None and x.op is not None), default=0)
             slots = open_rows.setdefault(v.op[:2], {})
             at = min((r for r, row in slots.items() if first <= r <= first + self.SLACK and len(row) < self.n_ops), default=None)
@@ -125,6 +175,13 @@ class _Ops:
             v.depth = at
         for at in sorted(rounds):
             for vs in rounds[at]:
+                if isinstance(vs, _Mds):
+                    r = b.new_row(self.mds_gate)
+                    b.place(r, [(MDS_IN + 2 * k + l, x.src[l]) for k, x in enumerate(vs.ins) for l in range(2)])
+                    for k, o in enumerate(vs.outs):
+                        o.src = ((MDS_OUT + 2 * k, r), (MDS_OUT + 2 * k + 1, r))
+                    self.mds_rows.append(r)
+                    continue
                 c0, c1 = vs[0].op[:2]
                 r = b.new_row(self.gate, c0, c1)
                 feeds = []
@@ -138,7 +195,8 @@ class _Ops:
                 self.rows.append(r)
                 self.count += len(vs)
         for v in self.pending:                                  # placed: leaves of whatever comes next
-            v.op, v.depth = None, 0
+            for x in (v.outs if isinstance(v, _Mds) else (v,)):
+                x.op, x.depth = None, 0
         self.pending = []
 
 
@@ -182,7 +240,13 @@ class PlonkVanishingCircuit(CircuitBuilder):
     CircuitBuilder.circuit()) and n_pi_inner describe the INNER circuit; cap_height is its proofs'.  Cells are wire * N + row."""
     n_public_args = 4
 
-    def __init__(self, log_n, params, circuit, cap_height, n_pi_inner, num_wires=135, num_routed=80, min_log_n=10):
+    def __init__(self, log_n, params, circuit, cap_height, n_pi_inner, num_wires=135, num_routed=80, min_log_n=10, poseidon_mds=False,
+                 alpha_chunk=None):
+        """poseidon_mds: the inner gate whose program is merkle.poseidon_swap_gate() at SWAP_LAYOUT, word for word, is evaluated
+        numerically through PoseidonMds rows (_poseidon_constraints) instead of from its monomials; refused if there is none.
+        alpha_chunk = K >= 2: the closing Horner in alpha runs inside chunks of K terms, then in alpha^K over the chunk sums"""
+        assert alpha_chunk is None or (isinstance(alpha_chunk, int) and alpha_chunk >= 2), "alpha_chunk must be an int of at least 2"
+        self.poseidon_mds, self.alpha_chunk = bool(poseidon_mds), alpha_chunk
         R, D, C = ((params.num_routed_wires, params.max_degree, params.num_challenges) if hasattr(params, "max_degree") else
                    tuple(int(x) for x in params))
         assert n_pi_inner > 0, "an inner proof without public inputs has no public-input hash to build"
@@ -208,12 +272,22 @@ class PlonkVanishingCircuit(CircuitBuilder):
         self.pi_gzeta, self.pi_state = self.pi_zeta + 2, self.pi_zeta + 4
         self.n_ops = num_routed // 8
         assert self.n_ops >= 1 and 25 <= num_routed
-        CircuitBuilder.__init__(self, num_wires, num_routed, GATE_NAMES, GATE_GROUP, 2, self.pi_state + 12)
+        self.routed_gates = []
+        if self.poseidon_mds:
+            want = poseidon_swap_gate(**SWAP_LAYOUT)
+            self.routed_gates = [g for g, gate in enumerate(circuit["gates"]) if gate[5] == 123 and np.array_equal(gate_words(circuit, g), want)]
+            assert self.routed_gates, "poseidon_mds: no inner gate's program is the Poseidon swap gate's at SWAP_LAYOUT"
+            assert MDS_OUT + 24 <= num_routed
+        self.mds_gate, self.swap_gate = (POSEIDON_MDS, POSEIDON_MDS + 1) if self.poseidon_mds else (None, POSEIDON_SWAP)
+        names, group = (MDS_GATE_NAMES, MDS_GATE_GROUP) if self.poseidon_mds else (GATE_NAMES, GATE_GROUP)
+        CircuitBuilder.__init__(self, num_wires, num_routed, names, group, 2, self.pi_state + 12)
         self.declare_basic(1)
         self.declare(ARITHMETIC_EXT, 3, (GEN_ARITHMETIC_EXT, self.n_ops, self.k0, self.k1, EXT_W), arithmetic_ext_into, self.n_ops, self.k0,
                      self.k1, EXT_W)
         self.declare(QUOTIENT_EXT, 3, (GEN_QUOTIENT_EXT, 1, self.k0, self.k1, EXT_W), arithmetic_ext_into, 1, self.k0, self.k1, EXT_W)
-        declare_swap_gate(self, POSEIDON_SWAP)
+        if self.poseidon_mds:
+            declare_mds_gate(self, self.mds_gate, MDS_IN, MDS_OUT)
+        declare_swap_gate(self, self.swap_gate)
         self._wiring()
         self.finish(min_log_n)
 
@@ -230,9 +304,9 @@ class PlonkVanishingCircuit(CircuitBuilder):
         ZERO, ONE = _V(src=(zero, zero)), _V(src=(one, zero))
         base = lambda s: _V(src=(s, zero))
         # the public-input hash and the transcript
-        self.pih_row = self.hash_rows(POSEIDON_SWAP, zero, [pi(self.pi_inner + t) for t in range(self.n_pi_inner)])
+        self.pih_row = self.hash_rows(self.swap_gate, zero, [pi(self.pi_inner + t) for t in range(self.n_pi_inner)])
         self.pih_cells = pih = [(self.s_out + t, self.pih_row[-1]) for t in range(4)]
-        ch = _Challenger(self, POSEIDON_SWAP, zero, [zero] * 12, [])
+        ch = _Challenger(self, self.swap_gate, zero, [zero] * 12, [])
         for t in range(4):
             ch.observe(pi(self.pi_digest + t))
         for s in pih:
@@ -259,7 +333,7 @@ class PlonkVanishingCircuit(CircuitBuilder):
         pps = [self._opened(K + R + W + C + k) for k in range(C * np_)]
         qs = [self._opened(K + R + W + self.nz + k) for k in range(C * D)]
         zs_next = [self._opened(self.n0 + c) for c in range(C)]
-        ops = self.ops = _Ops(self, ARITHMETIC_EXT, self.n_ops)
+        ops = self.ops = _Ops(self, ARITHMETIC_EXT, self.n_ops, self.mds_gate)
         mul = lambda a, b: ops.op(1, 0, a, b)
         add = lambda a, b: ops.op(1, 1, a, ONE, b)
         sub = lambda a, b: ops.op(1, -1, a, ONE, b)
@@ -289,17 +363,35 @@ class PlonkVanishingCircuit(CircuitBuilder):
                     den = mul(den, ops.op(1, 1, sg[j], beta[c], wg[j]))
                 terms.append(sub(num, den))
         terms += self._gate_terms(ops, cv, wv, [base(s) for s in pih], ZERO, ONE)
-        # per challenge: Horner in alpha over the terms (last first) against Z_H times Horner in zeta^n over the quotient chunks
+        # per challenge: Horner in alpha over the terms (last first) against Z_H times Horner in zeta^n over the quotient chunks; with
+        # alpha_chunk = K the same sum as Horner inside chunks of K terms, then Horner in alpha^K over the chunk sums
+        def horner(ts, x):
+            acc = ts[-1]
+            for t in ts[-2::-1]:
+                acc = ops.op(1, 1, acc, x, t)
+            return acc
+
+        def power(x, e):
+            """x^e, e >= 2, by squaring from the top bit"""
+            acc = x
+            for bit in bin(e)[3:]:
+                acc = mul(acc, acc)
+                if bit == "1":
+                    acc = mul(acc, x)
+            return acc
         sides = []
         for c in range(C):
-            van = terms[-1]
-            for t in terms[-2::-1]:
-                van = ops.op(1, 1, van, alpha[c], t)
+            if self.alpha_chunk is None:
+                van = horner(terms, alpha[c])
+            else:
+                sums = [horner(terms[at:at + self.alpha_chunk], alpha[c]) for at in range(0, len(terms), self.alpha_chunk)]
+                van = sums[0] if len(sums) == 1 else horner(sums, power(alpha[c], self.alpha_chunk))
             acc = qs[c * D + D - 1]
             for d in range(D - 2, -1, -1):
                 acc = ops.op(1, 1, acc, zeta_n, qs[c * D + d])
             sides.append((van, mul(zh, acc)))
         ops.flush()
+        self.mds_rows = list(ops.mds_rows)
         self.term_cells = [t.src for t in terms]
         self.side_cells = [(a.src, b.src) for a, b in sides]
         for a, b in self.side_cells:
@@ -307,7 +399,7 @@ class PlonkVanishingCircuit(CircuitBuilder):
                 self.tie(a[l], b[l])
         # the outputs, public: the chain that hashes the public inputs reads them from the cells that hold them
         outs = list(self.zeta_cells) + list(self.gzeta_cells) + self.state_cells
-        self.chain_row = self.hash_rows(POSEIDON_SWAP, zero, [pi(t) for t in range(self.pi_zeta)] + outs)
+        self.chain_row = self.hash_rows(self.swap_gate, zero, [pi(t) for t in range(self.pi_zeta)] + outs)
         for k, s in enumerate(outs):
             self.public_input(self.pi_zeta + k, s)
         for t in range(4):
@@ -326,7 +418,7 @@ class PlonkVanishingCircuit(CircuitBuilder):
             return products[key]
         gt = [None] * self.ngc
         for g, (sel, row, lo, hi, _, ncons) in enumerate(circ["gates"]):
-            before = len(ops.pending)
+            before = ops.made
             f = None
             for i in list(range(lo, hi)) + ([UNUSED] if circ["num_selectors"] > 1 else []):
                 if i == row:
@@ -337,18 +429,57 @@ class PlonkVanishingCircuit(CircuitBuilder):
             filters.append(f)
             cons = gate_constraints(circ, g)
             self.gate_monomials.append(len({key for monos in cons for _, key in monos}))
+            values = self._poseidon_constraints(ops, wv, ONE) if g in self.routed_gates else None
             for j, monos in enumerate(cons):
                 acc = None
-                for coef, key in monos:
-                    acc = ops.op(coef, 0 if acc is None else 1, product(key), ONE, acc)
+                if values is not None:
+                    acc = values[j]
+                else:
+                    for coef, key in monos:
+                        acc = ops.op(coef, 0 if acc is None else 1, product(key), ONE, acc)
                 if acc is None:
                     continue                                                         # an empty constraint adds nothing
                 if f is None:
                     gt[j] = acc if gt[j] is None else ops.op(1, 1, acc, ONE, gt[j])
                 else:
                     gt[j] = ops.op(1, 0 if gt[j] is None else 1, f, acc, gt[j])
-            self.gate_ops.append(len(ops.pending) - before)
+            self.gate_ops.append(ops.made - before)
         return [ZERO if t is None else t for t in gt]
+
+    def _poseidon_constraints(self, ops, wv, ONE):
+        """the 123 constraint values of the Poseidon swap gate at SWAP_LAYOUT, in the program's order, by walking the permutation on the
+        opened wires: swap and deltas, the swapped inputs, then the rounds.  Every S-box input but round 0's is an opened wire, so every
+        w^7 is there early and a full round's PoseidonMds row reads nothing another row writes; only the 22 partial rounds chain,
+        elements 1 .. 11 passing from one row's outputs to the next row's inputs.  The round constants stay off the cells: the state is
+        cells + k with k a host-side vector of base-field constants, k <- M k behind an MDS row, and cell + k - wire is made only
+        where an element meets a constraint (one op with constants of its own each)"""
+        RC, MDS = poseidon_tables()
+        lay = SWAP_LAYOUT
+        in_, out, sw, delta = [wv[lay["in_"] + i] for i in range(12)], [wv[lay["out"] + i] for i in range(12)], wv[lay["swap"]], lay["delta"]
+        mul = lambda a, b: ops.op(1, 0, a, b)
+        sub = lambda a, b: ops.op(1, -1, a, ONE, b)
+
+        def pow7(x):
+            x2 = mul(x, x)
+            return mul(mul(x2, x2), mul(x2, x))
+        values = [ops.op(1, -1, sw, sw, sw)]                                       # swap (swap - 1)
+        values += [ops.op(1, -1, sw, sub(in_[4 + i], in_[i]), wv[delta + i]) for i in range(4)]
+        # round 0 on the swapped inputs (in_i + delta_i, in_(4+i) - delta_i, in_8 .. in_11), its constants added on the cells
+        swapped = [ops.op(1, 1, in_[i], ONE, wv[delta + i]) for i in range(4)] + [sub(in_[4 + i], wv[delta + i]) for i in range(4)] + in_[8:]
+        state = ops.mds([pow7(ops.op(RC[i], 1, ONE, ONE, swapped[i])) for i in range(12)])
+        k = [0] * 12
+        met = lambda cell, kk, wire: ops.op(kk, 1, ONE, ONE, sub(cell, wire))      # cell + k - wire
+        for rnd in range(1, 30):
+            k = [(k[i] + RC[12 * rnd + i]) % P for i in range(12)]
+            for i in (range(12) if rnd < 4 or rnd >= 26 else (0,)):
+                w = wv[sbox_wire(lay["sbox"], rnd, i)]
+                values.append(met(state[i], k[i], w))
+                state[i], k[i] = pow7(w), 0
+            state = ops.mds(state)
+            k = [sum(MDS[r][c] * k[c] for c in range(12)) % P for r in range(12)]
+        values += [met(state[i], k[i], out[i]) for i in range(12)]
+        assert len(values) == 123
+        return values
 
     # ---- the values ----
     def _check(self, digest, inner_pis, caps, opened):
@@ -466,8 +597,10 @@ class PlonkProofVerifier:
     and digest are the OUTER proofs'."""
 
     def __init__(self, ctx, log_n, params, circuit, inner_fri, n_pi_inner, fri_ctx=None, fri=None, outer_params=None, digest=None, min_log_n=10,
-                 verifier_data=None):
-        """ctx = None builds the verifying half alone (no device): verifier_data = per outer circuit its (constants_sigmas cap, digest),
+                 verifier_data=None, poseidon_mds=False, alpha_chunk=None):
+        """poseidon_mds, alpha_chunk: the vanishing circuit's; they are part of the verifier's shape (another setting is another circuit,
+        with another constants_sigmas cap).
+        ctx = None builds the verifying half alone (no device): verifier_data = per outer circuit its (constants_sigmas cap, digest),
         fri and outer_params as the provers had them"""
         from . import _lib
         from .fri_proof import FriProofCircuit, FriProofProver
@@ -478,6 +611,7 @@ class PlonkProofVerifier:
         n0, z0 = K + R + W + C * m + C * D, K + R + W
         arity = [int(inner_fri.arity_bits[r]) for r in range(inner_fri.n_rounds)]
         v_shape = (log_n, (R, D, C), circuit, cap_height, n_pi_inner)
+        v_kw = dict(min_log_n=min_log_n, poseidon_mds=poseidon_mds, alpha_chunk=alpha_chunk)
         f_shape = (log_n + inner_fri.rate_bits, cap_height, [K + R, W, C * m, C * D], [list(range(n0)), list(range(z0, z0 + C))], arity,
                    inner_fri.n_rounds, (1 << log_n) >> sum(arity), inner_fri.num_queries)
         f_kw = dict(min_log_n=min_log_n, pow_bits=inner_fri.pow_bits, pow_rule=inner_fri.pow_rule, n_in=0)
@@ -485,12 +619,12 @@ class PlonkProofVerifier:
         fri = (None, None) if fri is None else tuple(fri)
         if ctx is None:
             assert verifier_data is not None and None not in fri
-            self.vc, self.fc = PlonkVanishingCircuit(*v_shape, min_log_n=min_log_n), FriProofCircuit(*f_shape, **f_kw)
+            self.vc, self.fc = PlonkVanishingCircuit(*v_shape, **v_kw), FriProofCircuit(*f_shape, **f_kw)
             self.verifier_data = [(np.asarray(cap, dtype=np.uint64).reshape(-1), np.array([int(x) for x in dg], dtype=np.uint64))
                                   for cap, dg in verifier_data]
             self.outer_fri = fri
         else:
-            self.vanishing = PlonkVanishingProver(ctx, *v_shape, fri=fri[0], params=outer_params, digest=digest, min_log_n=min_log_n)
+            self.vanishing = PlonkVanishingProver(ctx, *v_shape, fri=fri[0], params=outer_params, digest=digest, **v_kw)
             try:
                 self.fri = FriProofProver(fri_ctx or ctx, *f_shape, fri=fri[1], params=outer_params, digest=digest, **f_kw)
             except Exception:

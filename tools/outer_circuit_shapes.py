@@ -3,6 +3,7 @@
 a circuit hands to the prover, for the shapes and inputs of tests/test_outer_circuit_pinned.py, which imports digests() from here.
 
     python tools/outer_circuit_shapes.py        # writes tests/golden/outer_circuit_shapes.json
+    python tools/outer_circuit_shapes.py --mds  # writes tests/golden/plonk_vanishing_mds_shapes.json (tests/test_plonk_vanishing_mds.py)
 
 Regenerate only when a circuit is meant to change, and say which entries moved and why."""
 import hashlib
@@ -14,6 +15,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PATH = os.path.join(ROOT, "tests", "golden", "outer_circuit_shapes.json")
+MDS_PATH = os.path.join(ROOT, "tests", "golden", "plonk_vanishing_mds_shapes.json")
 
 
 def _sha(*parts):
@@ -58,7 +60,18 @@ def digests(c, witness_args, public_args, sigma_rows=True):
     return out
 
 
+def main_mds():
+    """the vanishing circuit's routed shapes (poseidon_mds, alpha_chunk) of tests/test_plonk_vanishing_mds.py, each with its counts"""
+    sys.path.insert(0, ROOT)
+    from tests import test_plonk_vanishing_mds as t
+    out = {name: t.shape_digests(name) for name in t.PINNED}
+    json.dump(out, open(MDS_PATH, "w"), indent=1, sort_keys=True)
+    print("%d shapes -> %s" % (len(out), MDS_PATH))
+
+
 def main():
+    if "--mds" in sys.argv[1:]:
+        return main_mds()
     sys.path.insert(0, ROOT)
     from tests import test_outer_circuit_pinned as t
     out = {t.name(kind, shape): t.shape_digests(kind, shape) for kind, shape in t.SHAPES}
