@@ -565,7 +565,11 @@ int sipp_plonk_generate_witness(sipp_ctx *ctx, uint64_t *d_wires, const uint64_t
  * d_wires[d_copy_dst[k]] = d_wires[d_copy_src[k]] for k in [copy_offsets[l], copy_offsets[l + 1]).  Two small launches per level: the
  * sequence is captured once as a hipGraph per ctx and replayed while the arguments stay the same (SIPP_ROUTE_WITNESS_NO_GRAPH, or an
  * enabled profile, launches them one by one).  d_rows / d_copy_* are device arrays, the offsets host arrays of n_levels + 1 entries.
- * SIPP_E_BADARG also for a row or cell outside the table (checked on the device, reported after the last level). */
+ * SIPP_E_BADARG also for a row or cell outside the table (checked on the device, reported after the last level).
+ * n_gens is at most 32 here (the row-local call above has no limit): the generators travel in the level kernels' arguments, a circuit of
+ * up to 16 in the 16-entry struct and kernels it always had, one of 17 .. 32 in a 32-entry struct and the wide instantiation of the
+ * same kernels.  More than 32: SIPP_E_BADARG, decided on the host before anything is launched or uploaded; the ctx stays usable.
+ * sipp_circuit_build refuses such a circuit when it is given a schedule. */
 typedef struct {
     uint32_t n_levels;
     const uint32_t *d_rows;

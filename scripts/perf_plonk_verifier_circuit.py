@@ -3,7 +3,9 @@
 Poseidon kind at recursion-shaped parameters: the inner circuit is MerkleOpeningCircuit(16, 9, 4, 28) proved with
 sipp_amd.circuit.fri_params (blowup 8, cap height 4, arity 16, `queries` queries, 16 bits of proof of work).  The vanishing circuit is
 taken in its four VARIANTS in one interleaved run: today's (every inner gate from its monomials), the inner Poseidon gate through MDS
-rows (poseidon_mds), the closing Horner in chunks of 8 (alpha_chunk), and both.  Run by hand.  Every GPU step is a child process under
+rows (poseidon_mds), the closing Horner in chunks of 8 (alpha_chunk), and both.  Beside the pair stands the ONE-circuit verifier
+(sipp_amd/plonk_verifier.py PlonkVerifierCircuit, with poseidon_mds and alpha_chunk = 8: 17 generators), in the same interleaved runs:
+its witness generation, PlonkVerifierProver.prove_proof and verify.  Run by hand.  Every GPU step is a child process under
 its own `timeout`, the steps are chained, and nothing starts after a failure:
 
     inner     the device's inner proof; kept in a work file with its constants_sigmas cap and digest
@@ -90,11 +92,21 @@ def circuits_of(a):
     return o, vcs, fc
 
 
+JOINED = {"poseidon_mds": True, "alpha_chunk": 8}                   # the one-circuit verifier's variant: the one that fits the small table
+
+
+def joined_shape(a, o):
+    return (o["log_n"], (80, 8, 2), o["circuit"], inner_fri(a, o["log_n"]), o["n_pi"])
+
+
 def describe(a):
+    from sipp_amd import plonk_verifier as pj
     o, vcs, fc = circuits_of(a)
+    jc = pj.PlonkVerifierCircuit(*joined_shape(a, o), **JOINED)
     line = {"step": "shape"}
-    for name, c in [("vanishing_" + v, vc) for v, vc in vcs.items()] + [("fri_proof", fc)]:
+    for name, c in [("vanishing_" + v, vc) for v, vc in vcs.items()] + [("fri_proof", fc), ("verifier_joined", jc)]:
         line[name] = {"rows_used": c.rows_used, "log_n": c.log_n, "levels": c.n_levels, "public_inputs": c.n_pi, "witness_inputs": len(c.in_cycle)}
+    line["verifier_joined"]["generators"] = len(jc.generators())
     for v, vc in vcs.items():
         line["vanishing_" + v].update({"arithmetic_ops": vc.ops.count, "arithmetic_rows": len(vc.ops.rows), "mds_rows": len(vc.mds_rows),
                                        "ops_per_inner_gate": vc.gate_ops})
@@ -117,11 +129,15 @@ def witness(a):
     import sipp_amd
     from sipp_amd._lib import to_device
     from tests import _oracle
+    from sipp_amd import plonk_verifier as pj
     o, vcs, fc = circuits_of(a)
     v_args, f_args = arguments(o, vcs["monomials"], fc)             # the arguments do not depend on the variant
+    jc = pj.PlonkVerifierCircuit(*joined_shape(a, o), **JOINED)
+    j_args = pj.flat_proof_arguments(jc, o["proof"], o["cap"], INNER_DIGEST)
     ctx = sipp_amd.Ctx(workspace_bytes=2 << 30)
     runs = {}
-    for name, c, args, n_pub in [("vanishing_" + v, vc, v_args, 4) for v, vc in vcs.items()] + [("fri_proof", fc, f_args, 6)]:
+    for name, c, args, n_pub in ([("vanishing_" + v, vc, v_args, 4) for v, vc in vcs.items()] + [("fri_proof", fc, f_args, 6)] +
+                                 [("verifier_joined", jc, j_args, 3)]):
         pih = _oracle.hash_no_pad(np.array(c.public_inputs(*args[:n_pub]), dtype=np.uint64))
         runs[name] = (c, to_device(c.partial_witness(*args)), to_device(c.constants_sigmas()[:c.num_constants]),
                       sipp_amd.PlonkSchedule.from_dict(c.schedule()), pih)
@@ -140,9 +156,14 @@ def prove(a):
     import sipp_amd
     from sipp_amd import circuit as ci
     from sipp_amd import plonk_vanishing as pv
+    from sipp_amd import plonk_verifier as pj
     o, vcs, fc = circuits_of(a)
     gp = sipp_amd.PlonkParams(80, 8, 2)
     ctxs, vers = [], {}
+    jc = pj.PlonkVerifierCircuit(*joined_shape(a, o), **JOINED)     # built here for its size alone; the prover builds its own
+    j_fri = ci.fri_params(jc.log_n)
+    ctxs.append(ctx_for(jc.log_n, gp, j_fri, jc.circuit()))
+    joined = pj.PlonkVerifierProver(ctxs[0], *joined_shape(a, o), fri=j_fri, params=gp, **JOINED)
     for v, vc in vcs.items():                                       # one verifier per variant, each with its own two ctxs
         fris = (ci.fri_params(vc.log_n), ci.fri_params(fc.log_n))
         pair_ctxs = [ctx_for(c.log_n, gp, f, c.circuit()) for c, f in zip((vc, fc), fris)]
@@ -153,9 +174,19 @@ def prove(a):
     v_args, _ = arguments(o, vcs["monomials"], fc)
     cells, values = van.circ.input_cells(*v_args)
     pis = van.circ.public_inputs(*v_args)
-    t = {k: [] for k in [x + "_" + v for v in vers for x in ("prove_pair", "verify_pair")] + ["prove_words", "prove_inputs"]}
+    t = {k: [] for k in [x + "_" + v for v in vers for x in ("prove_pair", "verify_pair")] + ["prove_words", "prove_inputs", "prove_joined",
+                                                                                              "verify_joined"]}
     words = {}
+    inner_pis = [int(x) for x in o["proof"][len(o["proof"]) - o["n_pi"]:]]
     for _ in range(a.reps + 1):
+        t0 = time.perf_counter()                                    # the one circuit, in the same round as the pairs
+        one = joined.prove_proof(o["proof"], o["cap"], INNER_DIGEST)
+        t["prove_joined"].append(time.perf_counter() - t0)
+        t0 = time.perf_counter()
+        got = joined.verify(one, o["cap"], INNER_DIGEST)
+        t["verify_joined"].append(time.perf_counter() - t0)
+        assert got == inner_pis
+        words["joined"] = int(len(one))
         for v, ver in vers.items():                                 # interleaved: every variant sees the same clocks
             t0 = time.perf_counter()
             pair = ver.prove_proof(o["proof"], o["cap"], INNER_DIGEST)
@@ -174,7 +205,7 @@ def prove(a):
         t["prove_inputs"].append(time.perf_counter() - t0)
         assert (pf_w == pf_i).all()
     print(json.dumps({"step": "prove", **{k: stats(v) for k, v in t.items()}, "proof_words": words}))
-    for ver in vers.values():
+    for ver in list(vers.values()) + [joined]:
         ver.close()
     for ctx in ctxs:
         ctx.close()

@@ -83,6 +83,9 @@ extern "C" int sipp_circuit_build(sipp_ctx* ctx, uint32_t log_n, const sipp_plon
         (!sched->rows || !sched->level_offsets || !sched->copy_offsets ||
          (sched->copy_offsets[sched->n_levels] && (!sched->copy_src || !sched->copy_dst)) || sched->n_levels > (1u << 20)))
         return sipp_fail(ctx, SIPP_E_BADARG, "circuit build: incomplete schedule");
+    // sipp_plonk_generate_witness_levels' ceiling, refused here and not at the first proof (the row-local call has none)
+    if (sched && sched->n_levels && n_gens > 32)
+        return sipp_fail(ctx, SIPP_E_BADARG, "circuit build: more than 32 generators with a level schedule");
     SIPP_TRY(sipp_plonk_circuit_check(ctx, c, p));          // a malformed gate set is refused here, not at the first proof
     SIPP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
     sipp_circuit_data* cd = nullptr;

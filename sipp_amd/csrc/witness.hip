@@ -406,9 +406,13 @@ __global__ void __launch_bounds__(256) plonk_witness_kernel(GenArgs a) {
 }
 
 // ---- level by level -------------------------------------------------------------------------------------------------------------------
-constexpr uint32_t MAX_GENS = 16;
+// A circuit's generators travel by value in the kernel arguments (scalar loads by a wave-uniform index).  Up to NARROW_GENS the struct
+// is the one every circuit had before the ceiling rose; a circuit with more takes the same kernels over the MAX_GENS struct (1104 bytes
+// of arguments: under the 4 KiB limit), so that a circuit at or below NARROW_GENS launches what it always launched.
+constexpr uint32_t NARROW_GENS = 16, MAX_GENS = 32;
 constexpr uint32_t COOP_BELOW_ROWS = 16384;   // levels with fewer rows than this leave SIMDs empty with one lane per row
-struct LevelArgs {
+template <uint32_t NG>
+struct LevelArgsT {
     uint64_t* wires;
     const uint64_t* consts;
     uint32_t n, n_gens;
@@ -416,12 +420,15 @@ struct LevelArgs {
     uint32_t count;
     int* err;
     uint64_t pih[4];
-    sipp_plonk_generator g[MAX_GENS];
+    sipp_plonk_generator g[NG];
 };
+using LevelArgs = LevelArgsT<NARROW_GENS>;
+using LevelArgsWide = LevelArgsT<MAX_GENS>;
 
 // one lane per row of the level; the row runs the generator whose selector value it holds (the lanes of a wave may hold different gates:
 // the families are short except Poseidon, whose rows a schedule keeps together)
-__global__ void __launch_bounds__(64) plonk_witness_level_kernel(LevelArgs a) {
+template <class Args>
+__global__ void __launch_bounds__(64) plonk_witness_level_kernel(Args a) {
     const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= a.count) return;
     const uint32_t i = a.rows[k];
@@ -496,7 +503,8 @@ __device__ __forceinline__ void poseidon_lanes(uint64_t* wires, uint32_t n, uint
 }
 
 // the circuit's one Poseidon generator a.g[pos] (pos = -1: none) on the sixteen lanes, its parameters block-uniform
-__global__ void __launch_bounds__(64) plonk_witness_level_coop_kernel(LevelArgs a, int pos) {
+template <class Args>
+__global__ void __launch_bounds__(64) plonk_witness_level_coop_kernel(Args a, int pos) {
     __shared__ uint64_t sh[4][12];
     const CoopRow row = coop_row(a.rows, a.count, a.n, a.err);
     const uint32_t grp = row.grp, l = row.l, i = row.i, n = a.n;
@@ -523,8 +531,8 @@ __global__ void __launch_bounds__(64) plonk_witness_level_coop_kernel(LevelArgs 
 // a query's longest chain); a row that holds SIPP_GEN_REDUCING or _REDUCING_EXT spreads its coefficients over its sixteen lanes
 // (reducing_lanes) unless reduce_one_lane (SIPP_ROUTE_WITNESS_REDUCE_ONE_LANE).  It implies INTERP's code: an interpolation generator
 // may or may not be there.
-template <bool INTERP, bool REDUCE>
-__global__ void __launch_bounds__(64) plonk_witness_level_coop_rows_kernel(LevelArgs a, bool one_lane, bool reduce_one_lane) {
+template <bool INTERP, bool REDUCE, class Args>
+__global__ void __launch_bounds__(64) plonk_witness_level_coop_rows_kernel(Args a, bool one_lane, bool reduce_one_lane) {
     __shared__ uint64_t sh[4][12];
     const CoopRow row = coop_row(a.rows, a.count, a.n, a.err);
     const uint32_t grp = row.grp, l = row.l, i = row.i, n = a.n;
@@ -680,19 +688,12 @@ void sipp_witness_graph_release(sipp_ctx* ctx) {
     ctx->wgraph.key.clear();
 }
 
-extern "C" int sipp_plonk_generate_witness_levels(sipp_ctx* ctx, uint64_t* d_wires, const uint64_t* d_constants, uint32_t log_n,
-                                                  uint32_t num_wires, uint32_t num_constants, const sipp_plonk_generator* gens, size_t n_gens,
-                                                  const uint64_t public_inputs_hash[4], const sipp_plonk_schedule* sched) {
-    if (!ctx) return SIPP_E_BADARG;
-    SIPP_TRY(witness_prepare(ctx, d_wires, d_constants, log_n, num_wires, num_constants, gens, n_gens, public_inputs_hash));
-    if (!sched || !sched->n_levels || sched->n_levels > (1u << 20) || !sched->d_rows || !sched->level_offsets || !sched->copy_offsets || n_gens > MAX_GENS)
-        return sipp_fail(ctx, SIPP_E_BADARG, "plonk witness: no schedule, no level, or more than 16 generators");
+namespace {
+// the levels of a checked call at one width of the argument struct (Args = LevelArgs or LevelArgsWide)
+template <class Args>
+int witness_levels_run(sipp_ctx* ctx, uint64_t* d_wires, const uint64_t* d_constants, uint32_t log_n, uint32_t num_wires, uint32_t num_constants,
+                       const sipp_plonk_generator* gens, size_t n_gens, const uint64_t* public_inputs_hash, const sipp_plonk_schedule* sched) {
     const uint32_t n = 1u << log_n, L = sched->n_levels;
-    for (uint32_t l = 0; l < L; l++)
-        if (sched->level_offsets[l] > sched->level_offsets[l + 1] || sched->copy_offsets[l] > sched->copy_offsets[l + 1])
-            return sipp_fail(ctx, SIPP_E_BADARG, "plonk witness: schedule offsets must not decrease");
-    if (sched->level_offsets[L] > n || (sched->copy_offsets[L] && (!sched->d_copy_src || !sched->d_copy_dst)))
-        return sipp_fail(ctx, SIPP_E_BADARG, "plonk witness: more scheduled rows than the table has, or copies without their cell lists");
     // the error flag lives in a persistent one-word table of the ctx (the captured graph keeps its address)
     int* d_err = reinterpret_cast<int*>(sipp_table_get(ctx, TAB_WITNESS_ERR, 0, 0));
     if (!d_err) {
@@ -714,11 +715,11 @@ extern "C" int sipp_plonk_generate_witness_levels(sipp_ctx* ctx, uint64_t* d_wir
     const bool reduce_one_lane = any_initial && (ctx->kernel_routes & SIPP_ROUTE_WITNESS_REDUCE_ONE_LANE);
     // a thin level's per-row kernel at the instantiation the circuit's families need (the one-lane flags are false wherever their code is
     // compiled out); none: the single-generator kernel
-    const auto rows_kernel = any_initial  ? plonk_witness_level_coop_rows_kernel<true, true>
-                             : any_interp ? plonk_witness_level_coop_rows_kernel<true, false>
-                             : per_row    ? plonk_witness_level_coop_rows_kernel<false, false>
+    const auto rows_kernel = any_initial  ? plonk_witness_level_coop_rows_kernel<true, true, Args>
+                             : any_interp ? plonk_witness_level_coop_rows_kernel<true, false, Args>
+                             : per_row    ? plonk_witness_level_coop_rows_kernel<false, false, Args>
                                           : nullptr;
-    LevelArgs a;     // the same for every level but for rows and count
+    Args a;          // the same for every level but for rows and count
     a.wires = d_wires; a.consts = d_constants; a.n = n; a.n_gens = (uint32_t)n_gens; a.err = d_err;
     for (int q = 0; q < 4; q++) a.pih[q] = public_inputs_hash ? public_inputs_hash[q] : 0;
     for (size_t q = 0; q < n_gens; q++) a.g[q] = gens[q];
@@ -730,11 +731,11 @@ extern "C" int sipp_plonk_generate_witness_levels(sipp_ctx* ctx, uint64_t* d_wir
                 a.rows = sched->d_rows + r0;
                 a.count = cnt;
                 if (cnt >= COOP_BELOW_ROWS)      // wide level: throughput, one lane per row
-                    hipLaunchKernelGGL(plonk_witness_level_kernel, dim3((cnt + 63) / 64), dim3(64), 0, ctx->stream, a);
+                    hipLaunchKernelGGL(plonk_witness_level_kernel<Args>, dim3((cnt + 63) / 64), dim3(64), 0, ctx->stream, a);
                 else if (rows_kernel)            // thin level: latency, sixteen lanes per row
                     hipLaunchKernelGGL(rows_kernel, dim3((cnt + 3) / 4), dim3(64), 0, ctx->stream, a, one_lane, reduce_one_lane);
                 else
-                    hipLaunchKernelGGL(plonk_witness_level_coop_kernel, dim3((cnt + 3) / 4), dim3(64), 0, ctx->stream, a, pos_gen);
+                    hipLaunchKernelGGL(plonk_witness_level_coop_kernel<Args>, dim3((cnt + 3) / 4), dim3(64), 0, ctx->stream, a, pos_gen);
             }
             const uint32_t c0 = sched->copy_offsets[l], cc = sched->copy_offsets[l + 1] - c0;
             if (cc)
@@ -782,4 +783,26 @@ extern "C" int sipp_plonk_generate_witness_levels(sipp_ctx* ctx, uint64_t* d_wir
     SIPP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (h_err) return sipp_fail(ctx, SIPP_E_BADARG, "plonk witness: the schedule names a row or a cell outside the wire table");
     return SIPP_OK;
+}
+}  // namespace
+
+extern "C" int sipp_plonk_generate_witness_levels(sipp_ctx* ctx, uint64_t* d_wires, const uint64_t* d_constants, uint32_t log_n,
+                                                  uint32_t num_wires, uint32_t num_constants, const sipp_plonk_generator* gens, size_t n_gens,
+                                                  const uint64_t public_inputs_hash[4], const sipp_plonk_schedule* sched) {
+    if (!ctx) return SIPP_E_BADARG;
+    // the ceiling first: nothing is launched, copied or uploaded for a circuit past it
+    if (n_gens > MAX_GENS) return sipp_fail(ctx, SIPP_E_BADARG, "plonk witness: more than 32 generators (the level kernels carry at most 32)");
+    SIPP_TRY(witness_prepare(ctx, d_wires, d_constants, log_n, num_wires, num_constants, gens, n_gens, public_inputs_hash));
+    if (!sched || !sched->n_levels || sched->n_levels > (1u << 20) || !sched->d_rows || !sched->level_offsets || !sched->copy_offsets)
+        return sipp_fail(ctx, SIPP_E_BADARG, "plonk witness: no schedule or no level");
+    const uint32_t n = 1u << log_n, L = sched->n_levels;
+    for (uint32_t l = 0; l < L; l++)
+        if (sched->level_offsets[l] > sched->level_offsets[l + 1] || sched->copy_offsets[l] > sched->copy_offsets[l + 1])
+            return sipp_fail(ctx, SIPP_E_BADARG, "plonk witness: schedule offsets must not decrease");
+    if (sched->level_offsets[L] > n || (sched->copy_offsets[L] && (!sched->d_copy_src || !sched->d_copy_dst)))
+        return sipp_fail(ctx, SIPP_E_BADARG, "plonk witness: more scheduled rows than the table has, or copies without their cell lists");
+    // a circuit at or below NARROW_GENS launches the kernels, with the arguments, it launched before the ceiling rose
+    return n_gens <= NARROW_GENS
+               ? witness_levels_run<LevelArgs>(ctx, d_wires, d_constants, log_n, num_wires, num_constants, gens, n_gens, public_inputs_hash, sched)
+               : witness_levels_run<LevelArgsWide>(ctx, d_wires, d_constants, log_n, num_wires, num_constants, gens, n_gens, public_inputs_hash, sched);
 }

@@ -3,6 +3,8 @@ sipp_amd/fri_verifier.py (query_rounds_into) behind a challenger that runs IN CI
 recalled), with the proof of work.  alpha, every beta_r and every x_index are generated cells: nobody who asks for the proof picks them.
 
   FriProofCircuit   the statement "this opening proof verifies against these caps, behind this transcript"
+  _proof_into       (a method of the circuit) the transcript, the proof of work and the queries behind a challenger that is handed in,
+                    over sources: this circuit passes its public inputs, sipp_amd/plonk_verifier.py's joined circuit its own
   FriProofProver    the circuit through the library's CircuitData: the map from the proof's words to the input cells is fixed at build
                     (words_map) and set on the device once; prove_proof(flat proof, caps, points, transcript) sends the words and
                     calls sipp_circuit_prove_words (without a device map: a numpy gather and sipp_circuit_prove_inputs);
@@ -69,17 +71,21 @@ class FriProofCircuit(FriQueryRoundCircuit):
         groups = gate_groups(cap_height, self.arity_bits)
         # the two groups of degree <= 4 are full: the BaseSum-shaped gates (degree 2) get a group of their own
         CircuitBuilder.__init__(self, num_wires, num_routed, GATE_NAMES, groups + (groups[-1] + 1,) * 3, 2, self.pi_finals + 2 * final_len)
-        self._declare_gates()
-        self.declare(BASE_SPLIT64, 2, (GEN_BASE_SPLIT, 64, 1), base_sum_into, 64)
-        self.declare(BASE_SUM_CAP, 2, (GEN_BASE_SUM, cap_height, 1), base_sum_into, cap_height)
-        self.declare(BASE_SUM_WITHIN, 2, (GEN_BASE_SUM, self.arity_bits, 1), base_sum_into, self.arity_bits)
-        assert _i64(1 << 63) + P == 1 << 63                     # the top limb's coefficient is a negative program word
+        self._declare_proof_gates()
         self._in_keys = []
         self._wiring()
         self.finish(min_log_n)
         cells = [x for cyc in self.pi_cycle + self.in_cycle for x in cyc]
         assert len(cells) == len(set(cells))
         self._proof_layout()
+
+    def _declare_proof_gates(self):
+        """the sixteen gates of GATE_NAMES: the query rounds' thirteen, the 64-limb split and the two le_sum shapes"""
+        self._declare_gates()
+        self.declare(BASE_SPLIT64, 2, (GEN_BASE_SPLIT, 64, 1), base_sum_into, 64)
+        self.declare(BASE_SUM_CAP, 2, (GEN_BASE_SUM, self.cap_height, 1), base_sum_into, self.cap_height)
+        self.declare(BASE_SUM_WITHIN, 2, (GEN_BASE_SUM, self.arity_bits, 1), base_sum_into, self.arity_bits)
+        assert _i64(1 << 63) + P == 1 << 63                     # the top limb's coefficient is a negative program word
 
     # public-input positions (pi_point, pi_opened, pi_cap, pi_final: the parent's, from this circuit's offsets); what is drawn in circuit
     # has none
@@ -113,20 +119,33 @@ class FriProofCircuit(FriQueryRoundCircuit):
         self.omega_row, omega = self.constant(self.omega_m)
         self.ginv_row, ginv = self.constant(self.g_inv)
         ch = _Challenger(self, POSEIDON_SWAP, zero, [pi(self.pi_state(t)) for t in range(12)], [pi(self.pi_pending(t)) for t in range(self.n_in)])
+        self._proof_into(ch, (zero, one, omega, ginv))
+        self.hash_public_inputs(POSEIDON_SWAP, zero)
+
+    def _proof_into(self, ch, consts, opened=None, cap=None, round_cap=None, point=None, final=None):
+        """The FRI transcript, the proof of work and the queries behind challenger ch (a _Challenger on this builder, with whatever it
+        has absorbed so far).  consts = the cells (zero, one, omega_M, 1 / g); opened(b, j, l), cap(o, j, w), round_cap(r, j, w),
+        point(b, l), final(k, l): the sources of fri_verifier.query_rounds_into, None = this circuit's public inputs.  The proof-of-work
+        witness and what query_rounds_into makes are witness inputs.  Sets alpha_cells, beta_cells, response_cell, index_cells, the
+        row lists, transcript_row (every row of ch so far) and transcript_levels."""
+        zero = consts[0]
+        opened = opened or (lambda b, j, l: pi(self.pi_opened(b, j, l)))
+        round_cap = round_cap or (lambda r, j, w: pi(self.pi_round_cap(r, j, w)))
+        final = final or (lambda k, l: pi(self.pi_final(k, l)))
         for b, cols in enumerate(self.batches):
             for j in range(len(cols)):
                 for l in range(2):
-                    ch.observe(pi(self.pi_opened(b, j, l)))
+                    ch.observe(opened(b, j, l))
         self.alpha_cells = alpha = (ch.get(), ch.get())
         self.beta_cells = []
         for r in range(self.n_rounds):
             for j in range(self.n_cap):
                 for w in range(4):
-                    ch.observe(pi(self.pi_round_cap(r, j, w)))
+                    ch.observe(round_cap(r, j, w))
             self.beta_cells.append((ch.get(), ch.get()))
         for k in range(self.final_len):
             for l in range(2):
-                ch.observe(pi(self.pi_final(k, l)))
+                ch.observe(final(k, l))
         # the proof of work
         witness = self._new_input("pow_witness")
         if self.pow_rule == 0:
@@ -155,10 +174,9 @@ class FriProofCircuit(FriQueryRoundCircuit):
             self.within_row[q].append(self._le_sum(BASE_SUM_WITHIN, bits))
             return (0, self.within_row[q][-1])
         beta = self.beta_cells
-        query_rounds_into(self, (zero, one, omega, ginv), alpha, lambda r, l: beta[r][l], bits_of, cap_index_of, within_of)
+        query_rounds_into(self, consts, alpha, lambda r, l: beta[r][l], bits_of, cap_index_of, within_of, opened, cap, round_cap, point, final)
         self.transcript_row = list(ch.rows)
         self.transcript_levels = max(self._level[r] for r in self.transcript_row + self.pow_hash_row) + 1
-        self.hash_public_inputs(POSEIDON_SWAP, zero)
 
     # ---- the values ----
     def _check(self, transcript, points, opened, caps, round_caps, final_poly, pow_witness=None, queries=None):

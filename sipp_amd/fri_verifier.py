@@ -66,19 +66,28 @@ ROW_NAMES = ("bs_row", "exp0_row", "x_row", "init_ra_row", "init_hash_row", "ini
              "coset_path_row", "horner_row")
 
 
-def query_rounds_into(c, consts, alpha, beta, bits_of, cap_index_of, within_of):
+def query_rounds_into(c, consts, alpha, beta, bits_of, cap_index_of, within_of, opened=None, cap=None, round_cap=None, point=None, final=None):
     """Every query round of circuit c (a FriQueryRoundCircuit, or sipp_amd/fri_proof.py's circuit of the same shape attributes and public-
     input positions) with what the challenges decide given as arguments.  consts = the cells (zero, one, omega_M, 1 / g); alpha: two limb
     sources; beta(r, l): the source of limb l of round r's challenge; bits_of(q) -> (the row that split query q's index, its log_m bit
     cells, low first); cap_index_of(q, bits) -> the source of the index's top cap_height bits as one value; within_of(q, r, bits) -> the
     source of round r's index within its coset (bits: the arity_bits cells it is made of).  The opened rows, the siblings, the
     evaluations and the coset siblings are witness inputs made here (c._new_input).  Sets c.opened_row, c.power_row and the per-query
-    row lists ROW_NAMES."""
+    row lists ROW_NAMES.
+    What the proof and its statement carry besides are sources too: opened(b, j, l) = limb l of batch b's opened value j; cap(o, j, w) =
+    word w of digest j of initial oracle o's cap; round_cap(r, j, w) the same of round r's cap; point(b, l) = limb l of batch b's point;
+    final(k, l) = limb l of the final polynomial's coefficient k.  None = c's public input at c.pi_opened / pi_cap / pi_round_cap /
+    pi_point / pi_final: a circuit that holds them elsewhere (witness inputs, cells drawn in circuit) passes its own."""
     zero, one, omega, ginv = consts
+    opened = opened or (lambda b, j, l: pi(c.pi_opened(b, j, l)))
+    cap = cap or (lambda o, j, w: pi(c.pi_cap(o, j, w)))
+    round_cap = round_cap or (lambda r, j, w: pi(c.pi_round_cap(r, j, w)))
+    point = point or (lambda b, l: pi(c.pi_point(b, l)))
+    final = final or (lambda k, l: pi(c.pi_final(k, l)))
     a, M, C = c.arity_bits, c.log_m, c.cap_height
     cap_shape = (RANDOM_ACCESS_CAP, c.cap_rows, c.cap_copies, c.cap_stride, c.n_cap)
     # once per proof and batch: the reduced openings, alpha^len
-    c.opened_row, c.power_row, acc_o, alpha_len = openings_into(c, REDUCING_EXT, alpha, zero, lambda b, j, l: pi(c.pi_opened(b, j, l)))
+    c.opened_row, c.power_row, acc_o, alpha_len = openings_into(c, REDUCING_EXT, alpha, zero, opened)
     for name in ROW_NAMES:
         setattr(c, name, [])
     for q in range(c.n_queries):
@@ -92,12 +101,12 @@ def query_rounds_into(c, consts, alpha, beta, bits_of, cap_index_of, within_of):
             row = [c._new_input("row", q, o, k) for k in range(width)]
             sib = [[c._new_input("sibling", q, o, l, t) for t in range(4)] for l in range(c.height)]
             ra, hs, path = opening_into(c, cap_shape, POSEIDON_SWAP, zero, row, bits[:c.height], cap_index,
-                                        lambda j, w: pi(c.pi_cap(o, j, w)), cap_bits, lambda l, t: sib[l][t])
+                                        lambda j, w: cap(o, j, w), cap_bits, lambda l, t: sib[l][t])
             leaves += row
             ras.append(ra); hashes.append(hs); paths.append(path)
         # the combination of those same row cells, times x: the first old
         (lf, nm, dn, qt, tt, orow), old = combine_into(c, (REDUCING, QUOTIENT_EXT), alpha, zero, one, x, acc_o, alpha_len,
-                                                       lambda k: leaves[k], lambda b, l: pi(c.pi_point(b, l)))
+                                                       lambda k: leaves[k], point)
         # the folds: one cell per evaluation for the RandomAccess items, the interpolation row and (below) the coset leaf
         ev = [[[c._new_input("eval", q, r, j, l) for l in range(2)] for j in range(c.arity)] for r in range(c.n_rounds)]
         within = [within_of(q, r, bits[a * r:a * (r + 1)]) for r in range(c.n_rounds)]
@@ -108,11 +117,11 @@ def query_rounds_into(c, consts, alpha, beta, bits_of, cap_index_of, within_of):
         for r in range(c.n_rounds):
             sib = [[c._new_input("coset_sibling", q, r, l, t) for t in range(4)] for l in range(c.round_height[r])]
             ra, hs, path = opening_into(c, cap_shape, POSEIDON_SWAP, zero, [ev[r][j][l] for j in range(c.arity) for l in range(2)],
-                                        bits[a * (r + 1):M - C], cap_index, lambda j, w: pi(c.pi_round_cap(r, j, w)), cap_bits,
+                                        bits[a * (r + 1):M - C], cap_index, lambda j, w: round_cap(r, j, w), cap_bits,
                                         lambda l, t: sib[l][t])
             cras.append(ra); chashes.append(hs); cpaths.append(path)
         # the final polynomial at x is the last old
-        horner, acc = final_poly_into(c, zero, x_last, lambda k, l: pi(c.pi_final(k, l)))
+        horner, acc = final_poly_into(c, zero, x_last, final)
         for l in range(2):
             c.tie(acc[l], last[l])
         for name, got in zip(ROW_NAMES, (bs, e0, xr, ras, hashes, paths, lf, nm, dn, qt, tt, orow) + tuple(fold_rows) + (cras, chashes, cpaths, horner)):

@@ -6,6 +6,8 @@ constraints are evaluated at zeta from the opened values; the result is tied to 
   PlonkVanishingCircuit   the statement "these opened values meet the vanishing equation behind this transcript"; zeta, g zeta and the
                           departing sponge state are public OUTPUTS, for sipp_amd/fri_proof.py's circuit to take over from
   PlonkVanishingProver    the circuit through the library's CircuitData: prove_proof(flat inner proof, digest)
+  _vanishing_into         (a method of the circuit) the statement as a routine over sources: this circuit passes its public inputs,
+                          sipp_amd/plonk_verifier.py's joined circuit its witness inputs, and goes on with the challenger it returns
 
 The gate compiler.  The inner gate set is data: per gate a selector and one polynomial per constraint as monomials (the program words
 verify.cpp and circuit_ok read: a monomial count per constraint, per monomial an int64 coefficient -- negative words mean p + c -- and
@@ -245,6 +247,29 @@ class PlonkVanishingCircuit(CircuitBuilder):
         """poseidon_mds: the inner gate whose program is merkle.poseidon_swap_gate() at SWAP_LAYOUT, word for word, is evaluated
         numerically through PoseidonMds rows (_poseidon_constraints) instead of from its monomials; refused if there is none.
         alpha_chunk = K >= 2: the closing Horner in alpha runs inside chunks of K terms, then in alpha^K over the chunk sums"""
+        self._set_inner(log_n, params, circuit, cap_height, n_pi_inner, num_routed, poseidon_mds, alpha_chunk)
+        # public-input positions
+        self.pi_digest, self.pi_inner = 0, 4
+        self.pi_caps = 4 + n_pi_inner
+        self.pi_opened = self.pi_caps + 3 * 4 * self.n_cap
+        self.pi_zeta = self.pi_opened + 2 * self.n_open
+        self.pi_gzeta, self.pi_state = self.pi_zeta + 2, self.pi_zeta + 4
+        self.mds_gate, self.swap_gate = (POSEIDON_MDS, POSEIDON_MDS + 1) if self.poseidon_mds else (None, POSEIDON_SWAP)
+        names, group = (MDS_GATE_NAMES, MDS_GATE_GROUP) if self.poseidon_mds else (GATE_NAMES, GATE_GROUP)
+        CircuitBuilder.__init__(self, num_wires, num_routed, names, group, 2, self.pi_state + 12)
+        self.declare_basic(1)
+        self.declare(ARITHMETIC_EXT, 3, (GEN_ARITHMETIC_EXT, self.n_ops, self.k0, self.k1, EXT_W), arithmetic_ext_into, self.n_ops, self.k0,
+                     self.k1, EXT_W)
+        self.declare(QUOTIENT_EXT, 3, (GEN_QUOTIENT_EXT, 1, self.k0, self.k1, EXT_W), arithmetic_ext_into, 1, self.k0, self.k1, EXT_W)
+        if self.poseidon_mds:
+            declare_mds_gate(self, self.mds_gate, MDS_IN, MDS_OUT)
+        declare_swap_gate(self, self.swap_gate)
+        self._wiring()
+        self.finish(min_log_n)
+
+    def _set_inner(self, log_n, params, circuit, cap_height, n_pi_inner, num_routed, poseidon_mds, alpha_chunk):
+        """the inner circuit's shape with its refusals, and what the statement (_vanishing_into) reads of it; sipp_amd/plonk_verifier.py's
+        circuit takes the same"""
         assert alpha_chunk is None or (isinstance(alpha_chunk, int) and alpha_chunk >= 2), "alpha_chunk must be an int of at least 2"
         self.poseidon_mds, self.alpha_chunk = bool(poseidon_mds), alpha_chunk
         R, D, C = ((params.num_routed_wires, params.max_degree, params.num_challenges) if hasattr(params, "max_degree") else
@@ -264,12 +289,6 @@ class PlonkVanishingCircuit(CircuitBuilder):
         self.n_open = self.n0 + C
         self.n_cap = 1 << cap_height
         self.ngc = max(g[5] for g in circuit["gates"])
-        # public-input positions
-        self.pi_digest, self.pi_inner = 0, 4
-        self.pi_caps = 4 + n_pi_inner
-        self.pi_opened = self.pi_caps + 3 * 4 * self.n_cap
-        self.pi_zeta = self.pi_opened + 2 * self.n_open
-        self.pi_gzeta, self.pi_state = self.pi_zeta + 2, self.pi_zeta + 4
         self.n_ops = num_routed // 8
         assert self.n_ops >= 1 and 25 <= num_routed
         self.routed_gates = []
@@ -278,40 +297,47 @@ class PlonkVanishingCircuit(CircuitBuilder):
             self.routed_gates = [g for g, gate in enumerate(circuit["gates"]) if gate[5] == 123 and np.array_equal(gate_words(circuit, g), want)]
             assert self.routed_gates, "poseidon_mds: no inner gate's program is the Poseidon swap gate's at SWAP_LAYOUT"
             assert MDS_OUT + 24 <= num_routed
-        self.mds_gate, self.swap_gate = (POSEIDON_MDS, POSEIDON_MDS + 1) if self.poseidon_mds else (None, POSEIDON_SWAP)
-        names, group = (MDS_GATE_NAMES, MDS_GATE_GROUP) if self.poseidon_mds else (GATE_NAMES, GATE_GROUP)
-        CircuitBuilder.__init__(self, num_wires, num_routed, names, group, 2, self.pi_state + 12)
-        self.declare_basic(1)
-        self.declare(ARITHMETIC_EXT, 3, (GEN_ARITHMETIC_EXT, self.n_ops, self.k0, self.k1, EXT_W), arithmetic_ext_into, self.n_ops, self.k0,
-                     self.k1, EXT_W)
-        self.declare(QUOTIENT_EXT, 3, (GEN_QUOTIENT_EXT, 1, self.k0, self.k1, EXT_W), arithmetic_ext_into, 1, self.k0, self.k1, EXT_W)
-        if self.poseidon_mds:
-            declare_mds_gate(self, self.mds_gate, MDS_IN, MDS_OUT)
-        declare_swap_gate(self, self.swap_gate)
-        self._wiring()
-        self.finish(min_log_n)
 
     # ---- the statement ----
-    def _opened(self, k):
-        return _V(src=(pi(self.pi_opened + 2 * k), pi(self.pi_opened + 2 * k + 1)))
-
     def _wiring(self):
-        R, D, C, K, W, m, np_ = self.R, self.D, self.C, self.K, self.W, self.m, self.np_
         self.pi_row = self.new_row(PUBLIC_INPUT)
         self.place(self.pi_row)
         self.zero_row, zero = self.constant(0)
         self.one_row, one = self.constant(1)
+        ch = self._vanishing_into((ARITHMETIC_EXT, QUOTIENT_EXT, self.mds_gate, self.swap_gate), zero, one,
+                                  lambda t: pi(self.pi_digest + t), lambda t: pi(self.pi_inner + t),
+                                  lambda o, t: pi(self.pi_caps + 4 * self.n_cap * o + t), lambda k, l: pi(self.pi_opened + 2 * k + l))
+        self.state_cells = list(ch.sponge)
+        # the outputs, public: the chain that hashes the public inputs reads them from the cells that hold them
+        outs = list(self.zeta_cells) + list(self.gzeta_cells) + self.state_cells
+        self.chain_row = self.hash_rows(self.swap_gate, zero, [pi(t) for t in range(self.pi_zeta)] + outs)
+        for k, s in enumerate(outs):
+            self.public_input(self.pi_zeta + k, s)
+        for t in range(4):
+            self.tie((self.s_out + t, self.chain_row[-1]), (t, self.pi_row))
+
+    def _vanishing_into(self, gates, zero, one, digest, inner_pi, cap_word, opened):
+        """The statement on this builder, with everything it reads given as sources: gates = (the ArithmeticExt gate of n_ops ops, the
+        one-op QuotientExt gate, the PoseidonMds gate or None, the PoseidonSwap gate); zero, one: the constants' cells; digest(t): word t
+        of the inner circuit digest; inner_pi(t): inner public input t; cap_word(o, t): word t of the flat cap of the wires (0), Z (1)
+        and quotient (2) oracle; opened(k, l): limb l of opened value k in the proof's order.  -> the challenger as it leaves, nothing
+        pending, zeta drawn last (sipp_amd/plonk_verifier.py's circuit goes on with it).  Sets pih_row, pih_cells, beta_cells,
+        gamma_cells, alpha_cells, zeta_cells, gzeta_cells, zeta_n_cells, zh_cells, l0_row, l0_cells, ops, mds_rows, term_cells,
+        side_cells, transcript_row."""
+        R, D, C, K, W, m, np_ = self.R, self.D, self.C, self.K, self.W, self.m, self.np_
+        arithmetic_gate, quotient_gate, mds_gate, swap_gate = gates
+        _opened = lambda k: _V(src=(opened(k, 0), opened(k, 1)))
         ZERO, ONE = _V(src=(zero, zero)), _V(src=(one, zero))
         base = lambda s: _V(src=(s, zero))
         # the public-input hash and the transcript
-        self.pih_row = self.hash_rows(self.swap_gate, zero, [pi(self.pi_inner + t) for t in range(self.n_pi_inner)])
+        self.pih_row = self.hash_rows(swap_gate, zero, [inner_pi(t) for t in range(self.n_pi_inner)])
         self.pih_cells = pih = [(self.s_out + t, self.pih_row[-1]) for t in range(4)]
-        ch = _Challenger(self, self.swap_gate, zero, [zero] * 12, [])
+        ch = _Challenger(self, swap_gate, zero, [zero] * 12, [])
         for t in range(4):
-            ch.observe(pi(self.pi_digest + t))
+            ch.observe(digest(t))
         for s in pih:
             ch.observe(s)
-        cap = lambda o: [pi(self.pi_caps + 4 * self.n_cap * o + t) for t in range(4 * self.n_cap)]
+        cap = lambda o: [cap_word(o, t) for t in range(4 * self.n_cap)]
         for s in cap(0):
             ch.observe(s)
         self.beta_cells = [ch.get() for _ in range(C)]
@@ -322,18 +348,18 @@ class PlonkVanishingCircuit(CircuitBuilder):
         for s in cap(2):
             ch.observe(s)
         self.zeta_cells = (ch.get(), ch.get())
-        self.state_cells, self.transcript_row = list(ch.sponge), list(ch.rows)
+        self.transcript_row = list(ch.rows)
         beta, gamma, alpha = ([base(s) for s in cells] for cells in (self.beta_cells, self.gamma_cells, self.alpha_cells))
         zeta = _V(src=self.zeta_cells)
         # the opened values
-        cv = [self._opened(k) for k in range(K)]
-        sg = [self._opened(K + j) for j in range(R)]
-        wv = [self._opened(K + R + i) for i in range(W)]
-        zs = [self._opened(K + R + W + c) for c in range(C)]
-        pps = [self._opened(K + R + W + C + k) for k in range(C * np_)]
-        qs = [self._opened(K + R + W + self.nz + k) for k in range(C * D)]
-        zs_next = [self._opened(self.n0 + c) for c in range(C)]
-        ops = self.ops = _Ops(self, ARITHMETIC_EXT, self.n_ops, self.mds_gate)
+        cv = [_opened(k) for k in range(K)]
+        sg = [_opened(K + j) for j in range(R)]
+        wv = [_opened(K + R + i) for i in range(W)]
+        zs = [_opened(K + R + W + c) for c in range(C)]
+        pps = [_opened(K + R + W + C + k) for k in range(C * np_)]
+        qs = [_opened(K + R + W + self.nz + k) for k in range(C * D)]
+        zs_next = [_opened(self.n0 + c) for c in range(C)]
+        ops = self.ops = _Ops(self, arithmetic_gate, self.n_ops, mds_gate)
         mul = lambda a, b: ops.op(1, 0, a, b)
         add = lambda a, b: ops.op(1, 1, a, ONE, b)
         sub = lambda a, b: ops.op(1, -1, a, ONE, b)
@@ -346,7 +372,7 @@ class PlonkVanishingCircuit(CircuitBuilder):
         ops.flush()
         self.zeta_n_cells, self.zh_cells, self.gzeta_cells = zeta_n.src, zh.src, gzeta.src
         # Z_H = n (zeta - 1) L_0: the generator writes the multiplicand; zeta = 1 writes zero
-        self.l0_row = self.new_row(QUOTIENT_EXT, (1 << self.inner_log_n) % P, 0)
+        self.l0_row = self.new_row(quotient_gate, (1 << self.inner_log_n) % P, 0)
         self.place(self.l0_row, [(0, d1.src[0]), (1, d1.src[1]), (4, zero), (5, zero), (6, zh.src[0]), (7, zh.src[1])])
         l0 = _V(src=((2, self.l0_row), (3, self.l0_row)))
         self.l0_cells = l0.src
@@ -397,13 +423,7 @@ class PlonkVanishingCircuit(CircuitBuilder):
         for a, b in self.side_cells:
             for l in range(2):
                 self.tie(a[l], b[l])
-        # the outputs, public: the chain that hashes the public inputs reads them from the cells that hold them
-        outs = list(self.zeta_cells) + list(self.gzeta_cells) + self.state_cells
-        self.chain_row = self.hash_rows(self.swap_gate, zero, [pi(t) for t in range(self.pi_zeta)] + outs)
-        for k, s in enumerate(outs):
-            self.public_input(self.pi_zeta + k, s)
-        for t in range(4):
-            self.tie((self.s_out + t, self.chain_row[-1]), (t, self.pi_row))
+        return ch
 
     def _gate_terms(self, ops, cv, wv, pih, ZERO, ONE):
         """the gate compiler -> ngc terms.  Sets gate_monomials (distinct monomials per gate) and gate_ops (ops per gate)"""
