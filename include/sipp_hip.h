@@ -645,6 +645,70 @@ int sipp_circuit_prove_words(sipp_circuit_data *cd, const uint64_t *words, size_
                              uint64_t *proof_out, size_t proof_cap, size_t *proof_len);
 int sipp_circuit_verify(const sipp_circuit_data *cd, const uint64_t *proof, size_t len, int *reason);
 
+/* ---- LOOKUP TABLES by a log-derivative argument: the columns below the quotient ----------------------------
+ * The library's own statement of a LogUp lookup (not plonky2's RE / SLDC bookkeeping): the table lives in CONSTANT columns, the
+ * multiplicities in WIRES.  A description is eight uint32 words:  q_look, look_wire0, n_look, q_tab, tab_const0, tab_mult0, n_tab, 0.
+ *   q_look, q_tab: constant columns (not selector columns) of 0 / 1 that mark looking rows and table rows;
+ *   slot k < n_look of a looking row: the pair (x, y) = wires (look_wire0 + 2k, look_wire0 + 2k + 1);
+ *   slot k < n_tab of a table row: the pair (tx, ty) = constant columns (tab_const0 + 2k, + 2k + 1), multiplicity m = wire tab_mult0 + k;
+ *   unused table slots repeat a real entry, unused looking slots look a real entry up;  n_look = n_tab = 0: no lookups (the calls
+ *   below do nothing).
+ * Refusals: n_look or n_tab above 128 SIPP_E_UNSUPPORTED; a column outside the circuit, q_look or q_tab below num_selectors, one of
+ * n_look / n_tab zero and the other not, a last word that is not 0, a marker cell that is neither 0 nor 1: SIPP_E_BADARG.
+ * d_wires [num_wires][N], d_constants [num_constants][N] (the constant columns in front of the constants_sigmas batch): VALUES in
+ * natural row order.  A looking or table value is its field value, whatever u64 holds it.
+ *
+ * sipp_plonk_lookup_multiplicities: zeroes the m cells of the table rows, then adds one for every slot of every looking row to the
+ * table slot with the equal pair.  Among equal table pairs the first in (row, slot) order takes every look; the search goes through a
+ * sorted index of the table's distinct pairs (built here on the host from the constant columns), so the counts do not depend on the
+ * order the device reaches the rows in.  A looked-up pair that is in no table slot: SIPP_E_WITNESS (a device flag read back once; the
+ * m cells are then unspecified, the ctx stays usable).
+ *
+ * sipp_plonk_lookup_sums: the running-sum columns for the caller's eta, theta (num_challenges host words each; any u64 congruent to
+ * the value).  With D = max_degree, the looking slots in Jl = ceil(n_look / D) groups of up to D and the table slots in Jt =
+ * ceil(n_tab / D) groups, J = Jl + Jt, per challenge and row:
+ *   looking group j:  U_j - U_(j-1) = q_look sum_k 1 / d_k,        d_k = theta - (x_k + eta y_k)
+ *   table group j:    U_j - U_(j-1) = - q_tab sum_k m_k / e_k,     e_k = theta - (tx_k + eta ty_k)
+ * U_(-1) = S(x), U_(J-1) = S(g x), S(1) = 0.  d_out [num_challenges J][N], the order of the columns behind the permutation's in the
+ * zs_partial_products oracle: S_0 .. S_(C-1), then U_0 .. U_(J-2) of challenge 0, of challenge 1, ...
+ * (sipp_plonk_lookup_num_columns = num_challenges J; 0 for an empty description or one outside the supported range).
+ * A row whose marker is 0 contributes 0 whatever it holds.  On a marked row a vanishing d_k or e_k (theta hit a combination) is
+ * SIPP_E_WITNESS -- not 1 / 0 = 0; d_out is then unspecified. */
+uint32_t sipp_plonk_lookup_num_columns(const sipp_plonk_params *p, const uint32_t *lookup);
+int sipp_plonk_lookup_multiplicities(sipp_ctx *ctx, uint64_t *d_wires, const uint64_t *d_constants, uint32_t log_n, uint32_t num_wires,
+                                     uint32_t num_constants, uint32_t num_selectors, const uint32_t *lookup);
+int sipp_plonk_lookup_sums(sipp_ctx *ctx, const uint64_t *d_wires, const uint64_t *d_constants, uint32_t log_n, uint32_t num_wires,
+                           uint32_t num_constants, uint32_t num_selectors, const sipp_plonk_params *p, const uint32_t *lookup,
+                           const uint64_t *etas, const uint64_t *thetas, uint64_t *d_out);
+/* The whole argument: sipp_plonk_prove_gates / sipp_plonk_gates_proof_size / sipp_plonk_verify_gates with a description (`lookup`,
+ * eight words, never NULL).  An EMPTY description is those calls, the proof "SIPPPLK3" byte for byte.  With a non-empty one:
+ *   - the transcript draws eta_0 .. eta_(C-1), then theta_0 .. theta_(C-1) behind the gammas;
+ *   - the S / U columns of sipp_plonk_lookup_sums go behind the Z / partial-product columns of the zs_partial_products oracle;
+ *   - the C boundary terms L_0(x) S_c(x), then challenge by challenge the J chain terms
+ *       looking group:  (U_j - U_(j-1)) Dl - q_look Nl,   Dl = prod_k d_k,  Nl = sum_k prod_(k' != k) d_k'
+ *       table group:    (U_j - U_(j-1)) Dt + q_tab Nt,    Dt = prod_k e_k,  Nt = sum_k m_k prod_(k' != k) e_k'
+ *     follow the gate-constraint terms in the one reduce_with_powers list (each of degree <= max_degree + 1, as a partial-product term);
+ *   - batch 0 opens every new column at zeta, batch 1 the S columns at g zeta behind the Z columns;
+ *   - flat proof "SIPPPLK4": header[24] = the sixteen words of "SIPPPLK3" with the new magic, then the eight description words
+ *     | wires cap | zs_partial_products cap | quotient cap | opening proof | public_inputs.
+ * The wire table holds the multiplicities already (sipp_plonk_lookup_multiplicities); a table the caller spoiled gives a proof the
+ * verifier refuses (stage 210) or SIPP_E_WITNESS (theta on a combination).  The verifier refuses (201) a header whose eight words are
+ * not the caller's description, and a description that does not fit the circuit; the lookup terms are part of the stage-210 check.
+ * sipp_circuit_set_lookup: the description of a circuit data (refusals as above; the sorted index of the table is built here, once).
+ * After it sipp_circuit_prove / _prove_inputs / _prove_words run the multiplicities behind witness generation and prove with the
+ * description, sipp_circuit_proof_size and sipp_circuit_verify follow it.  An empty description takes it off again. */
+size_t sipp_plonk_gates_lookup_proof_size(uint32_t log_n, const sipp_plonk_params *p, const sipp_fri_params *fp, const sipp_plonk_circuit *c,
+                                          uint32_t n_public_inputs, const uint32_t *lookup);
+int sipp_plonk_prove_gates_lookup(sipp_ctx *ctx, const uint64_t *d_wires, const uint64_t *d_constants_sigmas, const sipp_oracle *wires_oracle,
+                                  const uint64_t *wires_cap, const sipp_oracle *constants_sigmas_oracle, uint32_t log_n,
+                                  const sipp_plonk_params *p, const sipp_fri_params *fp, const sipp_plonk_circuit *c,
+                                  const uint64_t circuit_digest[4], const uint64_t *public_inputs, uint32_t n_public_inputs,
+                                  const uint32_t *lookup, uint64_t *proof_out, size_t proof_cap, size_t *proof_len);
+int sipp_plonk_verify_gates_lookup(const uint64_t *proof, size_t len, const uint64_t *constants_sigmas_cap, const sipp_plonk_params *p,
+                                   const sipp_fri_params *fp, const sipp_plonk_circuit *c, const uint64_t circuit_digest[4],
+                                   const uint32_t *lookup, int *reason);
+int sipp_circuit_set_lookup(sipp_circuit_data *cd, const uint32_t *lookup);
+
 /* ---- verification of the generic proofs (host code like sipp_stark_verify; stages in *reason, may be NULL) -------------------------
  * sipp_fri_verify_openings: PolynomialBatch::verify_openings over a proof of sipp_fri_prove_openings -- caps[o] = the cap of oracle o
  * (2^cap_height x 4 words), ncols / n_salt (may be NULL = 0) per oracle, the batches as proved; the caller's transcript goes in and

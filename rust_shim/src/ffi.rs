@@ -291,6 +291,25 @@ extern "C" {
                                   wires_cap: *const u64, constants_sigmas_oracle: *const SippOracle, log_n: u32, p: *const SippPlonkParams,
                                   fp: *const SippFriParams, c: *const SippPlonkCircuit, circuit_digest: *const u64, public_inputs: *const u64,
                                   n_public_inputs: u32, proof_out: *mut u64, proof_cap: usize, proof_len: *mut usize) -> c_int;
+    /// lookup tables by a log-derivative argument: the multiplicities of a wire table, the running-sum columns S / U
+    pub fn sipp_plonk_lookup_num_columns(p: *const SippPlonkParams, lookup: *const u32) -> u32;
+    pub fn sipp_plonk_lookup_multiplicities(ctx: *mut SippCtxOpaque, d_wires: *mut u64, d_constants: *const u64, log_n: u32, num_wires: u32,
+                                            num_constants: u32, num_selectors: u32, lookup: *const u32) -> c_int;
+    pub fn sipp_plonk_lookup_sums(ctx: *mut SippCtxOpaque, d_wires: *const u64, d_constants: *const u64, log_n: u32, num_wires: u32,
+                                  num_constants: u32, num_selectors: u32, p: *const SippPlonkParams, lookup: *const u32,
+                                  etas: *const u64, thetas: *const u64, d_out: *mut u64) -> c_int;
+    /// the gates-as-data prover, its size function and verifier with a lookup description ("SIPPPLK4"; an empty one: "SIPPPLK3")
+    pub fn sipp_plonk_gates_lookup_proof_size(log_n: u32, p: *const SippPlonkParams, fp: *const SippFriParams, c: *const SippPlonkCircuit,
+                                              n_public_inputs: u32, lookup: *const u32) -> usize;
+    pub fn sipp_plonk_prove_gates_lookup(ctx: *mut SippCtxOpaque, d_wires: *const u64, d_constants_sigmas: *const u64,
+                                         wires_oracle: *const SippOracle, wires_cap: *const u64, constants_sigmas_oracle: *const SippOracle,
+                                         log_n: u32, p: *const SippPlonkParams, fp: *const SippFriParams, c: *const SippPlonkCircuit,
+                                         circuit_digest: *const u64, public_inputs: *const u64, n_public_inputs: u32, lookup: *const u32,
+                                         proof_out: *mut u64, proof_cap: usize, proof_len: *mut usize) -> c_int;
+    pub fn sipp_plonk_verify_gates_lookup(proof: *const u64, len: usize, constants_sigmas_cap: *const u64, p: *const SippPlonkParams,
+                                          fp: *const SippFriParams, c: *const SippPlonkCircuit, circuit_digest: *const u64,
+                                          lookup: *const u32, reason: *mut c_int) -> c_int;
+    pub fn sipp_circuit_set_lookup(cd: *mut SippCircuitDataOpaque, lookup: *const u32) -> c_int;
     pub fn sipp_ntt_batch(ctx: *mut SippCtxOpaque, d_cols: *mut u64, col_stride: usize, ncols: usize, log_n: u32, inverse: c_int) -> c_int;
     pub fn sipp_lde_batch(ctx: *mut SippCtxOpaque, d_values: *const u64, d_coeffs: *mut u64, d_lde: *mut u64, ncols: usize, log_n: u32) -> c_int;
     pub fn sipp_poseidon_leaves(ctx: *mut SippCtxOpaque, d_lde: *const u64, ncols: usize, log_leaves: u32, d_digests: *mut u64) -> c_int;

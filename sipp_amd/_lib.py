@@ -170,6 +170,9 @@ SIGNATURES = {
                                           C.POINTER(FriParams), C.POINTER(Challenger), vp, C.c_size_t, C.POINTER(C.c_size_t)]),
     "sipp_plonk_num_partial_products": (C.c_uint32, [C.POINTER(PlonkParams)]),
     "sipp_plonk_zs_partial_products": (C.c_int, [vp, vp, vp, C.c_uint32, C.POINTER(PlonkParams), u64p, u64p, vp]),
+    "sipp_plonk_lookup_num_columns": (C.c_uint32, [C.POINTER(PlonkParams), u32p]),
+    "sipp_plonk_lookup_multiplicities": (C.c_int, [vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, u32p]),
+    "sipp_plonk_lookup_sums": (C.c_int, [vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(PlonkParams), u32p, u64p, u64p, vp]),
     "sipp_plonk_quotient_chunks": (C.c_int, [vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.POINTER(PlonkParams), u64p, u64p, u64p, vp]),
     "sipp_plonk_quotient_chunks_ex": (C.c_int, [vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.POINTER(PlonkParams), u64p, u64p, u64p, vp, C.c_uint32, vp]),
     "sipp_plonk_prove_ex": (C.c_int, [vp, vp, vp, C.POINTER(Oracle), u64p, C.POINTER(Oracle), C.c_uint32, C.POINTER(PlonkParams), C.POINTER(FriParams),
@@ -178,6 +181,14 @@ SIGNATURES = {
     "sipp_plonk_gates_proof_size": (C.c_size_t, [C.c_uint32, C.POINTER(PlonkParams), C.POINTER(FriParams), C.POINTER(PlonkCircuit), C.c_uint32]),
     "sipp_plonk_prove_gates": (C.c_int, [vp, vp, vp, C.POINTER(Oracle), u64p, C.POINTER(Oracle), C.c_uint32, C.POINTER(PlonkParams), C.POINTER(FriParams),
                                          C.POINTER(PlonkCircuit), u64p, u64p, C.c_uint32, vp, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "sipp_plonk_gates_lookup_proof_size": (C.c_size_t, [C.c_uint32, C.POINTER(PlonkParams), C.POINTER(FriParams), C.POINTER(PlonkCircuit), C.c_uint32,
+                                                        u32p]),
+    "sipp_plonk_prove_gates_lookup": (C.c_int, [vp, vp, vp, C.POINTER(Oracle), u64p, C.POINTER(Oracle), C.c_uint32, C.POINTER(PlonkParams),
+                                                C.POINTER(FriParams), C.POINTER(PlonkCircuit), u64p, u64p, C.c_uint32, u32p, vp, C.c_size_t,
+                                                C.POINTER(C.c_size_t)]),
+    "sipp_plonk_verify_gates_lookup": (C.c_int, [u64p, C.c_size_t, u64p, C.POINTER(PlonkParams), C.POINTER(FriParams), C.POINTER(PlonkCircuit), u64p,
+                                                 u32p, C.POINTER(C.c_int)]),
+    "sipp_circuit_set_lookup": (C.c_int, [vp, u32p]),
     "sipp_plonk_generate_witness": (C.c_int, [vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(PlonkGenerator), C.c_size_t, u64p]),
     "sipp_plonk_generate_witness_levels": (C.c_int, [vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(PlonkGenerator), C.c_size_t, u64p,
                                                      C.POINTER(PlonkSchedule)]),
@@ -234,6 +245,22 @@ def lib():
 
 
 SIPP_E_VERIFY = -9
+
+
+def plonk_verify_gates_lookup(proof, constants_sigmas_cap, p, fp, circuit, digest, lookup):
+    """sipp_plonk_verify_gates_lookup: the library's own check of a "SIPPPLK4" proof (host code; no ctx, no GPU) against the caller's
+    lookup description (eight words; an empty one: a "SIPPPLK3" proof).  Returns 0 for an accepted proof, else the refusing stage."""
+    pf = np.ascontiguousarray(proof, dtype=np.uint64)
+    cap = np.ascontiguousarray(constants_sigmas_cap, dtype=np.uint64).reshape(-1)
+    words = [int(x) for x in lookup]
+    if len(words) != 8:
+        raise SippError(-1, "a lookup description is eight words")
+    reason = C.c_int(0)
+    rc = lib().sipp_plonk_verify_gates_lookup(pf.ctypes.data_as(u64p), len(pf), cap.ctypes.data_as(u64p), C.byref(p), C.byref(fp), C.byref(circuit),
+                                              (C.c_uint64 * 4)(*[int(x) for x in digest]), (C.c_uint32 * 8)(*words), C.byref(reason))
+    if rc not in (0, SIPP_E_VERIFY):
+        raise SippError(rc, "sipp_plonk_verify_gates_lookup")
+    return reason.value
 
 
 def stark_verify(proof, cfg=None):
@@ -421,6 +448,36 @@ class Ctx:
                                                        self._u64(gammas), out.data_ptr()), "plonk_zs_partial_products")
         return out
 
+    # ---- lookup tables by a log-derivative argument (include/sipp_hip.h: the eight-word description) ----
+    @staticmethod
+    def _lookup_words(lookup):
+        words = [int(x) for x in lookup]
+        if len(words) != 8:
+            raise SippError(-1, "a lookup description is eight words")
+        return (C.c_uint32 * 8)(*words)
+
+    def plonk_lookup_multiplicities(self, wires, constants, log_n, num_selectors, lookup):
+        """sipp_plonk_lookup_multiplicities: wires [W, N], constants [K, N] device int64; the m cells of `wires` are rewritten in place"""
+        assert wires.is_cuda and wires.is_contiguous() and constants.is_cuda and constants.is_contiguous()
+        assert wires.shape[1] == constants.shape[1] == 1 << log_n
+        self._ck(self.L.sipp_plonk_lookup_multiplicities(self.h, wires.data_ptr(), constants.data_ptr(), log_n, wires.shape[0],
+                                                         constants.shape[0], num_selectors, self._lookup_words(lookup)),
+                 "plonk_lookup_multiplicities")
+        return wires
+
+    def plonk_lookup_sums(self, wires, constants, log_n, num_selectors, p, lookup, etas, thetas):
+        """sipp_plonk_lookup_sums: wires [W, N], constants [K, N] device int64 -> [C J, N]: S_0 .. S_(C-1), then the U's per challenge"""
+        import torch
+        assert wires.is_cuda and wires.is_contiguous() and constants.is_cuda and constants.is_contiguous()
+        assert wires.shape[1] == constants.shape[1] == 1 << log_n
+        words = self._lookup_words(lookup)
+        rows = self.L.sipp_plonk_lookup_num_columns(C.byref(p), words)
+        out = torch.empty((rows, 1 << log_n), dtype=torch.int64, device=wires.device)
+        self._ck(self.L.sipp_plonk_lookup_sums(self.h, wires.data_ptr(), constants.data_ptr(), log_n, wires.shape[0], constants.shape[0],
+                                               num_selectors, C.byref(p), words, self._u64(etas), self._u64(thetas), out.data_ptr()),
+                 "plonk_lookup_sums")
+        return out
+
     def plonk_quotient_chunks(self, wires_lde, sigmas_lde, zs_lde, log_n, rate_bits, p, betas, gammas, alphas):
         import torch
         out = torch.empty((p.num_challenges * p.max_degree, 1 << log_n), dtype=torch.int64, device=wires_lde.device)
@@ -477,6 +534,26 @@ class Ctx:
                                                None if cs_oracle is None else C.byref(cs_oracle), log_n, C.byref(p), C.byref(fp), C.byref(circuit),
                                                self._u64(digest), self._u64(pis) if pis else None, len(pis), out.ctypes.data, cap, C.byref(n)),
                  "plonk_prove_gates")
+        return out[: n.value]
+
+    def plonk_prove_gates_lookup(self, wires, constants_sigmas, log_n, p, fp, circuit, digest, public_inputs, lookup, wires_oracle=None,
+                                 wires_cap=None, cs_oracle=None):
+        """sipp_plonk_prove_gates_lookup: plonk_prove_gates with a lookup description (eight words); the wire table holds the
+        multiplicities already.  Returns the flat "SIPPPLK4" proof -- "SIPPPLK3", word for word plonk_prove_gates', for an empty one."""
+        pis = [int(x) for x in public_inputs]
+        words = self._lookup_words(lookup)
+        cap = self.L.sipp_plonk_gates_lookup_proof_size(log_n, C.byref(p), C.byref(fp), C.byref(circuit), len(pis), words)
+        if cap == 0:
+            raise SippError(-1, "sipp_plonk_gates_lookup_proof_size")
+        out = np.zeros(cap, dtype=np.uint64)
+        n = C.c_size_t()
+        wc_arr = None if wires_cap is None else np.ascontiguousarray(wires_cap, dtype=np.uint64).reshape(-1)
+        wcap = None if wc_arr is None else wc_arr.ctypes.data_as(u64p)
+        self._ck(self.L.sipp_plonk_prove_gates_lookup(self.h, wires.data_ptr(), constants_sigmas.data_ptr(),
+                                                      None if wires_oracle is None else C.byref(wires_oracle), wcap,
+                                                      None if cs_oracle is None else C.byref(cs_oracle), log_n, C.byref(p), C.byref(fp),
+                                                      C.byref(circuit), self._u64(digest), self._u64(pis) if pis else None, len(pis), words,
+                                                      out.ctypes.data, cap, C.byref(n)), "plonk_prove_gates_lookup")
         return out[: n.value]
 
     def plonk_generate_witness(self, wires, constants, log_n, gens, pih=None):
@@ -792,6 +869,7 @@ class CircuitData:
         ctx._ck(self.L.sipp_circuit_verifier_data(self.h, cap.ctypes.data, dg.ctypes.data), "circuit_verifier_data")
         self.cap, self.digest = cap, dg
         self.input_map = None                              # (n_words, n_extra) once set_input_map has been served
+        self.lookup = None                                 # the eight words once set_lookup has been served
 
     def prove(self, wires, public_inputs):
         w = np.ascontiguousarray(wires, dtype=np.uint64)
@@ -852,6 +930,12 @@ class CircuitData:
                                                      pis.ctypes.data_as(C.POINTER(C.c_uint64)) if len(pis) else None, len(pis), out.ctypes.data, cap,
                                                      C.byref(n)), "circuit_prove_words")
         return out[: n.value]
+
+    def set_lookup(self, lookup):
+        """sipp_circuit_set_lookup: the eight-word lookup description; every later prove call runs the multiplicities behind witness
+        generation and proves the lookup argument ("SIPPPLK4"), verify() checks it.  An empty description takes it off again."""
+        self.ctx._ck(self.L.sipp_circuit_set_lookup(self.h, Ctx._lookup_words(lookup)), "circuit_set_lookup")
+        self.lookup = tuple(int(x) for x in lookup)
 
     def verify(self, proof):
         """-> (status, refusing stage): (0, 0) = accepted"""

@@ -10,7 +10,9 @@ gate programs more than one of them uses, the builder that turns rows and feeds 
   CircuitBuilder            the gate registry (selector groups, programs, generators); rows by new_row(); wiring by place(), which ties
                             the cells, schedules the copies and gives every row the level behind its latest computed source, and tie();
                             the public-input Poseidon chain; finish(), which fixes N and makes the cycles and the level schedule.  A
-                            circuit is a subclass: it declares its gates, writes its statement as builder calls and finishes
+                            circuit is a subclass: it declares its gates, writes its statement as builder calls and finishes.
+                            Lookups (one table, include/sipp_hip.h "LOOKUP TABLES"): declare_lookup() names two zero-constraint gates,
+                            table() writes the table rows, lookup() / range_check() fill looking rows; the description rides in circuit()
   _Challenger               plonky2's RecursiveChallenger on a builder (sipp_amd/fri_proof.py says how it buffers and duplexes)
   CircuitProver             a built circuit through the library's CircuitData
 
@@ -213,6 +215,7 @@ class CircuitBuilder:
         self._uf, self._copies = _Cells(), []                   # copies: (level of the source, src cell, dst cell)
         self._pi_cells = [None] * n_pi                          # one cell of public input t: every cell of its cycle takes its value
         self._in_cells = []                                     # the same for the witness inputs
+        self._lk = None                                         # declare_lookup()'s layout; without one nothing below changes
 
     # ---- gates ----
     def declare(self, index, degree, gen=None, fill=None, *args):
@@ -306,9 +309,74 @@ class CircuitBuilder:
         for t in range(4):
             self.tie((self.s_out + t, self.chain_row[-1]), (t, self.pi_row))
 
+    # ---- lookups: one table in constant columns, the multiplicities in wires ----
+    def declare_lookup(self, table_gate, looking_gate, n_look, n_tab, look_wire0=0, tab_mult0=None):
+        """table_gate, looking_gate: two gates declared with no constraints (declare(index, 0)) that only mark the table rows and the
+        looking rows.  A looking row holds n_look pairs in the routed wires look_wire0 ..; a table row holds n_tab pairs in constant
+        columns of their own behind the builder's, its multiplicities in the wires tab_mult0 .. (default: behind the looking wires).
+        The constant columns grow by q_look, q_tab and the 2 n_tab table columns."""
+        assert self._lk is None and 1 <= n_look <= 128 and 1 <= n_tab <= 128
+        tab_mult0 = look_wire0 + 2 * n_look if tab_mult0 is None else tab_mult0
+        assert look_wire0 + 2 * n_look <= self.num_routed and tab_mult0 + n_tab <= self.num_wires
+        k = self.num_constants
+        self._lk = {"table_gate": table_gate, "looking_gate": looking_gate, "n_look": n_look, "n_tab": n_tab, "look_wire0": look_wire0,
+                    "tab_mult0": tab_mult0, "q_look": k, "q_tab": k + 1, "tab_const0": k + 2, "entries": None, "table_rows": [],
+                    "pending": [], "zero": None}
+        self.num_constants = k + 2 + 2 * n_tab
+
+    def table(self, entries):
+        """the table: (x, y) pairs (a range table: (v, 0)).  Table rows are written here; the slots the last row has left repeat the last
+        entry.  -> the entries, as range_check()'s `table` argument"""
+        lk = self._lk
+        assert lk is not None and lk["entries"] is None and len(entries) >= 1
+        ent = [(int(x) % P, int(y) % P) for x, y in entries]
+        for at in range(0, len(ent), lk["n_tab"]):
+            r = self.new_row(lk["table_gate"])
+            self.place(r)
+            lk["table_rows"].append((r, (ent[at:at + lk["n_tab"]] + [ent[-1]] * lk["n_tab"])[:lk["n_tab"]]))
+        lk["entries"] = ent
+        return ent
+
+    def lookup(self, x_source, y_source):
+        """the pair (x, y) must be a table entry.  Pairs are gathered n_look to a looking row; a row that stays short repeats its first
+        pair (flush_lookups(), which finish() calls)"""
+        lk = self._lk
+        assert lk is not None and lk["entries"] is not None
+        lk["pending"].append((x_source, y_source))
+        if len(lk["pending"]) == lk["n_look"]:
+            self.flush_lookups()
+
+    def range_check(self, x_source, table=None):
+        """x is the first coordinate of an entry (x, 0): a lookup of (x, 0) against a range table"""
+        lk = self._lk
+        assert table is None or table is lk["entries"], "one table a circuit"
+        if lk["zero"] is None:
+            lk["zero"] = self.constant(0)[1]
+        self.lookup(x_source, lk["zero"])
+
+    def flush_lookups(self):
+        lk = self._lk
+        if lk is None or not lk["pending"]:
+            return
+        pairs = (lk["pending"] + [lk["pending"][0]] * lk["n_look"])[:lk["n_look"]]
+        lk["pending"] = []
+        r = self.new_row(lk["looking_gate"])
+        feeds = []
+        for k, (xs, ys) in enumerate(pairs):
+            feeds += [(lk["look_wire0"] + 2 * k, xs), (lk["look_wire0"] + 2 * k + 1, ys)]
+        self.place(r, feeds)
+
+    def lookup_description(self):
+        """the eight words of include/sipp_hip.h; all zero without a declared lookup"""
+        lk = self._lk
+        if lk is None:
+            return (0,) * 8
+        return (lk["q_look"], lk["look_wire0"], lk["n_look"], lk["q_tab"], lk["tab_const0"], lk["tab_mult0"], lk["n_tab"], 0)
+
     def finish(self, min_log_n):
         """N is known: cells become wire * N + row.  min_log_n: the device prover's FRI takes degree bits 10 .. 24; smaller circuits
         are padded with Noop rows"""
+        self.flush_lookups()
         assert len(self.gates) == len(self.gate_names)
         self.programs = np.array(self._prog.words, dtype=np.int64)
         rows = self._rows
@@ -346,9 +414,12 @@ class CircuitBuilder:
     # ---- the public face ----
     def circuit(self):
         """the circuit dict of tools/plonk_synth.circuit(): num_wires, num_routed, num_constants, num_selectors, gates, programs"""
-        return {"num_wires": self.num_wires, "num_routed": self.num_routed, "num_constants": self.num_constants,
-                "num_selectors": self.num_selectors, "gates": list(self.gates), "programs": self.programs,
-                "num_gate_constraints": max(g[5] for g in self.gates), "gate_names": self.gate_names}
+        out = {"num_wires": self.num_wires, "num_routed": self.num_routed, "num_constants": self.num_constants,
+               "num_selectors": self.num_selectors, "gates": list(self.gates), "programs": self.programs,
+               "num_gate_constraints": max(g[5] for g in self.gates), "gate_names": self.gate_names}
+        if self._lk is not None:
+            out["lookup"] = self.lookup_description()
+        return out
 
     def generators(self):
         """[(kind, selector_index, row, p0 .. p4)] (include/sipp_hip.h sipp_plonk_generator)"""
@@ -374,8 +445,21 @@ class CircuitBuilder:
         sig = np.empty((R, n), dtype=np.uint64)
         for j in range(R):
             sig[j] = _gl_mul(ks[pm[j] >> self.log_n], pw[pm[j] & (n - 1)])
-        consts = [self.c0, self.c1][:self.num_constants - self.num_selectors]
+        consts = [self.c0, self.c1][:self.k_lookup0() - self.num_selectors]
+        if self._lk is not None:
+            lk = self._lk
+            cols = np.zeros((2 + 2 * lk["n_tab"], n), dtype=np.uint64)
+            cols[0] = self.gate == lk["looking_gate"]
+            cols[1] = self.gate == lk["table_gate"]
+            for r, slots in lk["table_rows"]:
+                for k, (x, y) in enumerate(slots):
+                    cols[2 + 2 * k][r], cols[3 + 2 * k][r] = x, y
+            consts = consts + list(cols)
         return np.ascontiguousarray(np.concatenate([np.stack(sels + consts), sig]).astype(np.uint64))
+
+    def k_lookup0(self):
+        """the first constant column of the lookup argument (= num_constants without one)"""
+        return self.num_constants if self._lk is None else self._lk["q_look"]
 
     def public_input_witness(self, pis):
         """[num_wires][N] with every cell on a cycle of a public input set (plonky2's PartialWitness), everything else 0: the generators
@@ -427,6 +511,8 @@ class CircuitProver:
         self._pc = _lib.PlonkCircuit.from_dict(self.circuit)
         self.data = _lib.CircuitData(ctx, c.log_n, self.params, self.fri, self._pc, c.constants_sigmas(), c.generators(), sched=c.schedule(),
                                      digest=digest)
+        if "lookup" in self.circuit:      # the description rides in circuit(): the multiplicities and the argument on every prove path
+            self.data.set_lookup(self.circuit["lookup"])
         self.cap, self.digest = self.data.cap, self.data.digest
 
     def prove(self, *inputs):

@@ -28,10 +28,16 @@ struct sipp_circuit_data {
     uint64_t* d_map = nullptr;
     size_t map_n = 0, map_words = 0, map_extra = 0;
     bool has_map = false;
+    // the lookup description of sipp_circuit_set_lookup (all zero: none) and the sorted index of its table, a block of its own like the map
+    uint32_t lookup[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    uint64_t* d_index = nullptr;
+    uint32_t n_index = 0;
+    bool has_lookup() const { return lookup[2] != 0; }
     ~sipp_circuit_data() {
         if (ctx) (void)hipSetDevice(ctx->device);
         for (void* q : dev) (void)hipFree(q);
         if (d_map) (void)hipFree(d_map);
+        if (d_index) (void)hipFree(d_index);
     }
 };
 
@@ -162,7 +168,7 @@ extern "C" int sipp_circuit_verifier_data(const sipp_circuit_data* cd, uint64_t*
 }
 
 extern "C" size_t sipp_circuit_proof_size(const sipp_circuit_data* cd, uint32_t n_public_inputs) {
-    return cd ? sipp_plonk_gates_proof_size(cd->log_n, &cd->p, &cd->fp, &cd->circ, n_public_inputs) : 0;
+    return cd ? sipp_plonk_gates_lookup_proof_size(cd->log_n, &cd->p, &cd->fp, &cd->circ, n_public_inputs, cd->lookup) : 0;
 }
 
 namespace {
@@ -178,8 +184,13 @@ int prove_uploaded(sipp_circuit_data* cd, const uint64_t* public_inputs, uint32_
     else
         SIPP_TRY(sipp_plonk_generate_witness(ctx, cd->d_wires, cd->d_cs, cd->log_n, cd->circ.num_wires, cd->circ.num_constants, cd->gens.data(),
                                              cd->gens.size(), pih));
-    return sipp_plonk_prove_gates(ctx, cd->d_wires, cd->d_cs, nullptr, nullptr, &cd->cs_oracle, cd->log_n, &cd->p, &cd->fp, &cd->circ, cd->digest,
-                                  public_inputs, n_public_inputs, proof_out, proof_cap, proof_len);
+    if (!cd->has_lookup())
+        return sipp_plonk_prove_gates(ctx, cd->d_wires, cd->d_cs, nullptr, nullptr, &cd->cs_oracle, cd->log_n, &cd->p, &cd->fp, &cd->circ, cd->digest,
+                                      public_inputs, n_public_inputs, proof_out, proof_cap, proof_len);
+    // the multiplicities behind witness generation: the looking wires are the generators' outputs (or the caller's cells)
+    SIPP_TRY(sipp_lookup_multiplicities_indexed(ctx, cd->d_wires, cd->d_cs, cd->log_n, cd->lookup, cd->d_index, cd->n_index));
+    return sipp_plonk_prove_gates_lookup(ctx, cd->d_wires, cd->d_cs, nullptr, nullptr, &cd->cs_oracle, cd->log_n, &cd->p, &cd->fp, &cd->circ,
+                                         cd->digest, public_inputs, n_public_inputs, cd->lookup, proof_out, proof_cap, proof_len);
 }
 
 // the input cells of sipp_circuit_prove_inputs: one lane per pair, grid-stride.  Pairs that name one cell race; whichever store lands,
@@ -237,6 +248,36 @@ extern "C" int sipp_circuit_set_input_map(sipp_circuit_data* cd, const uint64_t*
         (void)hipFree(cd->d_map);
     }
     cd->d_map = d_new; cd->map_n = n; cd->map_words = n_words; cd->map_extra = n_extra; cd->has_map = true;
+    return SIPP_OK;
+}
+
+extern "C" int sipp_circuit_set_lookup(sipp_circuit_data* cd, const uint32_t* lookup) {
+    if (!cd) return SIPP_E_BADARG;
+    sipp_ctx* ctx = cd->ctx;
+    SIPP_TRY(sipp_lookup_check(ctx, lookup, cd->circ.num_wires, cd->circ.num_constants, cd->circ.num_selectors));
+    SIPP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    const bool empty = lookup[2] == 0 && lookup[6] == 0;
+    uint64_t* d_new = nullptr;
+    std::vector<uint64_t> index;
+    if (!empty) {
+        if (sipp_plonk_gates_lookup_proof_size(cd->log_n, &cd->p, &cd->fp, &cd->circ, 0, lookup) == 0)
+            return sipp_fail(ctx, SIPP_E_BADARG, "circuit lookup: the description does not fit the parameters");
+        SIPP_TRY(sipp_lookup_index_host(ctx, cd->d_cs, cd->log_n, lookup, &index));
+        void* q = nullptr;
+        if (hipMalloc(&q, (index.empty() ? 1 : index.size()) * 8) != hipSuccess) return sipp_fail(ctx, SIPP_E_NOMEM, "circuit lookup: hipMalloc failed");
+        d_new = reinterpret_cast<uint64_t*>(q);
+        if (!index.empty() && hipMemcpy(d_new, index.data(), index.size() * 8, hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipFree(q);
+            return sipp_fail(ctx, SIPP_E_HIP, "circuit lookup: upload failed");
+        }
+    }
+    // the old index goes only now: every refusal above has left the description before in force.  No kernel reads it: a proof ends on the host
+    if (cd->d_index) {
+        (void)hipStreamSynchronize(ctx->stream);
+        (void)hipFree(cd->d_index);
+    }
+    cd->d_index = d_new; cd->n_index = (uint32_t)(index.size() / 3);
+    for (int q = 0; q < 8; q++) cd->lookup[q] = empty ? 0 : lookup[q];
     return SIPP_OK;
 }
 
@@ -330,5 +371,5 @@ extern "C" int sipp_circuit_prove_words(sipp_circuit_data* cd, const uint64_t* w
 
 extern "C" int sipp_circuit_verify(const sipp_circuit_data* cd, const uint64_t* proof, size_t len, int* reason) {
     if (!cd) return SIPP_E_BADARG;
-    return sipp_plonk_verify_gates(proof, len, cd->cap.data(), &cd->p, &cd->fp, &cd->circ, cd->digest, reason);
+    return sipp_plonk_verify_gates_lookup(proof, len, cd->cap.data(), &cd->p, &cd->fp, &cd->circ, cd->digest, cd->lookup, reason);
 }

@@ -258,6 +258,17 @@ int sipp_k_merkle_levels(sipp_ctx* ctx, uint64_t* d_tree, uint32_t log_leaves, u
 int sipp_k_poseidon_permute(sipp_ctx* ctx, uint64_t* d_states, size_t n);
 void sipp_witness_graph_release(sipp_ctx* ctx);   // witness.hip
 int sipp_plonk_circuit_check(sipp_ctx* ctx, const sipp_plonk_circuit* c, const sipp_plonk_params* p);   // plonk.hip
+// lookup.hip -- a lookup description is the eight words of include/sipp_hip.h.  _check: its refusals (an empty one passes);
+// _index_host: the sorted index of the table's distinct pairs (kx | ky | cell, a third of the vector each), built once per circuit;
+// _multiplicities_indexed: sipp_plonk_lookup_multiplicities over an index the caller keeps on the device; _quotient_terms: adds
+// Z_H^-1 sum_k alpha^(terms_in_front + k) term_k over the quotient coset into d_qv [C][N D] (leaf order, in front of the coset iNTT).
+int sipp_lookup_check(sipp_ctx* ctx, const uint32_t* lookup, uint32_t num_wires, uint32_t num_constants, uint32_t num_selectors);
+int sipp_lookup_index_host(sipp_ctx* ctx, const uint64_t* d_constants, uint32_t log_n, const uint32_t* lookup, std::vector<uint64_t>* out);
+int sipp_lookup_multiplicities_indexed(sipp_ctx* ctx, uint64_t* d_wires, const uint64_t* d_constants, uint32_t log_n, const uint32_t* lookup,
+                                       const uint64_t* d_index, uint32_t n_index);
+int sipp_lookup_quotient_terms(sipp_ctx* ctx, const uint64_t* d_wires_lde, const uint64_t* d_consts_lde, const uint64_t* d_sums_lde, uint32_t log_n,
+                               uint32_t rate_bits, const sipp_plonk_params* p, const uint32_t* lookup, const uint64_t* etas, const uint64_t* thetas,
+                               const uint64_t* alphas, uint64_t terms_in_front, uint64_t* d_qv);
 
 // ---- AIR layer (trace.hip / quotient.hip / stark.hip) -----------------------------------------
 #include "air_tables.h"

@@ -323,16 +323,22 @@ struct GateSet {
     const sipp_plonk_circuit* c;
     const uint64_t* pih;
 };
+// the lookup argument's terms behind the gate constraints (lookup.hip): the description, its challenges, the S / U columns' LDE
+struct LookupSet {
+    const uint32_t* words;
+    const uint64_t *etas, *thetas;
+    const uint64_t* d_sums_lde;
+};
 int quotient_chunks_impl(sipp_ctx* ctx, const uint64_t* d_wires_lde, const uint64_t* d_sigmas_lde, const uint64_t* d_zs_lde, uint32_t log_n,
                          uint32_t rate_bits, const sipp_plonk_params* p, const uint64_t* betas, const uint64_t* gammas, const uint64_t* alphas,
-                         const uint64_t* d_gate_terms, uint32_t num_gate_terms, const GateSet* gs, uint64_t* d_chunks);
+                         const uint64_t* d_gate_terms, uint32_t num_gate_terms, const GateSet* gs, const LookupSet* ls, uint64_t* d_chunks);
 }  // namespace
 
 int sipp_plonk_quotient_chunks_ex(sipp_ctx* ctx, const uint64_t* d_wires_lde, const uint64_t* d_sigmas_lde, const uint64_t* d_zs_lde, uint32_t log_n,
                                   uint32_t rate_bits, const sipp_plonk_params* p, const uint64_t* betas, const uint64_t* gammas,
                                   const uint64_t* alphas, const uint64_t* d_gate_terms, uint32_t num_gate_terms, uint64_t* d_chunks) {
     return quotient_chunks_impl(ctx, d_wires_lde, d_sigmas_lde, d_zs_lde, log_n, rate_bits, p, betas, gammas, alphas, d_gate_terms, num_gate_terms,
-                                nullptr, d_chunks);
+                                nullptr, nullptr, d_chunks);
 }
 
 namespace {
@@ -446,7 +452,7 @@ int circuit_check(sipp_ctx* ctx, const sipp_plonk_circuit* c, const sipp_plonk_p
 
 int quotient_chunks_impl(sipp_ctx* ctx, const uint64_t* d_wires_lde, const uint64_t* d_sigmas_lde, const uint64_t* d_zs_lde, uint32_t log_n,
                          uint32_t rate_bits, const sipp_plonk_params* p, const uint64_t* betas, const uint64_t* gammas, const uint64_t* alphas,
-                         const uint64_t* d_gate_terms, uint32_t num_gate_terms, const GateSet* gs, uint64_t* d_chunks) {
+                         const uint64_t* d_gate_terms, uint32_t num_gate_terms, const GateSet* gs, const LookupSet* ls, uint64_t* d_chunks) {
     if ((num_gate_terms != 0) != (d_gate_terms != nullptr) || num_gate_terms > (1u << 20)) return ctx ? sipp_fail(ctx, SIPP_E_BADARG, "plonk: gate terms and their count disagree") : SIPP_E_BADARG;
 
     if (!ctx || !d_wires_lde || !d_sigmas_lde || !d_zs_lde || !betas || !gammas || !alphas || !d_chunks) return SIPP_E_BADARG;
@@ -514,6 +520,9 @@ int quotient_chunks_impl(sipp_ctx* ctx, const uint64_t* d_wires_lde, const uint6
         hipLaunchKernelGGL(plonk_quotient_kernel, dim3((unsigned)((nd + 255) / 256)), dim3(256), 0, ctx->stream, a);
     }
     SIPP_CHECK_HIP(ctx, hipGetLastError());
+    if (ls)      // the lookup terms follow the gate constraints in the one reduce_with_powers list: a kernel of its own adds them
+        SIPP_TRY(sipp_lookup_quotient_terms(ctx, d_wires_lde, gs->d_consts_lde, ls->d_sums_lde, log_n, rate_bits, p, ls->words, ls->etas, ls->thetas,
+                                            alphas, (uint64_t)C + (uint64_t)C * m + num_gate_terms + num_gate_constraints(gs->c), d_chunks));
     // coset_ifft(7): leaf-order values -> natural coefficients; [C][n D] natural == [C D][n] chunks
     SIPP_TRY(sipp_ntt_dit(ctx, d_chunks, nd, log_n + log_d, C, true, NttDiag{gl::inv(gl::GEN), 0}));
     return sipp_sync(ctx);
@@ -540,6 +549,9 @@ struct PlonkExtra {
     // gates as data ("SIPPPLK3"): d_wires holds circ->num_wires columns, d_sigmas is the WHOLE constants_sigmas batch (num_constants
     // columns in front of the sigmas)
     const sipp_plonk_circuit* circ = nullptr;
+    // a NON-EMPTY lookup description ("SIPPPLK4", with circ): the S / U columns behind the permutation's in the zs_partial_products
+    // oracle, eta / theta drawn behind the gammas, the lookup terms behind the gate constraints
+    const uint32_t* lookup = nullptr;
 };
 int plonk_prove_impl(sipp_ctx* ctx, const uint64_t* d_wires, const uint64_t* d_sigmas, uint32_t log_n, const sipp_plonk_params* p,
                      const sipp_fri_params* fp, const uint64_t circuit_digest[4], const uint64_t public_inputs_hash[4], const PlonkExtra& ex,
@@ -550,21 +562,25 @@ int plonk_prove_impl(sipp_ctx* ctx, const uint64_t* d_wires, const uint64_t* d_s
 // m = chunks of routed wires (check()).
 struct PlonkLayout {
     uint32_t ncols[4];
-    sipp_poly_range at_zeta[4], at_gzeta[1];
-    size_t header_words;      // 8, or 16 with the gates as data ("SIPPPLK3")
-    PlonkLayout(const sipp_plonk_params* p, uint32_t m, const sipp_plonk_circuit* circ) {
+    sipp_poly_range at_zeta[4], at_gzeta[2];
+    uint32_t n_gzeta;         // 1, or 2 with lookups: the S columns behind the Z columns
+    size_t header_words;      // 8, 16 with the gates as data ("SIPPPLK3"), 24 with a lookup description ("SIPPPLK4")
+    PlonkLayout(const sipp_plonk_params* p, uint32_t m, const sipp_plonk_circuit* circ, const uint32_t* lookup = nullptr) {
         const uint32_t R = p->num_routed_wires, C = p->num_challenges;
-        const uint32_t nc[4] = {(circ ? circ->num_constants : 0) + R, circ ? circ->num_wires : R, C * m, C * p->max_degree};
+        const uint32_t n_lk = lookup ? sipp_plonk_lookup_num_columns(p, lookup) : 0;
+        const uint32_t nc[4] = {(circ ? circ->num_constants : 0) + R, circ ? circ->num_wires : R, C * m + n_lk, C * p->max_degree};
         for (uint32_t o = 0; o < 4; o++) {
             ncols[o] = nc[o];
             at_zeta[o] = sipp_poly_range{o, 0, nc[o]};
         }
         at_gzeta[0] = sipp_poly_range{2, 0, C};
-        header_words = circ ? 16 : 8;
+        at_gzeta[1] = sipp_poly_range{2, C * m, C * m + C};
+        n_gzeta = n_lk ? 2 : 1;
+        header_words = n_lk ? 24 : circ ? 16 : 8;
     }
     void batches(gl::E2 zeta, gl::E2 gzeta, sipp_fri_batch out[2]) const {
         out[0] = sipp_fri_batch{{zeta.c0, zeta.c1}, 4, at_zeta};
-        out[1] = sipp_fri_batch{{gzeta.c0, gzeta.c1}, 1, at_gzeta};
+        out[1] = sipp_fri_batch{{gzeta.c0, gzeta.c1}, n_gzeta, at_gzeta};
     }
     // u64 words in front of the opening proof (header, the three caps the proof carries) and of the opening proof itself (0: the
     // FRI parameters do not fit the degree)
@@ -581,10 +597,10 @@ struct PlonkLayout {
 };
 // words of a whole proof; 0 when check() refuses the parameters or the FRI parameters do not fit
 size_t plonk_proof_words(uint32_t log_n, const sipp_plonk_params* p, const sipp_fri_params* fp, const sipp_plonk_circuit* circ,
-                         uint32_t n_public_inputs) {
+                         uint32_t n_public_inputs, const uint32_t* lookup = nullptr) {
     uint32_t log_d, m;
     if (!fp || check(nullptr, p, log_n, &log_d, &m) != SIPP_OK) return 0;
-    const PlonkLayout lay(p, m, circ);
+    const PlonkLayout lay(p, m, circ, lookup);
     const size_t op = lay.opening_words(log_n, fp);
     return op ? lay.head_words(log_n, fp) + op + n_public_inputs : 0;
 }
@@ -630,8 +646,8 @@ int plonk_prove_impl(sipp_ctx* ctx, const uint64_t* d_wires, const uint64_t* d_s
     const uint32_t R = p->num_routed_wires, D = p->max_degree, C = p->num_challenges, nz = C * m;
     const size_t n = (size_t)1 << log_n, M = n << fp->rate_bits, cap_n = (size_t)1 << std::min(fp->cap_height, log_n + fp->rate_bits);
     const uint32_t K = ex.circ ? ex.circ->num_constants : 0, Wn = ex.circ ? ex.circ->num_wires : R;
-    const PlonkLayout lay(p, m, ex.circ);
-    const uint32_t* ncols = lay.ncols;
+    const PlonkLayout lay(p, m, ex.circ, ex.lookup);
+    const uint32_t* ncols = lay.ncols;             // (ncols[2] = nz + the S / U columns of a lookup description)
     const uint64_t* d_sigma_vals = d_sigmas + (size_t)K * n;      // the sigmas behind the constant columns
     uint64_t *co[4], *lde[4], *tree[4];
     const sipp_oracle* pre[4] = {ex.sigmas_oracle, ex.wires_oracle, nullptr, nullptr};
@@ -662,18 +678,26 @@ int plonk_prove_impl(sipp_ctx* ctx, const uint64_t* d_wires, const uint64_t* d_s
     uint64_t betas[MAX_CH], gammas[MAX_CH], alphas[MAX_CH];
     for (uint32_t c = 0; c < C; c++) betas[c] = ch.get();
     for (uint32_t c = 0; c < C; c++) gammas[c] = ch.get();
+    uint64_t etas[MAX_CH], thetas[MAX_CH];
+    if (ex.lookup) {      // drawn only with a description: a circuit without lookups keeps its transcript
+        for (uint32_t c = 0; c < C; c++) etas[c] = ch.get();
+        for (uint32_t c = 0; c < C; c++) thetas[c] = ch.get();
+    }
     {
-        uint64_t* zs = arena_alloc_t<uint64_t>(ctx, (size_t)nz * n);
+        uint64_t* zs = arena_alloc_t<uint64_t>(ctx, (size_t)ncols[2] * n);
         if (!zs) return SIPP_E_NOMEM;
         SIPP_TRY(sipp_plonk_zs_partial_products(ctx, d_wires, d_sigma_vals, log_n, p, betas, gammas, zs));
-        SIPP_TRY(sipp_commit_batch_ex(ctx, zs, 0, co[2], lde[2], tree[2], nz, log_n, fp->rate_bits, fp->cap_height, nullptr, 0, cap_of(2)));
+        if (ex.lookup)
+            SIPP_TRY(sipp_plonk_lookup_sums(ctx, d_wires, d_sigmas, log_n, Wn, K, ex.circ->num_selectors, p, ex.lookup, etas, thetas, zs + (size_t)nz * n));
+        SIPP_TRY(sipp_commit_batch_ex(ctx, zs, 0, co[2], lde[2], tree[2], ncols[2], log_n, fp->rate_bits, fp->cap_height, nullptr, 0, cap_of(2)));
     }
     ch.observe_many(cap_of(2), cap_n * 4);
     for (uint32_t c = 0; c < C; c++) alphas[c] = ch.get();
     {
         const GateSet gs{lde[0], ex.circ, public_inputs_hash};
+        const LookupSet ls{ex.lookup, etas, thetas, lde[2] + (size_t)nz * M};
         SIPP_TRY(quotient_chunks_impl(ctx, lde[1], lde[0] + (size_t)K * M, lde[2], log_n, fp->rate_bits, p, betas, gammas, alphas, ex.d_gate_terms,
-                                      ex.n_gate_terms, ex.circ ? &gs : nullptr, co[3]));
+                                      ex.n_gate_terms, ex.circ ? &gs : nullptr, ex.lookup ? &ls : nullptr, co[3]));
     }
     SIPP_TRY(sipp_commit_batch_ex(ctx, co[3], 1, co[3], lde[3], tree[3], (size_t)C * D, log_n, fp->rate_bits, fp->cap_height, nullptr, 0, cap_of(3)));
     ch.observe_many(cap_of(3), cap_n * 4);
@@ -690,7 +714,12 @@ int plonk_prove_impl(sipp_ctx* ctx, const uint64_t* d_wires, const uint64_t* d_s
     ch.store(&cs);
     size_t op_len = 0;
     SIPP_TRY(sipp_fri_prove_openings(ctx, oracles, 4, batches, 2, log_n, fp, &cs, proof_out + head, proof_cap - head - tail, &op_len));
-    if (ex.circ) {
+    if (ex.lookup) {
+        uint64_t h[24] = {0x344b4c5050504953ULL /* "SIPPPLK4" */, log_n, R, D, C, head + op_len + tail, Wn, K, ex.circ->num_selectors,
+                          ex.circ->num_gates, num_gate_constraints(ex.circ), tail, 0, 0, 0, 0};
+        for (int q = 0; q < 8; q++) h[16 + q] = ex.lookup[q];
+        memcpy(proof_out, h, sizeof h);
+    } else if (ex.circ) {
         const uint64_t h[16] = {0x334b4c5050504953ULL /* "SIPPPLK3" */, log_n, R, D, C, head + op_len + tail, Wn, K, ex.circ->num_selectors,
                                 ex.circ->num_gates, num_gate_constraints(ex.circ), tail, 0, 0, 0, 0};
         memcpy(proof_out, h, sizeof h);
@@ -719,14 +748,37 @@ size_t sipp_plonk_gates_proof_size(uint32_t log_n, const sipp_plonk_params* p, c
     return plonk_proof_words(log_n, p, fp, c, n_public_inputs);
 }
 
+namespace {
+bool lookup_empty(const uint32_t* lookup) { return !lookup || (lookup[2] == 0 && lookup[6] == 0); }
+}  // namespace
+
+size_t sipp_plonk_gates_lookup_proof_size(uint32_t log_n, const sipp_plonk_params* p, const sipp_fri_params* fp, const sipp_plonk_circuit* c,
+                                          uint32_t n_public_inputs, const uint32_t* lookup) {
+    if (!c || !p || c->num_wires < p->num_routed_wires || c->num_wires > 4096 || c->num_constants > 1024) return 0;
+    if (sipp_lookup_check(nullptr, lookup, c->num_wires, c->num_constants, c->num_selectors) != SIPP_OK) return 0;
+    return plonk_proof_words(log_n, p, fp, c, n_public_inputs, lookup_empty(lookup) ? nullptr : lookup);
+}
+
 int sipp_plonk_prove_gates(sipp_ctx* ctx, const uint64_t* d_wires, const uint64_t* d_constants_sigmas, const sipp_oracle* wires_oracle,
                            const uint64_t* wires_cap, const sipp_oracle* constants_sigmas_oracle, uint32_t log_n, const sipp_plonk_params* p,
                            const sipp_fri_params* fp, const sipp_plonk_circuit* c, const uint64_t circuit_digest[4], const uint64_t* public_inputs,
                            uint32_t n_public_inputs, uint64_t* proof_out, size_t proof_cap, size_t* proof_len) {
+    static const uint32_t none[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    return sipp_plonk_prove_gates_lookup(ctx, d_wires, d_constants_sigmas, wires_oracle, wires_cap, constants_sigmas_oracle, log_n, p, fp, c,
+                                         circuit_digest, public_inputs, n_public_inputs, none, proof_out, proof_cap, proof_len);
+}
+
+int sipp_plonk_prove_gates_lookup(sipp_ctx* ctx, const uint64_t* d_wires, const uint64_t* d_constants_sigmas, const sipp_oracle* wires_oracle,
+                                  const uint64_t* wires_cap, const sipp_oracle* constants_sigmas_oracle, uint32_t log_n,
+                                  const sipp_plonk_params* p, const sipp_fri_params* fp, const sipp_plonk_circuit* c,
+                                  const uint64_t circuit_digest[4], const uint64_t* public_inputs, uint32_t n_public_inputs,
+                                  const uint32_t* lookup, uint64_t* proof_out, size_t proof_cap, size_t* proof_len) {
+    if (!lookup) return SIPP_E_BADARG;
     if (!ctx || !d_wires || !d_constants_sigmas || !fp || !p || !c || !circuit_digest || !proof_out || !proof_len ||
         (n_public_inputs && !public_inputs) || (wires_oracle != nullptr) != (wires_cap != nullptr) || n_public_inputs > (1u << 24))
         return SIPP_E_BADARG;
     SIPP_TRY(circuit_check(ctx, c, p));
+    SIPP_TRY(sipp_lookup_check(ctx, lookup, c->num_wires, c->num_constants, c->num_selectors));
     if ((wires_oracle && (wires_oracle->n_polys != c->num_wires || wires_oracle->n_salt || !wires_oracle->d_coeffs || !wires_oracle->d_lde ||
                           !wires_oracle->d_tree)) ||
         (constants_sigmas_oracle &&
@@ -738,5 +790,6 @@ int sipp_plonk_prove_gates(sipp_ctx* ctx, const uint64_t* d_wires, const uint64_
     PlonkExtra ex;
     ex.public_inputs = public_inputs; ex.n_public_inputs = n_public_inputs; ex.v2 = true;
     ex.sigmas_oracle = constants_sigmas_oracle; ex.wires_oracle = wires_oracle; ex.wires_cap = wires_cap; ex.circ = c;
+    ex.lookup = lookup_empty(lookup) ? nullptr : lookup;      // an empty description: "SIPPPLK3", word for word
     return plonk_prove_impl(ctx, d_wires, d_constants_sigmas, log_n, p, fp, circuit_digest, pih, ex, proof_out, proof_cap, proof_len);
 }

@@ -904,6 +904,7 @@ int verify(const uint64_t* proof, size_t len, const sipp_stark_config& cfg) {
 // ------------------------------------------------------------------------------------------------------------------------------
 constexpr uint64_t FRI_MAGIC = 0x5349505046524931ULL;    // "SIPPFRI1"
 constexpr uint64_t PLONK_MAGIC3 = 0x334b4c5050504953ULL;  // "SIPPPLK3" (as bytes in memory)
+constexpr uint64_t PLONK_MAGIC4 = 0x344b4c5050504953ULL;  // "SIPPPLK4": header[16] of PLK3, then the eight words of the lookup description
 
 FriShape fri_shape_of(const sipp_fri_params& p) {
     FriShape f;
@@ -988,8 +989,19 @@ bool circuit_ok(const sipp_plonk_circuit& c, const sipp_plonk_params& p) {
 // plonk/verifier.rs with the gate constraints evaluated at zeta from the OPENED constants and wires (gates as data: per gate a selector
 // filter and one polynomial per constraint), the permutation argument's Z(1) = 1 and partial-product terms, one reduce_with_powers per
 // challenge against the quotient chunks, then the opening proof
+// `lk`: the caller's NON-EMPTY lookup description (nullptr: none, the proof is "SIPPPLK3").  With one the proof is "SIPPPLK4": eta, theta
+// behind the gammas, the S / U columns behind the permutation's (S again at g zeta), the lookup terms behind the gate constraints.
+bool lookup_ok(const uint32_t* w, const sipp_plonk_circuit& c) {
+    // every bound before anything is sized by these words (the refusals of sipp_plonk_prove_gates_lookup)
+    if (w[2] == 0 || w[6] == 0 || w[2] > 128 || w[6] > 128 || w[7] != 0 || c.num_wires > 4096 || c.num_constants > 1024) return false;
+    if (w[0] >= c.num_constants || w[3] >= c.num_constants || w[0] < c.num_selectors || w[3] < c.num_selectors) return false;
+    if (w[1] >= c.num_wires || w[1] + 2 * w[2] > c.num_wires || w[5] >= c.num_wires || w[5] + w[6] > c.num_wires) return false;
+    return w[4] < c.num_constants && w[4] + 2 * w[6] <= c.num_constants;
+}
+
 int plonk_verify(const uint64_t* proof, size_t len, const uint64_t* cs_cap, const sipp_plonk_params& p, const sipp_fri_params& fp,
-                 const sipp_plonk_circuit& c, const uint64_t digest[4]) {
+                 const sipp_plonk_circuit& c, const uint64_t digest[4], const uint32_t* lk) {
+    if (lk && !lookup_ok(lk, c)) return 201;
     if (p.num_routed_wires == 0 || p.max_degree < 2 || p.max_degree > 64 || (p.max_degree & (p.max_degree - 1)) || p.num_challenges == 0 ||
         p.num_challenges > 8 || !circuit_ok(c, p))
         return 201;
@@ -999,19 +1011,26 @@ int plonk_verify(const uint64_t* proof, size_t len, const uint64_t* cs_cap, cons
     for (uint32_t g = 0; g < c.num_gates; g++) ngc = c.gates[g].num_constraints > ngc ? c.gates[g].num_constraints : ngc;
     if (fp.cap_height > 16) return 201;
     const size_t cap_n = (size_t)1 << fp.cap_height;
-    if (len < 16 + 3 * cap_n * 4 || proof[0] != PLONK_MAGIC3 || proof[2] != R || proof[3] != D || proof[4] != C || proof[5] != len || proof[6] != W ||
+    const size_t hw = lk ? 24 : 16;
+    const uint32_t Jl = lk ? (lk[2] + D - 1) / D : 0, Jt = lk ? (lk[6] + D - 1) / D : 0, J = Jl + Jt, nlk = C * J, nzl = nz + nlk;
+    if (lk) {      // the header's description is the caller's, word for word
+        if (len < hw) return 201;
+        for (int q = 0; q < 8; q++)
+            if (proof[16 + q] != lk[q]) return 201;
+    }
+    if (len < hw + 3 * cap_n * 4 || proof[0] != (lk ? PLONK_MAGIC4 : PLONK_MAGIC3) || proof[2] != R || proof[3] != D || proof[4] != C || proof[5] != len || proof[6] != W ||
         proof[7] != K || proof[8] != c.num_selectors || proof[9] != c.num_gates || proof[10] != ngc || (proof[12] | proof[13] | proof[14] | proof[15]))
         return 201;
     const size_t n_pi = (size_t)proof[11];
-    if (proof[11] > len - (16 + 3 * cap_n * 4)) return 201;
+    if (proof[11] > len - (hw + 3 * cap_n * 4)) return 201;
     const unsigned log_n = (unsigned)proof[1];
     if (proof[1] < 1 || proof[1] > 26 || !fri_params_ok(fp, log_n)) return 202;
     // every body word is a field element in canonical form (x + p would hash and compute like x: a second encoding of the same proof)
-    for (size_t i = 16; i < len; i++)
+    for (size_t i = hw; i < len; i++)
         if (proof[i] >= gl::P) return 141;
     uint64_t pih[4];
     host::Challenger::hash_no_pad(proof + len - n_pi, n_pi, pih);
-    const uint64_t *wcap = proof + 16, *zcap = wcap + cap_n * 4, *qcap = zcap + cap_n * 4, *op = qcap + cap_n * 4;
+    const uint64_t *wcap = proof + hw, *zcap = wcap + cap_n * 4, *qcap = zcap + cap_n * 4, *op = qcap + cap_n * 4;
     const size_t op_len = len - (size_t)(op - proof) - n_pi;
     host::Challenger ch;
     ch.observe_many(digest, 4);
@@ -1020,15 +1039,21 @@ int plonk_verify(const uint64_t* proof, size_t len, const uint64_t* cs_cap, cons
     uint64_t betas[8], gammas[8], alphas[8];
     for (uint32_t i = 0; i < C; i++) betas[i] = ch.get();
     for (uint32_t i = 0; i < C; i++) gammas[i] = ch.get();
+    uint64_t etas[8] = {0}, thetas[8] = {0};
+    if (lk) {
+        for (uint32_t i = 0; i < C; i++) etas[i] = ch.get();
+        for (uint32_t i = 0; i < C; i++) thetas[i] = ch.get();
+    }
     ch.observe_many(zcap, cap_n * 4);
     for (uint32_t i = 0; i < C; i++) alphas[i] = ch.get();
     ch.observe_many(qcap, cap_n * 4);
     const E2 zeta = ch.get_ext();
-    const size_t n0 = (size_t)K + R + W + nz + (size_t)C * D, n_open = n0 + C;
+    const size_t n0 = (size_t)K + R + W + nzl + (size_t)C * D, n_open = n0 + C + (lk ? C : 0);
     if (op_len < 8 + 2 * n_open) return 203;
     std::vector<E2> v(n_open);
     for (size_t k = 0; k < n_open; k++) v[k] = E2{op[8 + 2 * k], op[8 + 2 * k + 1]};
-    const E2 *cv = v.data(), *sg = cv + K, *wv = cv + K + R, *zs = wv + W, *pps = zs + C, *qs = zs + nz, *zs_next = cv + n0;
+    const E2 *cv = v.data(), *sg = cv + K, *wv = cv + K + R, *zs = wv + W, *pps = zs + C, *ss = zs + nz, *us = ss + C, *qs = zs + nzl, *zs_next = cv + n0,
+             *ss_next = zs_next + C;
     // gate constraint terms: term j = sum over gates of filter_g(selector) * constraint_(g, j)
     std::vector<E2> terms;
     const uint64_t n = (uint64_t)1 << log_n;
@@ -1072,6 +1097,30 @@ int plonk_verify(const uint64_t* proof, size_t len, const uint64_t* cs_cap, cons
             }
         }
         for (uint32_t j = 0; j < ngc; j++) terms.push_back(gt[j]);
+        if (lk) {
+            // L_0(zeta) S_c(zeta), then per challenge the chain  (U_j - U_(j-1)) Dl - q_look Nl,  (U_j - U_(j-1)) Dt + q_tab Nt
+            // with U_(-1) = S(zeta), U_(J-1) = S(g zeta)
+            for (uint32_t cc = 0; cc < C; cc++) terms.push_back(gl::mul(l0, ss[cc]));
+            const E2 ql = cv[lk[0]], qt = cv[lk[3]];
+            for (uint32_t cc = 0; cc < C; cc++) {
+                E2 prev = ss[cc];
+                for (uint32_t j = 0; j < J; j++) {
+                    const bool look = j < Jl;
+                    const uint32_t jj = look ? j : j - Jl, cnt = look ? lk[2] : lk[6];
+                    E2 N = e2(0), Dn = e2(1);
+                    for (uint32_t k = jj * D; k < (jj + 1) * D && k < cnt; k++) {
+                        const E2 vx = look ? wv[lk[1] + 2 * k] : cv[lk[4] + 2 * k], vy = look ? wv[lk[1] + 2 * k + 1] : cv[lk[4] + 2 * k + 1];
+                        const E2 d = gl::sub(e2(thetas[cc]), gl::add(vx, gl::scale(vy, etas[cc])));
+                        N = gl::add(gl::mul(N, d), look ? Dn : gl::mul(wv[lk[5] + k], Dn));
+                        Dn = gl::mul(Dn, d);
+                    }
+                    const E2 next = j + 1 == J ? ss_next[cc] : us[cc * (J - 1) + j];
+                    const E2 sd = gl::mul(gl::sub(next, prev), Dn);
+                    terms.push_back(look ? gl::sub(sd, gl::mul(ql, N)) : gl::add(sd, gl::mul(qt, N)));
+                    prev = next;
+                }
+            }
+        }
     }
     for (uint32_t cc = 0; cc < C; cc++) {
         E2 van = e2(0);
@@ -1081,9 +1130,9 @@ int plonk_verify(const uint64_t* proof, size_t len, const uint64_t* cs_cap, cons
         if (!gl::eq(van, gl::mul(zh, acc))) return 210;
     }
     const uint64_t* caps[4] = {cs_cap, wcap, zcap, qcap};
-    const uint32_t ncols[4] = {K + R, W, nz, C * D}, salt[4] = {0, 0, 0, 0};
-    const sipp_poly_range r0[4] = {{0, 0, K + R}, {1, 0, W}, {2, 0, nz}, {3, 0, C * D}}, r1[1] = {{2, 0, C}};
-    const FriBatchV batches[2] = {{zeta, 4, r0}, {gl::scale(zeta, gl::root_of_unity(log_n)), 1, r1}};
+    const uint32_t ncols[4] = {K + R, W, nzl, C * D}, salt[4] = {0, 0, 0, 0};
+    const sipp_poly_range r0[4] = {{0, 0, K + R}, {1, 0, W}, {2, 0, nzl}, {3, 0, C * D}}, r1[2] = {{2, 0, C}, {2, nz, nz + C}};
+    const FriBatchV batches[2] = {{zeta, 4, r0}, {gl::scale(zeta, gl::root_of_unity(log_n)), lk ? 2u : 1u, r1}};
     return fri_openings_verify(op, op_len, caps, ncols, salt, 4, batches, 2, log_n, fp, ch);
 }
 
@@ -1117,7 +1166,23 @@ extern "C" int sipp_plonk_verify_gates(const uint64_t* proof, size_t len, const 
     if (!proof || !constants_sigmas_cap || !p || !fp || !c || !circuit_digest) return SIPP_E_BADARG;
     int r;
     try {
-        r = plonk_verify(proof, len, constants_sigmas_cap, *p, *fp, *c, circuit_digest);
+        r = plonk_verify(proof, len, constants_sigmas_cap, *p, *fp, *c, circuit_digest, nullptr);
+    } catch (...) {
+        return SIPP_E_NOMEM;
+    }
+    if (reason) *reason = r;
+    return r == 0 ? SIPP_OK : SIPP_E_VERIFY;
+}
+
+extern "C" int sipp_plonk_verify_gates_lookup(const uint64_t* proof, size_t len, const uint64_t* constants_sigmas_cap, const sipp_plonk_params* p,
+                                              const sipp_fri_params* fp, const sipp_plonk_circuit* c, const uint64_t circuit_digest[4],
+                                              const uint32_t* lookup, int* reason) {
+    if (reason) *reason = 0;
+    if (!proof || !constants_sigmas_cap || !p || !fp || !c || !circuit_digest || !lookup) return SIPP_E_BADARG;
+    const bool empty = lookup[2] == 0 && lookup[6] == 0;      // an empty description: a "SIPPPLK3" proof
+    int r;
+    try {
+        r = plonk_verify(proof, len, constants_sigmas_cap, *p, *fp, *c, circuit_digest, empty ? nullptr : lookup);
     } catch (...) {
         return SIPP_E_NOMEM;
     }

@@ -278,6 +278,7 @@ class PlonkVanishingCircuit(CircuitBuilder):
         assert 1 <= C <= 8, "more than 8 challenges are out of scope"
         assert 2 <= D <= 64 and D & (D - 1) == 0, "max_degree must be a power of two (2 .. 64)"
         assert R >= 1 and 1 <= log_n <= 26 and 0 <= cap_height <= 16
+        assert not any(circuit.get("lookup", ())), "an inner circuit with lookups (a \"SIPPPLK4\" proof) is out of scope"
         bad = circuit_ok(circuit, R)
         assert bad is None, "the inner gate set is refused: %s" % bad
         self.inner_log_n, self.R, self.D, self.C, self.inner, self.inner_cap_height, self.n_pi_inner = log_n, R, D, C, circuit, cap_height, n_pi_inner
