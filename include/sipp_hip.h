@@ -529,10 +529,22 @@ int sipp_plonk_prove_gates(sipp_ctx *ctx, const uint64_t *d_wires, const uint64_
  *                                                                       the Poseidon kinds.  The inputs are field values, whatever word they
  *                                                                       hold; the outputs are canonical.  in + 24 <= num_wires, out + 24 <=
  *                                                                       num_wires, and the two ranges must not meet         (PoseidonMdsGenerator)
+ *   SIPP_GEN_LOOKUP         p = look_wire0, n_look, tab_const0, n_tab,  a looking row's y cells from a DENSE table: entry t has x = t and sits
+ *                               base_col                                in table row row0 + t / n_tab, slot t % n_tab (the constant columns
+ *                                                                       tab_const0 + 2 slot, + 2 slot + 1 of "LOOKUP TABLES" below).  On a
+ *                                                                       row it holds, row0 = const[base_col], T = const[base_col + 1] (field
+ *                                                                       values).  T = 0: a plain looking row, nothing is written.  Otherwise
+ *                                                                       for every slot k < n_look, x = w[look_wire0 + 2k]:
+ *                                                                       w[look_wire0 + 2k + 1] = const[tab_const0 + 2 (x % n_tab) + 1] on row
+ *                                                                       row0 + x / n_tab (canonical) if x < T and that row is below N, else 0.
+ *                                                                       n_look, n_tab >= 1, look_wire0 + 2 n_look <= num_wires, tab_const0 +
+ *                                                                       2 n_tab <= num_constants, base_col + 1 < num_constants
  * The five families from SIPP_GEN_ARITHMETIC_EXT to SIPP_GEN_QUOTIENT_EXT take ANY field value in every input cell; W != 0.
  * Defined behaviour outside a gate's range (the constraints, not the generators, refuse such rows): BASE_SPLIT drops the bits of w[0] at
  * and above n_limbs * bits; U32_MUL_ADD takes the low 32 bits of an operand that is not a u32, and with a stride wider than 5 + 2 limbs
- * the cells behind an op's limbs stay untouched; RANDOM_ACCESS with an index >= 2^bits selects by the low `bits` bits of the index.
+ * the cells behind an op's limbs stay untouched; RANDOM_ACCESS with an index >= 2^bits selects by the low `bits` bits of the index;
+ * LOOKUP writes y = 0 for an x outside the table (x >= T, or an entry's row outside the circuit; the row arithmetic is in 64 bits, so a
+ * row0 or T of any field value cannot wrap): the lookup argument refuses such a row, the multiplicities answer SIPP_E_WITNESS.
  * The generators are ROW-LOCAL: values that reach a gate's inputs through copy constraints from another gate's outputs have to be there
  * already (the caller orders its calls by level); d_constants = the circuit's constant columns [num_constants][N] (selectors first: the
  * front of d_constants_sigmas).  SIPP_E_BADARG for a layout that leaves the wire table or an unknown family. */
@@ -552,6 +564,7 @@ int sipp_plonk_prove_gates(sipp_ctx *ctx, const uint64_t *d_wires, const uint64_
 #define SIPP_GEN_QUOTIENT_EXT 14
 #define SIPP_GEN_BASE_SUM 15
 #define SIPP_GEN_POSEIDON_MDS 16
+#define SIPP_GEN_LOOKUP 17
 typedef struct {
     uint32_t kind, selector_index, row;
     uint32_t p[5];
@@ -647,28 +660,37 @@ int sipp_circuit_verify(const sipp_circuit_data *cd, const uint64_t *proof, size
 
 /* ---- LOOKUP TABLES by a log-derivative argument: the columns below the quotient ----------------------------
  * The library's own statement of a LogUp lookup (not plonky2's RE / SLDC bookkeeping): the table lives in CONSTANT columns, the
- * multiplicities in WIRES.  A description is eight uint32 words:  q_look, look_wire0, n_look, q_tab, tab_const0, tab_mult0, n_tab, 0.
+ * multiplicities in WIRES.  A description is eight uint32 words:
+ *   q_look, look_wire0, n_look, q_tab, tab_const0, tab_mult0, n_tab, tag_const0.
  *   q_look, q_tab: constant columns (not selector columns) of 0 / 1 that mark looking rows and table rows;
  *   slot k < n_look of a looking row: the pair (x, y) = wires (look_wire0 + 2k, look_wire0 + 2k + 1);
  *   slot k < n_tab of a table row: the pair (tx, ty) = constant columns (tab_const0 + 2k, + 2k + 1), multiplicity m = wire tab_mult0 + k;
  *   unused table slots repeat a real entry, unused looking slots look a real entry up;  n_look = n_tab = 0: no lookups (the calls
- *   below do nothing).
+ *   below do nothing);
+ *   tag_const0 = 0: ONE table; every call, transcript and proof is what it was before this word had a meaning.  Non-zero: SEVERAL
+ *   TABLES told apart by a tag, in two consecutive constant columns (not selector columns): column tag_const0 holds the tag of every
+ *   looking row, column tag_const0 + 1 the tag of every table row.  A tag is any field value, whatever u64 holds it; all slots of a
+ *   row share its tag, and unmarked rows may hold anything there.  An entry is then the triple (tag, x, y): a pair that exists only
+ *   under another tag is absent.
  * Refusals: n_look or n_tab above 128 SIPP_E_UNSUPPORTED; a column outside the circuit, q_look or q_tab below num_selectors, one of
- * n_look / n_tab zero and the other not, a last word that is not 0, a marker cell that is neither 0 nor 1: SIPP_E_BADARG.
+ * n_look / n_tab zero and the other not, a non-zero tag_const0 below num_selectors or with tag_const0 + 1 >= num_constants (or in an
+ * empty description), a marker cell that is neither 0 nor 1: SIPP_E_BADARG.
  * d_wires [num_wires][N], d_constants [num_constants][N] (the constant columns in front of the constants_sigmas batch): VALUES in
  * natural row order.  A looking or table value is its field value, whatever u64 holds it.
  *
  * sipp_plonk_lookup_multiplicities: zeroes the m cells of the table rows, then adds one for every slot of every looking row to the
- * table slot with the equal pair.  Among equal table pairs the first in (row, slot) order takes every look; the search goes through a
- * sorted index of the table's distinct pairs (built here on the host from the constant columns), so the counts do not depend on the
- * order the device reaches the rows in.  A looked-up pair that is in no table slot: SIPP_E_WITNESS (a device flag read back once; the
- * m cells are then unspecified, the ctx stays usable).
+ * table slot with the equal pair (with tags: the equal (tag, x, y), the looking row's tag against the table row's).  Among equal
+ * table entries the first in (row, slot) order takes every look; the search goes through a sorted index of the table's distinct
+ * entries (built here on the host from the constant columns), so the counts do not depend on the order the device reaches the rows
+ * in.  A looked-up pair that is in no table slot of its tag: SIPP_E_WITNESS (a device flag read back once; the m cells are then
+ * unspecified, the ctx stays usable).
  *
  * sipp_plonk_lookup_sums: the running-sum columns for the caller's eta, theta (num_challenges host words each; any u64 congruent to
  * the value).  With D = max_degree, the looking slots in Jl = ceil(n_look / D) groups of up to D and the table slots in Jt =
  * ceil(n_tab / D) groups, J = Jl + Jt, per challenge and row:
- *   looking group j:  U_j - U_(j-1) = q_look sum_k 1 / d_k,        d_k = theta - (x_k + eta y_k)
- *   table group j:    U_j - U_(j-1) = - q_tab sum_k m_k / e_k,     e_k = theta - (tx_k + eta ty_k)
+ *   looking group j:  U_j - U_(j-1) = q_look sum_k 1 / d_k,        d_k = theta - (x_k + eta y_k + eta^2 tag_look(row))
+ *   table group j:    U_j - U_(j-1) = - q_tab sum_k m_k / e_k,     e_k = theta - (tx_k + eta ty_k + eta^2 tag_tab(row))
+ * (the eta^2 terms only with tag_const0 != 0; a constant column has a wire's degree, so no term's degree and no column count changes)
  * U_(-1) = S(x), U_(J-1) = S(g x), S(1) = 0.  d_out [num_challenges J][N], the order of the columns behind the permutation's in the
  * zs_partial_products oracle: S_0 .. S_(C-1), then U_0 .. U_(J-2) of challenge 0, of challenge 1, ...
  * (sipp_plonk_lookup_num_columns = num_challenges J; 0 for an empty description or one outside the supported range).

@@ -134,6 +134,8 @@ pub const SIPP_GEN_QUOTIENT_EXT: u32 = 14;
 pub const SIPP_GEN_BASE_SUM: u32 = 15;
 /// SIPP_GEN_*: the Poseidon linear layer on twelve extension elements (p = in, out; two limbs per element)
 pub const SIPP_GEN_POSEIDON_MDS: u32 = 16;
+/// SIPP_GEN_*: a looking row's y cells from a dense lookup table (p = look_wire0, n_look, tab_const0, n_tab, base_col)
+pub const SIPP_GEN_LOOKUP: u32 = 17;
 
 /// one gate family's witness generator with its layout (include/sipp_hip.h, "WITNESS GENERATORS"): kind = SIPP_GEN_*
 #[repr(C)]

@@ -11,8 +11,11 @@ gate programs more than one of them uses, the builder that turns rows and feeds 
                             the cells, schedules the copies and gives every row the level behind its latest computed source, and tie();
                             the public-input Poseidon chain; finish(), which fixes N and makes the cycles and the level schedule.  A
                             circuit is a subclass: it declares its gates, writes its statement as builder calls and finishes.
-                            Lookups (one table, include/sipp_hip.h "LOOKUP TABLES"): declare_lookup() names two zero-constraint gates,
-                            table() writes the table rows, lookup() / range_check() fill looking rows; the description rides in circuit()
+                            Lookups (include/sipp_hip.h "LOOKUP TABLES"): declare_lookup() names two zero-constraint gates,
+                            table() writes the table rows, lookup() / range_check() fill looking rows; the description rides in circuit().
+                            declare_lookup(tables=True): several tables told apart by a tag (description word 7), and function tables --
+                            function_table(values) is the dense table t -> values[t], function_lookup(table, xs) places looking rows
+                            whose y cells SIPP_GEN_LOOKUP fills on the device and returns those cells as sources
   _Challenger               plonky2's RecursiveChallenger on a builder (sipp_amd/fri_proof.py says how it buffers and duplexes)
   CircuitProver             a built circuit through the library's CircuitData
 
@@ -30,6 +33,7 @@ GEN_BASE_SPLIT, GEN_CONSTANT, GEN_PUBLIC_INPUT, GEN_RANDOM_ACCESS, GEN_REDUCING,
 GEN_ARITHMETIC_EXT, GEN_EXPONENTIATION, GEN_COSET_INTERPOLATION, GEN_REDUCING_EXT, GEN_QUOTIENT_EXT = 10, 11, 12, 13, 14
 GEN_BASE_SUM = 15
 GEN_POSEIDON_MDS = 16
+GEN_LOOKUP = 17
 # program factor kinds
 _W, _K, _PIH = 0, 1, 2
 # upstream's PoseidonGate layout (SIPP_GEN_POSEIDON_SWAP): 135 wires
@@ -309,69 +313,121 @@ class CircuitBuilder:
         for t in range(4):
             self.tie((self.s_out + t, self.chain_row[-1]), (t, self.pi_row))
 
-    # ---- lookups: one table in constant columns, the multiplicities in wires ----
-    def declare_lookup(self, table_gate, looking_gate, n_look, n_tab, look_wire0=0, tab_mult0=None):
+    # ---- lookups: tables in constant columns, the multiplicities in wires ----
+    def declare_lookup(self, table_gate, looking_gate, n_look, n_tab, look_wire0=0, tab_mult0=None, tables=False):
         """table_gate, looking_gate: two gates declared with no constraints (declare(index, 0)) that only mark the table rows and the
         looking rows.  A looking row holds n_look pairs in the routed wires look_wire0 ..; a table row holds n_tab pairs in constant
         columns of their own behind the builder's, its multiplicities in the wires tab_mult0 .. (default: behind the looking wires).
-        The constant columns grow by q_look, q_tab and the 2 n_tab table columns."""
+        The constant columns grow by q_look, q_tab and the 2 n_tab table columns.
+        tables=True: several tables, told apart by a tag -- two more constant columns behind the table columns (the looking rows' tags,
+        the table rows' tags: description word 7); table() may then be called more than once, and the looking gate gets the generator
+        SIPP_GEN_LOOKUP, which fills the y cells of function_lookup()'s rows from the row's constants c0 = row0, c1 = T (so the
+        builder must have two constant columns); every other looking row has c0 = c1 = 0 and both coordinates fed."""
         assert self._lk is None and 1 <= n_look <= 128 and 1 <= n_tab <= 128
         tab_mult0 = look_wire0 + 2 * n_look if tab_mult0 is None else tab_mult0
         assert look_wire0 + 2 * n_look <= self.num_routed and tab_mult0 + n_tab <= self.num_wires
         k = self.num_constants
         self._lk = {"table_gate": table_gate, "looking_gate": looking_gate, "n_look": n_look, "n_tab": n_tab, "look_wire0": look_wire0,
                     "tab_mult0": tab_mult0, "q_look": k, "q_tab": k + 1, "tab_const0": k + 2, "entries": None, "table_rows": [],
-                    "pending": [], "zero": None}
+                    "pending": [], "zero": None, "tag_const0": 0, "tables": [], "row_tag": {}}
         self.num_constants = k + 2 + 2 * n_tab
+        if tables:
+            assert self.num_constants - 2 - 2 * n_tab - self.num_selectors == 2, "function rows keep row0 and T in c0, c1"
+            self._lk["tag_const0"] = self.num_constants
+            self.num_constants += 2
+            self._generators.append((GEN_LOOKUP, self._group[looking_gate], looking_gate, look_wire0, n_look, k + 2, n_tab, self.k0))
 
     def table(self, entries):
         """the table: (x, y) pairs (a range table: (v, 0)).  Table rows are written here; the slots the last row has left repeat the last
-        entry.  -> the entries, as range_check()'s `table` argument"""
+        entry.  -> the entries, as range_check()'s `table` argument; with tables=True a handle (a dict: tag, entries, row0, T) as the
+        `table` argument of lookup(), range_check() and function_lookup(), the tables taking the tags 0, 1, 2, ... as they come"""
         lk = self._lk
-        assert lk is not None and lk["entries"] is None and len(entries) >= 1
+        assert lk is not None and len(entries) >= 1 and (lk["tag_const0"] or lk["entries"] is None)
         ent = [(int(x) % P, int(y) % P) for x, y in entries]
+        handle = {"tag": len(lk["tables"]), "entries": ent, "row0": len(self._rows), "T": len(ent), "pending": [], "dense": False}
         for at in range(0, len(ent), lk["n_tab"]):
             r = self.new_row(lk["table_gate"])
             self.place(r)
             lk["table_rows"].append((r, (ent[at:at + lk["n_tab"]] + [ent[-1]] * lk["n_tab"])[:lk["n_tab"]]))
-        lk["entries"] = ent
-        return ent
+            lk["row_tag"][r] = handle["tag"]
+        lk["tables"].append(handle)
+        if not lk["tag_const0"]:
+            lk["entries"] = ent
+            return ent
+        return handle
 
-    def lookup(self, x_source, y_source):
-        """the pair (x, y) must be a table entry.  Pairs are gathered n_look to a looking row; a row that stays short repeats its first
-        pair (flush_lookups(), which finish() calls)"""
+    def function_table(self, values):
+        """the dense table t -> values[t], t < len(values): entry t is (t, values[t]) in table row row0 + t // n_tab, slot t % n_tab,
+        which is where SIPP_GEN_LOOKUP reads it.  -> the handle, with row0 and T = len(values)"""
+        assert self._lk is not None and self._lk["tag_const0"], "function tables need declare_lookup(tables=True)"
+        handle = self.table([(t, v) for t, v in enumerate(values)])
+        handle["dense"] = True
+        return handle
+
+    def _table(self, table):
+        """the handle lookups against `table` gather under: the one table of a circuit without tags, whatever `table` is"""
         lk = self._lk
-        assert lk is not None and lk["entries"] is not None
-        lk["pending"].append((x_source, y_source))
-        if len(lk["pending"]) == lk["n_look"]:
-            self.flush_lookups()
+        assert lk is not None and lk["tables"]
+        if not lk["tag_const0"]:
+            return lk["tables"][0]
+        assert any(table is t for t in lk["tables"]), "with several tables every lookup names its table's handle"
+        return table
+
+    def lookup(self, x_source, y_source, table=None):
+        """the pair (x, y) must be an entry of the table.  Pairs are gathered per table, n_look to a looking row; a row that stays short
+        repeats its first pair (flush_lookups(), which finish() calls)"""
+        t = self._table(table)
+        t["pending"].append((x_source, y_source))
+        if len(t["pending"]) == self._lk["n_look"]:
+            self._flush(t)
 
     def range_check(self, x_source, table=None):
         """x is the first coordinate of an entry (x, 0): a lookup of (x, 0) against a range table"""
         lk = self._lk
-        assert table is None or table is lk["entries"], "one table a circuit"
+        assert lk["tag_const0"] or table is None or table is lk["entries"], "one table a circuit"
         if lk["zero"] is None:
             lk["zero"] = self.constant(0)[1]
-        self.lookup(x_source, lk["zero"])
+        self.lookup(x_source, lk["zero"], table)
 
-    def flush_lookups(self):
+    def function_lookup(self, table, x_sources):
+        """y = f(x) for every source x, f a function_table(): whole looking rows of up to n_look slots with only the x cells fed (a
+        short row repeats its first x), c0 = row0 and c1 = T, so that the looking gate's generator writes the y cells.  A row runs one
+        level behind its latest x.  -> the y cells, sources for later rows like any generated cell"""
         lk = self._lk
-        if lk is None or not lk["pending"]:
+        assert lk is not None and any(table is t for t in lk["tables"]) and table["dense"]
+        n_look, lw, out = lk["n_look"], lk["look_wire0"], []
+        for at in range(0, len(x_sources), n_look):
+            xs = list(x_sources[at:at + n_look])
+            r = self.new_row(lk["looking_gate"], table["row0"], table["T"])
+            lk["row_tag"][r] = table["tag"]
+            self.place(r, [(lw + 2 * k, s) for k, s in enumerate((xs + [xs[0]] * n_look)[:n_look])])
+            out += [(lw + 2 * k + 1, r) for k in range(len(xs))]
+        return out
+
+    def _flush(self, t):
+        lk = self._lk
+        if not t["pending"]:
             return
-        pairs = (lk["pending"] + [lk["pending"][0]] * lk["n_look"])[:lk["n_look"]]
-        lk["pending"] = []
+        pairs = (t["pending"] + [t["pending"][0]] * lk["n_look"])[:lk["n_look"]]
+        t["pending"] = []
         r = self.new_row(lk["looking_gate"])
+        lk["row_tag"][r] = t["tag"]
         feeds = []
         for k, (xs, ys) in enumerate(pairs):
             feeds += [(lk["look_wire0"] + 2 * k, xs), (lk["look_wire0"] + 2 * k + 1, ys)]
         self.place(r, feeds)
+
+    def flush_lookups(self):
+        if self._lk is not None:
+            for t in self._lk["tables"]:
+                self._flush(t)
 
     def lookup_description(self):
         """the eight words of include/sipp_hip.h; all zero without a declared lookup"""
         lk = self._lk
         if lk is None:
             return (0,) * 8
-        return (lk["q_look"], lk["look_wire0"], lk["n_look"], lk["q_tab"], lk["tab_const0"], lk["tab_mult0"], lk["n_tab"], 0)
+        return (lk["q_look"], lk["look_wire0"], lk["n_look"], lk["q_tab"], lk["tab_const0"], lk["tab_mult0"], lk["n_tab"], lk["tag_const0"])
 
     def finish(self, min_log_n):
         """N is known: cells become wire * N + row.  min_log_n: the device prover's FRI takes degree bits 10 .. 24; smaller circuits
@@ -448,12 +504,15 @@ class CircuitBuilder:
         consts = [self.c0, self.c1][:self.k_lookup0() - self.num_selectors]
         if self._lk is not None:
             lk = self._lk
-            cols = np.zeros((2 + 2 * lk["n_tab"], n), dtype=np.uint64)
+            cols = np.zeros((2 + 2 * lk["n_tab"] + (2 if lk["tag_const0"] else 0), n), dtype=np.uint64)
             cols[0] = self.gate == lk["looking_gate"]
             cols[1] = self.gate == lk["table_gate"]
             for r, slots in lk["table_rows"]:
                 for k, (x, y) in enumerate(slots):
                     cols[2 + 2 * k][r], cols[3 + 2 * k][r] = x, y
+            if lk["tag_const0"]:                      # the looking rows' tags, then the table rows'
+                for r, tag in lk["row_tag"].items():
+                    cols[2 + 2 * lk["n_tab"] + (self.gate[r] == lk["table_gate"])][r] = tag
             consts = consts + list(cols)
         return np.ascontiguousarray(np.concatenate([np.stack(sels + consts), sig]).astype(np.uint64))
 

@@ -276,7 +276,7 @@ extern "C" int sipp_circuit_set_lookup(sipp_circuit_data* cd, const uint32_t* lo
         (void)hipStreamSynchronize(ctx->stream);
         (void)hipFree(cd->d_index);
     }
-    cd->d_index = d_new; cd->n_index = (uint32_t)(index.size() / 3);
+    cd->d_index = d_new; cd->n_index = (uint32_t)(index.size() / 4);
     for (int q = 0; q < 8; q++) cd->lookup[q] = empty ? 0 : lookup[q];
     return SIPP_OK;
 }

@@ -259,7 +259,7 @@ int sipp_k_poseidon_permute(sipp_ctx* ctx, uint64_t* d_states, size_t n);
 void sipp_witness_graph_release(sipp_ctx* ctx);   // witness.hip
 int sipp_plonk_circuit_check(sipp_ctx* ctx, const sipp_plonk_circuit* c, const sipp_plonk_params* p);   // plonk.hip
 // lookup.hip -- a lookup description is the eight words of include/sipp_hip.h.  _check: its refusals (an empty one passes);
-// _index_host: the sorted index of the table's distinct pairs (kx | ky | cell, a third of the vector each), built once per circuit;
+// _index_host: the sorted index of the table's distinct pairs (kx | ky | cell | kt, a quarter of the vector each), built once per circuit;
 // _multiplicities_indexed: sipp_plonk_lookup_multiplicities over an index the caller keeps on the device; _quotient_terms: adds
 // Z_H^-1 sum_k alpha^(terms_in_front + k) term_k over the quotient coset into d_qv [C][N D] (leaf order, in front of the coset iNTT).
 int sipp_lookup_check(sipp_ctx* ctx, const uint32_t* lookup, uint32_t num_wires, uint32_t num_constants, uint32_t num_selectors);

@@ -3,9 +3,13 @@
 // own statement, shaped to fit the outer prover's oracles (the table in CONSTANT columns, the multiplicities in WIRES); it does not
 // follow plonky2's RE / SLDC bookkeeping.
 //
-// Description (eight uint32 words): q_look, look_wire0, n_look, q_tab, tab_const0, tab_mult0, n_tab, 0.  q_look / q_tab are constant
-// columns of 0 / 1 that mark looking rows and table rows.  Slot k of a looking row is the pair of wires (look_wire0 + 2k, + 2k + 1);
-// slot k of a table row is the pair of constants (tab_const0 + 2k, + 2k + 1) with its multiplicity in wire tab_mult0 + k.
+// Description (eight uint32 words): q_look, look_wire0, n_look, q_tab, tab_const0, tab_mult0, n_tab, tag_const0.  q_look / q_tab are
+// constant columns of 0 / 1 that mark looking rows and table rows.  Slot k of a looking row is the pair of wires (look_wire0 + 2k,
+// + 2k + 1); slot k of a table row is the pair of constants (tab_const0 + 2k, + 2k + 1) with its multiplicity in wire tab_mult0 + k.
+// tag_const0 = 0: one table.  Otherwise SEVERAL TABLES told apart by a tag: constant column tag_const0 holds the tag of every looking
+// row, tag_const0 + 1 the tag of every table row (any field value), and a combination is x + eta y + eta^2 tag: a pair under another
+// tag is another entry.  Every kernel that forms a combination is a template over TAGGED: the one-table instantiation is the code it
+// was before the tags, the tagged one loads its row's tag once and folds eta^2 tag into theta.
 //
 // Layout: column-major [column][row], natural row order, like plonk.hip.  Kernels: one lane per table cell (zero), one lane per looking
 // slot (binary search in the sorted index, one 64-bit atomic add on the multiplicity cell: integer additions commute, so the counts do
@@ -20,17 +24,19 @@ namespace {
 constexpr uint32_t MAX_SLOTS = 128, MAX_CH = 8, MAX_GROUPS = 128;   // groups: ceil(128 / 2) looking + ceil(128 / 2) table
 
 struct Lookup {
-    uint32_t q_look, look_wire0, n_look, q_tab, tab_const0, tab_mult0, n_tab;
+    uint32_t q_look, look_wire0, n_look, q_tab, tab_const0, tab_mult0, n_tab, tag_const0;
     bool empty() const { return n_look == 0 && n_tab == 0; }
+    bool tagged() const { return tag_const0 != 0; }
 };
+Lookup lookup_of(const uint32_t* w) { return Lookup{w[0], w[1], w[2], w[3], w[4], w[5], w[6], w[7]}; }
 
 // the refusals of include/sipp_hip.h, in its order: sizes the build does not serve, then a description that does not fit the circuit
 int lookup_check(sipp_ctx* ctx, const uint32_t* w, uint32_t num_wires, uint32_t num_constants, uint32_t num_selectors, Lookup* out) {
     if (!w) return sipp_fail(ctx, SIPP_E_BADARG, "lookup: no description");
-    const Lookup l{w[0], w[1], w[2], w[3], w[4], w[5], w[6]};
+    const Lookup l = lookup_of(w);
     *out = l;
     if (l.n_look > MAX_SLOTS || l.n_tab > MAX_SLOTS) return sipp_fail(ctx, SIPP_E_UNSUPPORTED, "lookup: at most 128 looking slots and 128 table slots a row");
-    if (w[7] != 0) return sipp_fail(ctx, SIPP_E_BADARG, "lookup: the description's last word must be 0");
+    if (l.empty() && l.tagged()) return sipp_fail(ctx, SIPP_E_BADARG, "lookup: an empty description names no tag columns");
     if (l.empty()) return SIPP_OK;
     if (l.n_look == 0 || l.n_tab == 0) return sipp_fail(ctx, SIPP_E_BADARG, "lookup: looking slots without table slots, or the reverse");
     if (num_wires > 4096 || num_constants > 1024 || num_selectors > num_constants)
@@ -42,15 +48,18 @@ int lookup_check(sipp_ctx* ctx, const uint32_t* w, uint32_t num_wires, uint32_t 
         return sipp_fail(ctx, SIPP_E_BADARG, "lookup: the description names a column outside the circuit");
     if (l.q_look < num_selectors || l.q_tab < num_selectors)
         return sipp_fail(ctx, SIPP_E_BADARG, "lookup: q_look and q_tab are constant columns behind the selector columns");
+    if (l.tagged() && (l.tag_const0 < num_selectors || (uint64_t)l.tag_const0 + 1 >= num_constants))
+        return sipp_fail(ctx, SIPP_E_BADARG, "lookup: tag_const0 names two constant columns behind the selector columns");
     return SIPP_OK;
 }
 
 // ---- multiplicities ------------------------------------------------------------------------------------------------------------------
-// The index of a table: its DISTINCT canonical pairs in ascending (x, y) order, each with the wire cell of the first slot in
-// (row, slot) order that holds it -- that slot takes every look of the pair, the others stay 0.
+// The index of a table: its DISTINCT canonical entries (tag, x, y) in ascending order (the tag of an untagged description is 0), each
+// with the wire cell of the first slot in (row, slot) order that holds it -- that slot takes every look of the entry, the others stay 0.
 struct TableIndex {
     const uint64_t *kx, *ky;   // [T] sorted
     const uint64_t* cell;      // [T] index into the wire table: (tab_mult0 + slot) * n + row
+    const uint64_t* kt;        // [T] the tags; read by the tagged kernel only
     uint32_t T;
 };
 
@@ -69,45 +78,58 @@ __global__ void __launch_bounds__(256) lookup_zero_kernel(MultArgs a) {
     a.wires[(size_t)(a.l.tab_mult0 + k) * n + i] = 0;
 }
 
+template <bool TAGGED>
 __global__ void __launch_bounds__(256) lookup_count_kernel(MultArgs a) {
     const uint32_t n = 1u << a.log_n, i = blockIdx.x * blockDim.x + threadIdx.x, k = blockIdx.y;
     if (i >= n || gl::canon(a.consts[(size_t)a.l.q_look * n + i]) == 0) return;
     const uint64_t x = gl::canon(a.wires[(size_t)(a.l.look_wire0 + 2 * k) * n + i]);
     const uint64_t y = gl::canon(a.wires[(size_t)(a.l.look_wire0 + 2 * k + 1) * n + i]);
-    uint32_t lo = 0, hi = a.ix.T;                      // the first entry >= (x, y)
+    const uint64_t t = TAGGED ? gl::canon(a.consts[(size_t)a.l.tag_const0 * n + i]) : 0;      // the looking row's tag
+    uint32_t lo = 0, hi = a.ix.T;                      // the first entry >= (t, x, y)
     while (lo < hi) {
         const uint32_t mid = lo + (hi - lo) / 2;
         const uint64_t mx = a.ix.kx[mid], my = a.ix.ky[mid];
-        if (mx < x || (mx == x && my < y)) lo = mid + 1; else hi = mid;
+        bool below = mx < x || (mx == x && my < y);
+        if (TAGGED) {
+            const uint64_t mt = a.ix.kt[mid];
+            below = mt < t || (mt == t && below);
+        }
+        if (below) lo = mid + 1; else hi = mid;
     }
-    if (lo < a.ix.T && a.ix.kx[lo] == x && a.ix.ky[lo] == y)
+    if (lo < a.ix.T && a.ix.kx[lo] == x && a.ix.ky[lo] == y && (!TAGGED || a.ix.kt[lo] == t))
         atomicAdd(reinterpret_cast<unsigned long long*>(a.wires + a.ix.cell[lo]), 1ull);
     else
         atomicOr(a.flag, 1u);
 }
 
-// The index on the host (once per table: the table is constants): kx[T] | ky[T] | cell[T].  The marker columns must hold 0 / 1
+// The index on the host (once per table: the table is constants): kx[T] | ky[T] | cell[T] | kt[T].  The marker columns must hold 0 / 1
 int index_host(sipp_ctx* ctx, const uint64_t* d_consts, uint32_t log_n, const Lookup& l, std::vector<uint64_t>* out) {
     const size_t n = (size_t)1 << log_n;
     std::vector<uint64_t> qt(n), ql(n), tab((size_t)2 * l.n_tab * n);
     SIPP_CHECK_HIP(ctx, hipMemcpyAsync(qt.data(), d_consts + (size_t)l.q_tab * n, n * 8, hipMemcpyDeviceToHost, ctx->stream));
     SIPP_CHECK_HIP(ctx, hipMemcpyAsync(ql.data(), d_consts + (size_t)l.q_look * n, n * 8, hipMemcpyDeviceToHost, ctx->stream));
     SIPP_CHECK_HIP(ctx, hipMemcpyAsync(tab.data(), d_consts + (size_t)l.tab_const0 * n, tab.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+    std::vector<uint64_t> tag;                        // the table rows' tags
+    if (l.tagged()) {
+        tag.resize(n);
+        SIPP_CHECK_HIP(ctx, hipMemcpyAsync(tag.data(), d_consts + (size_t)(l.tag_const0 + 1) * n, n * 8, hipMemcpyDeviceToHost, ctx->stream));
+    }
     SIPP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    struct Entry { uint64_t x, y, cell; };
+    struct Entry { uint64_t t, x, y, cell; };
     std::vector<Entry> es;
     for (size_t i = 0; i < n; i++) {
         if (gl::canon(qt[i]) > 1 || gl::canon(ql[i]) > 1) return sipp_fail(ctx, SIPP_E_BADARG, "lookup: q_look and q_tab hold 0 or 1");
         if (gl::canon(qt[i]) == 0) continue;
         for (uint32_t k = 0; k < l.n_tab; k++)
-            es.push_back(Entry{gl::canon(tab[(size_t)(2 * k) * n + i]), gl::canon(tab[(size_t)(2 * k + 1) * n + i]), (size_t)(l.tab_mult0 + k) * n + i});
+            es.push_back(Entry{l.tagged() ? gl::canon(tag[i]) : 0, gl::canon(tab[(size_t)(2 * k) * n + i]), gl::canon(tab[(size_t)(2 * k + 1) * n + i]),
+                               (size_t)(l.tab_mult0 + k) * n + i});
     }
-    // stable: among equal pairs the first in (row, slot) order stays in front
-    std::stable_sort(es.begin(), es.end(), [](const Entry& a, const Entry& b) { return a.x != b.x ? a.x < b.x : a.y < b.y; });
-    es.erase(std::unique(es.begin(), es.end(), [](const Entry& a, const Entry& b) { return a.x == b.x && a.y == b.y; }), es.end());
+    // stable: among equal entries the first in (row, slot) order stays in front
+    std::stable_sort(es.begin(), es.end(), [](const Entry& a, const Entry& b) { return a.t != b.t ? a.t < b.t : a.x != b.x ? a.x < b.x : a.y < b.y; });
+    es.erase(std::unique(es.begin(), es.end(), [](const Entry& a, const Entry& b) { return a.t == b.t && a.x == b.x && a.y == b.y; }), es.end());
     const size_t T = es.size();
-    out->assign(3 * T, 0);
-    for (size_t t = 0; t < T; t++) (*out)[t] = es[t].x, (*out)[T + t] = es[t].y, (*out)[2 * T + t] = es[t].cell;
+    out->assign(4 * T, 0);
+    for (size_t t = 0; t < T; t++) (*out)[t] = es[t].x, (*out)[T + t] = es[t].y, (*out)[2 * T + t] = es[t].cell, (*out)[3 * T + t] = es[t].t;
     return SIPP_OK;
 }
 
@@ -117,13 +139,13 @@ int read_flag(sipp_ctx* ctx, const uint32_t* d_flag, uint32_t* h) {
     return SIPP_OK;
 }
 
-// zero, count, read the flag back: the index is device memory (kx | ky | cell, T each)
+// zero, count, read the flag back: the index is device memory (kx | ky | cell | kt, T each)
 int multiplicities_indexed(sipp_ctx* ctx, uint64_t* d_wires, const uint64_t* d_consts, uint32_t log_n, const Lookup& l, const uint64_t* d_index,
                            uint32_t T) {
     ArenaScope scope(ctx, true);
     MultArgs a{};
     a.wires = d_wires; a.consts = d_consts; a.log_n = log_n; a.l = l;
-    a.ix = TableIndex{d_index, d_index + T, d_index + 2 * (size_t)T, T};
+    a.ix = TableIndex{d_index, d_index + T, d_index + 2 * (size_t)T, d_index + 3 * (size_t)T, T};
     a.flag = arena_alloc_t<uint32_t>(ctx, 1);
     if (!a.flag) return SIPP_E_NOMEM;
     SIPP_CHECK_HIP(ctx, hipMemsetAsync(a.flag, 0, 4, ctx->stream));
@@ -131,12 +153,13 @@ int multiplicities_indexed(sipp_ctx* ctx, uint64_t* d_wires, const uint64_t* d_c
     {
         ProfScope ps(ctx, "lookup_mult");
         hipLaunchKernelGGL(lookup_zero_kernel, dim3((unsigned)((n + 255) / 256), l.n_tab), dim3(256), 0, ctx->stream, a);
-        hipLaunchKernelGGL(lookup_count_kernel, dim3((unsigned)((n + 255) / 256), l.n_look), dim3(256), 0, ctx->stream, a);
+        hipLaunchKernelGGL(l.tagged() ? lookup_count_kernel<true> : lookup_count_kernel<false>, dim3((unsigned)((n + 255) / 256), l.n_look), dim3(256),
+                           0, ctx->stream, a);
     }
     SIPP_CHECK_HIP(ctx, hipGetLastError());
     uint32_t flag = 0;
     SIPP_TRY(read_flag(ctx, a.flag, &flag));
-    if (flag) return sipp_fail(ctx, SIPP_E_WITNESS, "lookup: a looked-up pair is in no table slot");
+    if (flag) return sipp_fail(ctx, SIPP_E_WITNESS, "lookup: a looked-up pair is in no table slot (of its row's tag)");
     return SIPP_OK;
 }
 
@@ -153,11 +176,18 @@ struct SumArgs {
 };
 
 // A group's sum of 1 / d_k (looking) or m_k / e_k (table) as ONE fraction: slot by slot  N / Dn + m / d = (N d + m Dn) / (Dn d)
+template <bool TAGGED>
 __global__ void __launch_bounds__(256) lookup_group_kernel(SumArgs a) {
     const uint32_t n = 1u << a.log_n, i = blockIdx.x * blockDim.x + threadIdx.x, c = blockIdx.y;
     if (i >= n) return;
     const uint32_t J = a.Jl + a.Jt;
-    const uint64_t eta = a.eta[c], theta = a.theta[c];
+    const uint64_t eta = a.eta[c];
+    uint64_t theta_l = a.theta[c], theta_t = theta_l;     // theta - eta^2 tag: all slots of a row share its tag
+    if (TAGGED) {
+        const uint64_t eta2 = gl::mul(eta, eta);
+        theta_l = gl::sub(theta_l, gl::mul(eta2, a.consts[(size_t)a.l.tag_const0 * n + i]));
+        theta_t = gl::sub(theta_t, gl::mul(eta2, a.consts[(size_t)(a.l.tag_const0 + 1) * n + i]));
+    }
     const bool look = gl::canon(a.consts[(size_t)a.l.q_look * n + i]) != 0, tab = gl::canon(a.consts[(size_t)a.l.q_tab * n + i]) != 0;
     uint64_t* g = a.grp + (size_t)c * J * n + i;
     uint64_t num[MAX_GROUPS], pre[MAX_GROUPS];         // group numerators; prefix products of the group denominators
@@ -179,7 +209,7 @@ __global__ void __launch_bounds__(256) lookup_group_kernel(SumArgs a) {
                     vy = a.consts[(size_t)(a.l.tab_const0 + 2 * k + 1) * n + i];
                     m = gl::canon(a.wires[(size_t)(a.l.tab_mult0 + k) * n + i]);
                 }
-                const uint64_t d = gl::sub(theta, gl::mad(eta, vy, gl::canon(vx)));      // theta - (x + eta y)
+                const uint64_t d = gl::sub(lk ? theta_l : theta_t, gl::mad(eta, vy, gl::canon(vx)));      // theta - (x + eta y + eta^2 tag)
                 hit |= d == 0;
                 N = gl::add(gl::mul(N, d), lk ? Dn : gl::mul(m, Dn));
                 Dn = gl::mul(Dn, d);
@@ -273,7 +303,7 @@ int sipp_plonk_lookup_multiplicities(sipp_ctx* ctx, uint64_t* d_wires, const uin
     if (!d) return SIPP_E_NOMEM;
     if (!h.empty()) SIPP_CHECK_HIP(ctx, hipMemcpyAsync(d, h.data(), h.size() * 8, hipMemcpyHostToDevice, ctx->stream));
     SIPP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));   // `h` is host memory
-    return multiplicities_indexed(ctx, d_wires, d_constants, log_n, l, d, (uint32_t)(h.size() / 3));
+    return multiplicities_indexed(ctx, d_wires, d_constants, log_n, l, d, (uint32_t)(h.size() / 4));
 }
 
 int sipp_plonk_lookup_sums(sipp_ctx* ctx, const uint64_t* d_wires, const uint64_t* d_constants, uint32_t log_n, uint32_t num_wires,
@@ -301,7 +331,8 @@ int sipp_plonk_lookup_sums(sipp_ctx* ctx, const uint64_t* d_wires, const uint64_
     SIPP_CHECK_HIP(ctx, hipMemsetAsync(a.flag, 0, 4, ctx->stream));
     {
         ProfScope ps(ctx, "lookup_sums");
-        hipLaunchKernelGGL(lookup_group_kernel, dim3((unsigned)((n + 255) / 256), C), dim3(256), 0, ctx->stream, a);
+        hipLaunchKernelGGL(l.tagged() ? lookup_group_kernel<true> : lookup_group_kernel<false>, dim3((unsigned)((n + 255) / 256), C), dim3(256), 0,
+                           ctx->stream, a);
         hipLaunchKernelGGL(lookup_scan_kernel, dim3(C), dim3(1024), 0, ctx->stream, a.tot, d_out, log_n);
         hipLaunchKernelGGL(lookup_u_kernel, dim3((unsigned)((n + 255) / 256), C), dim3(256), 0, ctx->stream, a.grp, d_out, log_n, J, C);
     }
@@ -331,6 +362,7 @@ struct LqArgs {
     uint64_t* qv;             // [C][n D]
 };
 
+template <bool TAGGED>
 __global__ void __launch_bounds__(256) lookup_quotient_kernel(LqArgs a) {
     const uint32_t lq = a.log_n + a.log_d, nd = 1u << lq, pos = blockIdx.x * blockDim.x + threadIdx.x;
     if (pos >= nd) return;
@@ -356,7 +388,13 @@ __global__ void __launch_bounds__(256) lookup_quotient_kernel(LqArgs a) {
     for (uint32_t c = 0; c < C; c++) push(gl::mul(l0, a.sl[(size_t)c * a.stride + pos]));
     const uint64_t ql = a.cl[(size_t)a.l.q_look * a.stride + pos], qt = a.cl[(size_t)a.l.q_tab * a.stride + pos];
     for (uint32_t c = 0; c < C; c++) {
-        const uint64_t eta = a.eta[c], theta = a.theta[c];
+        const uint64_t eta = a.eta[c];
+        uint64_t theta_l = a.theta[c], theta_t = theta_l;     // theta - eta^2 tag(x): the tag columns' polynomials on the coset
+        if (TAGGED) {                                         // (88 VGPRs against 74 without the tags, held or read per challenge)
+            const uint64_t eta2 = gl::mul(eta, eta);
+            theta_l = gl::sub(theta_l, gl::mul(eta2, a.cl[(size_t)a.l.tag_const0 * a.stride + pos]));
+            theta_t = gl::sub(theta_t, gl::mul(eta2, a.cl[(size_t)(a.l.tag_const0 + 1) * a.stride + pos]));
+        }
         uint64_t prev = a.sl[(size_t)c * a.stride + pos];
         for (uint32_t j = 0; j < J; j++) {
             const bool lk = j < a.Jl;
@@ -372,7 +410,7 @@ __global__ void __launch_bounds__(256) lookup_quotient_kernel(LqArgs a) {
                     vy = a.cl[(size_t)(a.l.tab_const0 + 2 * k + 1) * a.stride + pos];
                     m = a.wl[(size_t)(a.l.tab_mult0 + k) * a.stride + pos];
                 }
-                const uint64_t d = gl::sub(theta, gl::mad(eta, vy, vx));
+                const uint64_t d = gl::sub(lk ? theta_l : theta_t, gl::mad(eta, vy, vx));
                 N = gl::add(gl::mul(N, d), lk ? Dn : gl::mul(m, Dn));
                 Dn = gl::mul(Dn, d);
             }
@@ -396,13 +434,13 @@ int sipp_lookup_check(sipp_ctx* ctx, const uint32_t* lookup, uint32_t num_wires,
 }
 
 int sipp_lookup_index_host(sipp_ctx* ctx, const uint64_t* d_constants, uint32_t log_n, const uint32_t* lookup, std::vector<uint64_t>* out) {
-    const Lookup l{lookup[0], lookup[1], lookup[2], lookup[3], lookup[4], lookup[5], lookup[6]};
+    const Lookup l = lookup_of(lookup);
     return index_host(ctx, d_constants, log_n, l, out);
 }
 
 int sipp_lookup_multiplicities_indexed(sipp_ctx* ctx, uint64_t* d_wires, const uint64_t* d_constants, uint32_t log_n, const uint32_t* lookup,
                                        const uint64_t* d_index, uint32_t n_index) {
-    const Lookup l{lookup[0], lookup[1], lookup[2], lookup[3], lookup[4], lookup[5], lookup[6]};
+    const Lookup l = lookup_of(lookup);
     return multiplicities_indexed(ctx, d_wires, d_constants, log_n, l, d_index, n_index);
 }
 
@@ -416,7 +454,7 @@ int sipp_lookup_quotient_terms(sipp_ctx* ctx, const uint64_t* d_wires_lde, const
     LqArgs a{};
     a.wl = d_wires_lde; a.cl = d_consts_lde; a.sl = d_sums_lde; a.stride = n << rate_bits;
     a.log_n = log_n; a.rate_bits = rate_bits; a.log_d = log_d; a.D = p->max_degree; a.C = p->num_challenges;
-    a.l = Lookup{lookup[0], lookup[1], lookup[2], lookup[3], lookup[4], lookup[5], lookup[6]};
+    a.l = lookup_of(lookup);
     a.Jl = groups(a.l.n_look, a.D); a.Jt = groups(a.l.n_tab, a.D);
     for (uint32_t c = 0; c < a.C; c++) {
         a.eta[c] = gl::canon(etas[c]); a.theta[c] = gl::canon(thetas[c]); a.alpha[c] = gl::canon(alphas[c]);
@@ -437,7 +475,8 @@ int sipp_lookup_quotient_terms(sipp_ctx* ctx, const uint64_t* d_wires_lde, const
     const size_t nd = n << log_d;
     {
         ProfScope ps(ctx, "lookup_quotient");
-        hipLaunchKernelGGL(lookup_quotient_kernel, dim3((unsigned)((nd + 255) / 256)), dim3(256), 0, ctx->stream, a);
+        hipLaunchKernelGGL(a.l.tagged() ? lookup_quotient_kernel<true> : lookup_quotient_kernel<false>, dim3((unsigned)((nd + 255) / 256)), dim3(256), 0,
+                           ctx->stream, a);
     }
     SIPP_CHECK_HIP(ctx, hipGetLastError());
     return SIPP_OK;

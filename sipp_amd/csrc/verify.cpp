@@ -993,7 +993,8 @@ bool circuit_ok(const sipp_plonk_circuit& c, const sipp_plonk_params& p) {
 // behind the gammas, the S / U columns behind the permutation's (S again at g zeta), the lookup terms behind the gate constraints.
 bool lookup_ok(const uint32_t* w, const sipp_plonk_circuit& c) {
     // every bound before anything is sized by these words (the refusals of sipp_plonk_prove_gates_lookup)
-    if (w[2] == 0 || w[6] == 0 || w[2] > 128 || w[6] > 128 || w[7] != 0 || c.num_wires > 4096 || c.num_constants > 1024) return false;
+    if (w[2] == 0 || w[6] == 0 || w[2] > 128 || w[6] > 128 || c.num_wires > 4096 || c.num_constants > 1024) return false;
+    if (w[7] != 0 && (w[7] < c.num_selectors || (uint64_t)w[7] + 1 >= c.num_constants)) return false;      // the two tag columns
     if (w[0] >= c.num_constants || w[3] >= c.num_constants || w[0] < c.num_selectors || w[3] < c.num_selectors) return false;
     if (w[1] >= c.num_wires || w[1] + 2 * w[2] > c.num_wires || w[5] >= c.num_wires || w[5] + w[6] > c.num_wires) return false;
     return w[4] < c.num_constants && w[4] + 2 * w[6] <= c.num_constants;
@@ -1101,8 +1102,10 @@ int plonk_verify(const uint64_t* proof, size_t len, const uint64_t* cs_cap, cons
             // L_0(zeta) S_c(zeta), then per challenge the chain  (U_j - U_(j-1)) Dl - q_look Nl,  (U_j - U_(j-1)) Dt + q_tab Nt
             // with U_(-1) = S(zeta), U_(J-1) = S(g zeta)
             for (uint32_t cc = 0; cc < C; cc++) terms.push_back(gl::mul(l0, ss[cc]));
-            const E2 ql = cv[lk[0]], qt = cv[lk[3]];
+            // several tables (word 7): a combination is x + eta y + eta^2 tag, the tag of the looking / the table row a constant column
+            const E2 ql = cv[lk[0]], qt = cv[lk[3]], tag_l = lk[7] ? cv[lk[7]] : e2(0), tag_t = lk[7] ? cv[lk[7] + 1] : e2(0);
             for (uint32_t cc = 0; cc < C; cc++) {
+                const uint64_t eta2 = gl::mul(etas[cc], etas[cc]);
                 E2 prev = ss[cc];
                 for (uint32_t j = 0; j < J; j++) {
                     const bool look = j < Jl;
@@ -1110,7 +1113,9 @@ int plonk_verify(const uint64_t* proof, size_t len, const uint64_t* cs_cap, cons
                     E2 N = e2(0), Dn = e2(1);
                     for (uint32_t k = jj * D; k < (jj + 1) * D && k < cnt; k++) {
                         const E2 vx = look ? wv[lk[1] + 2 * k] : cv[lk[4] + 2 * k], vy = look ? wv[lk[1] + 2 * k + 1] : cv[lk[4] + 2 * k + 1];
-                        const E2 d = gl::sub(e2(thetas[cc]), gl::add(vx, gl::scale(vy, etas[cc])));
+                        E2 comb = gl::add(vx, gl::scale(vy, etas[cc]));
+                        if (lk[7]) comb = gl::add(comb, gl::scale(look ? tag_l : tag_t, eta2));
+                        const E2 d = gl::sub(e2(thetas[cc]), comb);
                         N = gl::add(gl::mul(N, d), look ? Dn : gl::mul(wv[lk[5] + k], Dn));
                         Dn = gl::mul(Dn, d);
                     }

@@ -22,6 +22,8 @@
 // the multiplicand of an ArithmeticExtension-shaped row from its output: the one generator here that inverts.
 // The recursive evaluation of the Poseidon gate (recalled gates/poseidon_mds.rs) adds SIPP_GEN_POSEIDON_MDS, the linear layer on twelve
 // extension elements: a case of run_generator on one lane, wherever the row runs.
+// SIPP_GEN_LOOKUP is the library's own (no upstream gate): a looking row of the lookup argument (lookup.hip) takes its y cells from a dense
+// table in the constant columns, y = f(x) by address, no index; also one lane, wherever the row runs.
 #include "ctx.hpp"
 #include "poseidon_constants.h"
 #include <mutex>
@@ -143,6 +145,29 @@ __device__ __forceinline__ void poseidon_mds_row(uint64_t* wires, uint32_t n, ui
             const uint64_t lo = al + (ah << 32);
             wires[(size_t)(out + 2 * r + l) * n + i] = gl::reduce96((uint32_t)(ah >> 32) + (lo < al ? 1u : 0u), lo);
         }
+    }
+}
+
+// SIPP_GEN_LOOKUP on row i: entry t of a dense table (x = t) sits in table row row0 + t / n_tab, slot t % n_tab; row0 and T are the row's
+// own constants.  An x outside the table (x >= T, or an entry row at or behind n) writes y = 0: the lookup argument refuses the row.
+// 64-bit row arithmetic: row0, T and x are any field values.  `span` = the entries whose row is inside the circuit, so x < min(T, span)
+// says both conditions and bounds x below n n_tab < 2^58 before it is divided.
+__device__ __forceinline__ void lookup_row(uint64_t* wires, const uint64_t* consts, uint32_t n, uint32_t i, const sipp_plonk_generator& g) {
+    const uint32_t lw = g.p[0], n_look = g.p[1], tc = g.p[2], n_tab = g.p[3], bc = g.p[4];
+    const uint64_t row0 = gl::canon(consts[(size_t)bc * n + i]), T = gl::canon(consts[(size_t)(bc + 1) * n + i]);
+    if (T == 0) return;                                       // a plain looking row: both coordinates are the circuit's
+    const uint64_t span = row0 < n ? (uint64_t)(n - (uint32_t)row0) * n_tab : 0;
+    const uint64_t lim = T < span ? T : span;
+#pragma unroll 1
+    for (uint32_t k = 0; k < n_look; k++) {
+        const uint64_t x = gl::canon(wires[(size_t)(lw + 2 * k) * n + i]);
+        uint64_t y = 0;
+        if (x < lim) {
+            const uint64_t q = x / n_tab;                     // < n - row0
+            const uint32_t slot = (uint32_t)(x - q * n_tab);
+            y = gl::canon(consts[(size_t)(tc + 2 * slot + 1) * n + (uint32_t)(row0 + q)]);
+        }
+        wires[(size_t)(lw + 2 * k + 1) * n + i] = y;
     }
 }
 
@@ -307,6 +332,9 @@ __device__ __forceinline__ void run_generator(uint64_t* wires, const uint64_t* c
     }
     case SIPP_GEN_POSEIDON_MDS:
         poseidon_mds_row(wires, n, i, g.p[0], g.p[1]);
+        break;
+    case SIPP_GEN_LOOKUP:
+        lookup_row(wires, consts, n, i, g);
         break;
     default: break;
     }
@@ -612,6 +640,9 @@ bool layout_ok(const sipp_plonk_generator& g, uint32_t num_wires, uint32_t num_c
         const uint64_t in = g.p[0], out = g.p[1];
         return in + 24 <= nw && out + 24 <= nw && (in + 24 <= out || out + 24 <= in);
     }
+    case SIPP_GEN_LOOKUP:
+        return g.p[1] >= 1 && g.p[3] >= 1 && (uint64_t)g.p[0] + 2ull * g.p[1] <= nw && (uint64_t)g.p[2] + 2ull * g.p[3] <= num_constants &&
+               (uint64_t)g.p[4] + 1 < num_constants;
     case SIPP_GEN_POSEIDON_SWAP: {
         // written cells (out, sbox, delta) must not meet the read cells (in, swap): the two launch paths read and write in different orders
         const uint64_t in = g.p[0], out = g.p[1], sb = g.p[2], sw = g.p[3], dl = g.p[4];
@@ -630,8 +661,9 @@ const char* gen_name(uint32_t kind) {
     static const char* names[] = {"", "witness_arithmetic", "witness_base_split", "witness_constant", "witness_public_input", "witness_u32",
                                   "witness_random_access", "witness_reducing", "witness_poseidon", "witness_poseidon_swap",
                                   "witness_arithmetic_ext", "witness_exponentiation", "witness_coset_interpolation",
-                                  "witness_reducing_ext", "witness_quotient_ext", "witness_base_sum", "witness_poseidon_mds"};
-    return kind <= SIPP_GEN_POSEIDON_MDS ? names[kind] : "witness";
+                                  "witness_reducing_ext", "witness_quotient_ext", "witness_base_sum", "witness_poseidon_mds",
+                                  "witness_lookup"};
+    return kind <= SIPP_GEN_LOOKUP ? names[kind] : "witness";
 }
 
 }  // namespace
