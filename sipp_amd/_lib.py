@@ -252,12 +252,9 @@ def plonk_verify_gates_lookup(proof, constants_sigmas_cap, p, fp, circuit, diges
     lookup description (eight words; an empty one: a "SIPPPLK3" proof).  Returns 0 for an accepted proof, else the refusing stage."""
     pf = np.ascontiguousarray(proof, dtype=np.uint64)
     cap = np.ascontiguousarray(constants_sigmas_cap, dtype=np.uint64).reshape(-1)
-    words = [int(x) for x in lookup]
-    if len(words) != 8:
-        raise SippError(-1, "a lookup description is eight words")
     reason = C.c_int(0)
     rc = lib().sipp_plonk_verify_gates_lookup(pf.ctypes.data_as(u64p), len(pf), cap.ctypes.data_as(u64p), C.byref(p), C.byref(fp), C.byref(circuit),
-                                              (C.c_uint64 * 4)(*[int(x) for x in digest]), (C.c_uint32 * 8)(*words), C.byref(reason))
+                                              (C.c_uint64 * 4)(*[int(x) for x in digest]), Ctx._lookup_words(lookup), C.byref(reason))
     if rc not in (0, SIPP_E_VERIFY):
         raise SippError(rc, "sipp_plonk_verify_gates_lookup")
     return reason.value
@@ -497,25 +494,30 @@ class Ctx:
                  "plonk_quotient_chunks_ex")
         return out
 
+    def _plonk_prove(self, fn, size_fn, cap, wires, second, wires_oracle, wires_cap, second_oracle, log_n, p, fp, circuit, digest, pis, extra):
+        """what the three proof calls share: a buffer of `cap` words (the answer of `size_fn`; 0 = refused), the wires cap as an array
+        that lives until the call returns, the call sipp_<fn> -- whose arguments differ in `circuit` (None: none) and in `extra`, the
+        ones between the public inputs and the buffer -- and the proof cut to its length"""
+        if cap == 0:
+            raise SippError(-1, size_fn)
+        out = np.zeros(cap, dtype=np.uint64)
+        n = C.c_size_t()
+        wc_arr = None if wires_cap is None else np.ascontiguousarray(wires_cap, dtype=np.uint64).reshape(-1)
+        args = [self.h, wires.data_ptr(), second.data_ptr(), None if wires_oracle is None else C.byref(wires_oracle),
+                None if wc_arr is None else wc_arr.ctypes.data_as(u64p), None if second_oracle is None else C.byref(second_oracle), log_n,
+                C.byref(p), C.byref(fp)] + ([] if circuit is None else [C.byref(circuit)])
+        args += [self._u64(digest), self._u64(pis) if pis else None, len(pis)] + list(extra) + [out.ctypes.data, cap, C.byref(n)]
+        self._ck(getattr(self.L, "sipp_" + fn)(*args), fn)
+        return out[: n.value]
+
     def plonk_prove_ex(self, wires, sigmas, log_n, p, fp, digest, public_inputs, gate_terms=None, wires_oracle=None, wires_cap=None,
                        sigmas_oracle=None):
         """sipp_plonk_prove_ex: the flow with gate terms, public inputs (host ints) and optional pre-committed oracles (Oracle structs)"""
         pis = [int(x) for x in public_inputs]
         cap = self.L.sipp_plonk_perm_proof_size(log_n, C.byref(p), C.byref(fp))
-        if cap == 0:
-            raise SippError(-1, "sipp_plonk_perm_proof_size")
-        cap += len(pis)
-        out = np.zeros(cap, dtype=np.uint64)
-        n = C.c_size_t()
-        k = 0 if gate_terms is None else gate_terms.shape[0]
-        wc_arr = None if wires_cap is None else np.ascontiguousarray(wires_cap, dtype=np.uint64).reshape(-1)     # alive until the call returns
-        wcap = None if wc_arr is None else wc_arr.ctypes.data_as(u64p)
-        self._ck(self.L.sipp_plonk_prove_ex(self.h, wires.data_ptr(), sigmas.data_ptr(), None if wires_oracle is None else C.byref(wires_oracle), wcap,
-                                            None if sigmas_oracle is None else C.byref(sigmas_oracle), log_n, C.byref(p), C.byref(fp),
-                                            self._u64(digest), self._u64(pis) if pis else None, len(pis),
-                                            None if gate_terms is None else gate_terms.data_ptr(), k, out.ctypes.data, cap, C.byref(n)),
-                 "plonk_prove_ex")
-        return out[: n.value]
+        extra = [None, 0] if gate_terms is None else [gate_terms.data_ptr(), gate_terms.shape[0]]
+        return self._plonk_prove("plonk_prove_ex", "sipp_plonk_perm_proof_size", cap and cap + len(pis), wires, sigmas, wires_oracle, wires_cap,
+                                 sigmas_oracle, log_n, p, fp, None, digest, pis, extra)
 
     def plonk_prove_gates(self, wires, constants_sigmas, log_n, p, fp, circuit, digest, public_inputs, wires_oracle=None, wires_cap=None,
                           cs_oracle=None):
@@ -523,18 +525,8 @@ class Ctx:
         circuit = PlonkCircuit; the gate constraints are interpreted inside the quotient kernel.  Returns the flat "SIPPPLK3" proof."""
         pis = [int(x) for x in public_inputs]
         cap = self.L.sipp_plonk_gates_proof_size(log_n, C.byref(p), C.byref(fp), C.byref(circuit), len(pis))
-        if cap == 0:
-            raise SippError(-1, "sipp_plonk_gates_proof_size")
-        out = np.zeros(cap, dtype=np.uint64)
-        n = C.c_size_t()
-        wc_arr = None if wires_cap is None else np.ascontiguousarray(wires_cap, dtype=np.uint64).reshape(-1)
-        wcap = None if wc_arr is None else wc_arr.ctypes.data_as(u64p)
-        self._ck(self.L.sipp_plonk_prove_gates(self.h, wires.data_ptr(), constants_sigmas.data_ptr(),
-                                               None if wires_oracle is None else C.byref(wires_oracle), wcap,
-                                               None if cs_oracle is None else C.byref(cs_oracle), log_n, C.byref(p), C.byref(fp), C.byref(circuit),
-                                               self._u64(digest), self._u64(pis) if pis else None, len(pis), out.ctypes.data, cap, C.byref(n)),
-                 "plonk_prove_gates")
-        return out[: n.value]
+        return self._plonk_prove("plonk_prove_gates", "sipp_plonk_gates_proof_size", cap, wires, constants_sigmas, wires_oracle, wires_cap,
+                                 cs_oracle, log_n, p, fp, circuit, digest, pis, [])
 
     def plonk_prove_gates_lookup(self, wires, constants_sigmas, log_n, p, fp, circuit, digest, public_inputs, lookup, wires_oracle=None,
                                  wires_cap=None, cs_oracle=None):
@@ -543,18 +535,8 @@ class Ctx:
         pis = [int(x) for x in public_inputs]
         words = self._lookup_words(lookup)
         cap = self.L.sipp_plonk_gates_lookup_proof_size(log_n, C.byref(p), C.byref(fp), C.byref(circuit), len(pis), words)
-        if cap == 0:
-            raise SippError(-1, "sipp_plonk_gates_lookup_proof_size")
-        out = np.zeros(cap, dtype=np.uint64)
-        n = C.c_size_t()
-        wc_arr = None if wires_cap is None else np.ascontiguousarray(wires_cap, dtype=np.uint64).reshape(-1)
-        wcap = None if wc_arr is None else wc_arr.ctypes.data_as(u64p)
-        self._ck(self.L.sipp_plonk_prove_gates_lookup(self.h, wires.data_ptr(), constants_sigmas.data_ptr(),
-                                                      None if wires_oracle is None else C.byref(wires_oracle), wcap,
-                                                      None if cs_oracle is None else C.byref(cs_oracle), log_n, C.byref(p), C.byref(fp),
-                                                      C.byref(circuit), self._u64(digest), self._u64(pis) if pis else None, len(pis), words,
-                                                      out.ctypes.data, cap, C.byref(n)), "plonk_prove_gates_lookup")
-        return out[: n.value]
+        return self._plonk_prove("plonk_prove_gates_lookup", "sipp_plonk_gates_lookup_proof_size", cap, wires, constants_sigmas, wires_oracle,
+                                 wires_cap, cs_oracle, log_n, p, fp, circuit, digest, pis, [words])
 
     def plonk_generate_witness(self, wires, constants, log_n, gens, pih=None):
         """sipp_plonk_generate_witness: the gates' witness generators, in place on the device wire table [num_wires][N]; constants

@@ -7,6 +7,8 @@
 #include "ctx.hpp"
 #include "host_challenger.hpp"
 
+#include <memory>
+
 struct sipp_circuit_data {
     sipp_ctx* ctx = nullptr;
     uint32_t log_n = 0;
@@ -28,11 +30,12 @@ struct sipp_circuit_data {
     uint64_t* d_map = nullptr;
     size_t map_n = 0, map_words = 0, map_extra = 0;
     bool has_map = false;
-    // the lookup description of sipp_circuit_set_lookup (all zero: none) and the sorted index of its table, a block of its own like the map
+    // the lookup description of sipp_circuit_set_lookup (all zero: none), as the eight words the C calls take and as their one reading,
+    // and the sorted index of its table, a block of its own like the map
     uint32_t lookup[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    plonk_desc::Lookup lk{};
     uint64_t* d_index = nullptr;
     uint32_t n_index = 0;
-    bool has_lookup() const { return lookup[2] != 0; }
     ~sipp_circuit_data() {
         if (ctx) (void)hipSetDevice(ctx->device);
         for (void* q : dev) (void)hipFree(q);
@@ -54,6 +57,30 @@ template <typename T>
 int dev_upload(sipp_circuit_data* cd, const T* host, size_t count, T** out) {
     SIPP_TRY(dev_alloc(cd, count, out));
     if (count) SIPP_CHECK_HIP(cd->ctx, hipMemcpy(*out, host, count * sizeof(T), hipMemcpyHostToDevice));
+    return SIPP_OK;
+}
+// A block the data owns by itself (the input map, the lookup index) takes new contents: the new block is allocated and filled first, and
+// only then does the old one go -- a refusal or a failed upload leaves the previous block, and what the caller keeps beside it, in
+// force.  No kernel reads the old block any more: a proof ends on the host.  `parts`: host arrays laid back to back, `count` words each;
+// `who` opens the messages
+int replace_block(sipp_circuit_data* cd, uint64_t** block, std::initializer_list<const uint64_t*> parts, size_t count, const std::string& who) {
+    sipp_ctx* ctx = cd->ctx;
+    void* q = nullptr;
+    if (hipMalloc(&q, (count ? parts.size() * count : 1) * 8) != hipSuccess) return sipp_fail(ctx, SIPP_E_NOMEM, (who + ": hipMalloc failed").c_str());
+    uint64_t* d_new = reinterpret_cast<uint64_t*>(q);
+    size_t at = 0;
+    for (const uint64_t* part : parts) {
+        if (count && hipMemcpy(d_new + at, part, count * 8, hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipFree(q);
+            return sipp_fail(ctx, SIPP_E_HIP, (who + ": upload failed").c_str());
+        }
+        at += count;
+    }
+    if (*block) {
+        (void)hipStreamSynchronize(ctx->stream);
+        (void)hipFree(*block);
+    }
+    *block = d_new;
     return SIPP_OK;
 }
 uint32_t zs_columns(const sipp_plonk_params* p) { return p->num_challenges * ((p->num_routed_wires + p->max_degree - 1) / p->max_degree); }
@@ -94,9 +121,11 @@ extern "C" int sipp_circuit_build(sipp_ctx* ctx, uint32_t log_n, const sipp_plon
         return sipp_fail(ctx, SIPP_E_BADARG, "circuit build: more than 32 generators with a level schedule");
     SIPP_TRY(sipp_plonk_circuit_check(ctx, c, p));          // a malformed gate set is refused here, not at the first proof
     SIPP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    // owned from here to `*out`: every return in between, the SIPP_TRY / SIPP_CHECK_HIP ones included, releases the object and its device memory
+    std::unique_ptr<sipp_circuit_data> owner;
     sipp_circuit_data* cd = nullptr;
     try {
-        cd = new sipp_circuit_data();
+        owner.reset(cd = new sipp_circuit_data());
         cd->ctx = ctx; cd->log_n = log_n; cd->p = *p; cd->fp = *fp;
         cd->gates.assign(c->gates, c->gates + c->num_gates);
         cd->programs.assign(c->programs, c->programs + c->program_words);
@@ -106,43 +135,36 @@ extern "C" int sipp_circuit_build(sipp_ctx* ctx, uint32_t log_n, const sipp_plon
             cd->copy_offsets.assign(sched->copy_offsets, sched->copy_offsets + sched->n_levels + 1);
         }
     } catch (const std::bad_alloc&) {
-        delete cd;
         return sipp_fail(ctx, SIPP_E_NOMEM, "circuit build: host allocation failed");
     }
     cd->circ = *c;
     cd->circ.gates = cd->gates.data();
     cd->circ.programs = cd->programs.data();
-    auto bail = [&](int rc) {
-        delete cd;
-        return rc;
-    };
     const size_t n = (size_t)1 << log_n, ncols = (size_t)c->num_constants + p->num_routed_wires, m = n << fp->rate_bits;
-    int rc;
     if (sched && sched->n_levels) {
         const uint32_t L = sched->n_levels;
         for (uint32_t l = 0; l < L; l++)
             if (sched->level_offsets[l] > sched->level_offsets[l + 1] || sched->copy_offsets[l] > sched->copy_offsets[l + 1])
-                return bail(sipp_fail(ctx, SIPP_E_BADARG, "circuit build: schedule offsets must not decrease"));
-        if (sched->level_offsets[L] > n) return bail(sipp_fail(ctx, SIPP_E_BADARG, "circuit build: more scheduled rows than the table has"));
+                return sipp_fail(ctx, SIPP_E_BADARG, "circuit build: schedule offsets must not decrease");
+        if (sched->level_offsets[L] > n) return sipp_fail(ctx, SIPP_E_BADARG, "circuit build: more scheduled rows than the table has");
         uint32_t* d_rows = nullptr;
         uint64_t *d_src = nullptr, *d_dst = nullptr;
-        if ((rc = dev_upload(cd, sched->rows, sched->level_offsets[L], &d_rows)) != SIPP_OK) return bail(rc);
-        if ((rc = dev_upload(cd, sched->copy_src, sched->copy_offsets[L], &d_src)) != SIPP_OK) return bail(rc);
-        if ((rc = dev_upload(cd, sched->copy_dst, sched->copy_offsets[L], &d_dst)) != SIPP_OK) return bail(rc);
+        SIPP_TRY(dev_upload(cd, sched->rows, sched->level_offsets[L], &d_rows));
+        SIPP_TRY(dev_upload(cd, sched->copy_src, sched->copy_offsets[L], &d_src));
+        SIPP_TRY(dev_upload(cd, sched->copy_dst, sched->copy_offsets[L], &d_dst));
         cd->has_sched = true;
         cd->sched.n_levels = L; cd->sched.d_rows = d_rows; cd->sched.d_copy_src = d_src; cd->sched.d_copy_dst = d_dst;
         cd->sched.level_offsets = cd->level_offsets.data(); cd->sched.copy_offsets = cd->copy_offsets.data();
     }
     uint64_t *d_coeffs = nullptr, *d_lde = nullptr, *d_tree = nullptr;
-    if ((rc = dev_upload(cd, constants_sigmas, ncols * n, &cd->d_cs)) != SIPP_OK) return bail(rc);
-    if ((rc = dev_alloc(cd, (size_t)c->num_wires * n, &cd->d_wires)) != SIPP_OK) return bail(rc);
-    if ((rc = dev_alloc(cd, ncols * n, &d_coeffs)) != SIPP_OK) return bail(rc);
-    if ((rc = dev_alloc(cd, ncols * m, &d_lde)) != SIPP_OK) return bail(rc);
-    if ((rc = dev_alloc(cd, 2 * m * 4, &d_tree)) != SIPP_OK) return bail(rc);
+    SIPP_TRY(dev_upload(cd, constants_sigmas, ncols * n, &cd->d_cs));
+    SIPP_TRY(dev_alloc(cd, (size_t)c->num_wires * n, &cd->d_wires));
+    SIPP_TRY(dev_alloc(cd, ncols * n, &d_coeffs));
+    SIPP_TRY(dev_alloc(cd, ncols * m, &d_lde));
+    SIPP_TRY(dev_alloc(cd, 2 * m * 4, &d_tree));
     const uint32_t ch = fp->cap_height < log_n + fp->rate_bits ? fp->cap_height : log_n + fp->rate_bits;
     cd->cap.assign(((size_t)4) << ch, 0);
-    rc = sipp_commit_batch_ex(ctx, cd->d_cs, 0, d_coeffs, d_lde, d_tree, ncols, log_n, fp->rate_bits, fp->cap_height, nullptr, 0, cd->cap.data());
-    if (rc != SIPP_OK) return bail(rc);
+    SIPP_TRY(sipp_commit_batch_ex(ctx, cd->d_cs, 0, d_coeffs, d_lde, d_tree, ncols, log_n, fp->rate_bits, fp->cap_height, nullptr, 0, cd->cap.data()));
     SIPP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     cd->cs_oracle.d_coeffs = d_coeffs; cd->cs_oracle.d_lde = d_lde; cd->cs_oracle.d_tree = d_tree;
     cd->cs_oracle.n_polys = (uint32_t)ncols; cd->cs_oracle.n_salt = 0;
@@ -155,8 +177,8 @@ extern "C" int sipp_circuit_build(sipp_ctx* ctx, uint32_t log_n, const sipp_plon
             w.push_back(v);
         host::Challenger::hash_no_pad(w.data(), w.size(), cd->digest);
     }
-    if (sipp_plonk_gates_proof_size(log_n, p, fp, &cd->circ, 0) == 0) return bail(sipp_fail(ctx, SIPP_E_BADARG, "circuit build: parameters or gate set refused"));
-    *out = cd;
+    if (sipp_plonk_gates_proof_size(log_n, p, fp, &cd->circ, 0) == 0) return sipp_fail(ctx, SIPP_E_BADARG, "circuit build: parameters or gate set refused");
+    *out = owner.release();
     return SIPP_OK;
 }
 
@@ -184,41 +206,54 @@ int prove_uploaded(sipp_circuit_data* cd, const uint64_t* public_inputs, uint32_
     else
         SIPP_TRY(sipp_plonk_generate_witness(ctx, cd->d_wires, cd->d_cs, cd->log_n, cd->circ.num_wires, cd->circ.num_constants, cd->gens.data(),
                                              cd->gens.size(), pih));
-    if (!cd->has_lookup())
+    if (cd->lk.empty())
         return sipp_plonk_prove_gates(ctx, cd->d_wires, cd->d_cs, nullptr, nullptr, &cd->cs_oracle, cd->log_n, &cd->p, &cd->fp, &cd->circ, cd->digest,
                                       public_inputs, n_public_inputs, proof_out, proof_cap, proof_len);
     // the multiplicities behind witness generation: the looking wires are the generators' outputs (or the caller's cells)
-    SIPP_TRY(sipp_lookup_multiplicities_indexed(ctx, cd->d_wires, cd->d_cs, cd->log_n, cd->lookup, cd->d_index, cd->n_index));
+    SIPP_TRY(sipp_lookup_multiplicities_indexed(ctx, cd->d_wires, cd->d_cs, cd->log_n, cd->lk, cd->d_index, cd->n_index));
     return sipp_plonk_prove_gates_lookup(ctx, cd->d_wires, cd->d_cs, nullptr, nullptr, &cd->cs_oracle, cd->log_n, &cd->p, &cd->fp, &cd->circ,
                                          cd->digest, public_inputs, n_public_inputs, cd->lookup, proof_out, proof_cap, proof_len);
 }
 
-// the input cells of sipp_circuit_prove_inputs: one lane per pair, grid-stride.  Pairs that name one cell race; whichever store lands,
-// the check pass below sees every pair whose value the table does not hold.
-__global__ void __launch_bounds__(256) circuit_scatter_inputs_kernel(uint64_t* wires, const uint64_t* cells, const uint64_t* values, size_t count) {
+// The input cells of a proof: pair k puts its value at cells[k], one lane per pair, grid-stride.  MAPPED: the value is
+// staged[sources[k]] (sipp_circuit_prove_words: the staged words through the data's input map; every source is below the staged length,
+// sipp_circuit_set_input_map refuses a map where one is not), else staged[k] (sipp_circuit_prove_inputs).  Pairs that name one cell race;
+// whichever store lands, the check pass sees every pair whose value the table does not hold.
+template <bool MAPPED>
+__global__ void __launch_bounds__(256) circuit_scatter_kernel(uint64_t* wires, const uint64_t* cells, const uint64_t* sources, const uint64_t* staged,
+                                                              size_t count) {
     const size_t step = (size_t)gridDim.x * blockDim.x;
-    for (size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x; k < count; k += step) wires[cells[k]] = values[k];
+    for (size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x; k < count; k += step) wires[cells[k]] = staged[MAPPED ? sources[k] : k];
 }
-__global__ void __launch_bounds__(256) circuit_check_inputs_kernel(const uint64_t* wires, const uint64_t* cells, const uint64_t* values, size_t count,
-                                                                   unsigned int* conflict) {
+template <bool MAPPED>
+__global__ void __launch_bounds__(256) circuit_check_kernel(const uint64_t* wires, const uint64_t* cells, const uint64_t* sources, const uint64_t* staged,
+                                                            size_t count, unsigned int* conflict) {
     const size_t step = (size_t)gridDim.x * blockDim.x;
     bool bad = false;
-    for (size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x; k < count; k += step) bad |= wires[cells[k]] != values[k];
+    for (size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x; k < count; k += step) bad |= wires[cells[k]] != staged[MAPPED ? sources[k] : k];
     if (bad) atomicOr(conflict, 1u);
 }
-// the same two passes for sipp_circuit_prove_words: pair k takes its value from the staged words through the data's input map.  Every
-// cell is below the table's size and every source below the staged length: sipp_circuit_set_input_map refuses a map where one is not.
-__global__ void __launch_bounds__(256) circuit_scatter_words_kernel(uint64_t* wires, const uint64_t* cells, const uint64_t* sources,
-                                                                    const uint64_t* staged, size_t count) {
-    const size_t step = (size_t)gridDim.x * blockDim.x;
-    for (size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x; k < count; k += step) wires[cells[k]] = staged[sources[k]];
-}
-__global__ void __launch_bounds__(256) circuit_check_words_kernel(const uint64_t* wires, const uint64_t* cells, const uint64_t* sources,
-                                                                  const uint64_t* staged, size_t count, unsigned int* conflict) {
-    const size_t step = (size_t)gridDim.x * blockDim.x;
-    bool bad = false;
-    for (size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x; k < count; k += step) bad |= wires[cells[k]] != staged[sources[k]];
-    if (bad) atomicOr(conflict, 1u);
+
+// zero the wire table, scatter the `count` pairs, check them, wait for the flag and refuse, with the caller's words, one cell that took
+// two different values.  Device pointers (every cell below the table's size: the callers' host checks); d_sources == nullptr: pair k
+// takes d_staged[k].  The wait has ended every kernel that reads the caller's staging, which may go back to the arena before witness generation.
+int stage_inputs(sipp_circuit_data* cd, const uint64_t* d_cells, const uint64_t* d_sources, const uint64_t* d_staged, size_t count,
+                 unsigned int* d_conflict, const char* refusal) {
+    sipp_ctx* ctx = cd->ctx;
+    SIPP_CHECK_HIP(ctx, hipMemsetAsync(cd->d_wires, 0, ((size_t)cd->circ.num_wires << cd->log_n) * 8, ctx->stream));
+    if (!count) return SIPP_OK;
+    SIPP_CHECK_HIP(ctx, hipMemsetAsync(d_conflict, 0, 8, ctx->stream));
+    const size_t want = (count + 255) / 256;
+    const dim3 grid((unsigned)(want < 4096 ? want : 4096));
+    hipLaunchKernelGGL(d_sources ? circuit_scatter_kernel<true> : circuit_scatter_kernel<false>, grid, dim3(256), 0, ctx->stream, cd->d_wires, d_cells,
+                       d_sources, d_staged, count);
+    hipLaunchKernelGGL(d_sources ? circuit_check_kernel<true> : circuit_check_kernel<false>, grid, dim3(256), 0, ctx->stream, cd->d_wires, d_cells,
+                       d_sources, d_staged, count, d_conflict);
+    SIPP_CHECK_HIP(ctx, hipGetLastError());
+    unsigned int flag = 0;
+    SIPP_CHECK_HIP(ctx, hipMemcpyAsync(&flag, d_conflict, sizeof flag, hipMemcpyDeviceToHost, ctx->stream));
+    SIPP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return flag ? sipp_fail(ctx, SIPP_E_BADARG, refusal) : SIPP_OK;
 }
 }  // namespace
 
@@ -234,50 +269,31 @@ extern "C" int sipp_circuit_set_input_map(sipp_circuit_data* cd, const uint64_t*
         if (sources[k] >= staged) return sipp_fail(ctx, SIPP_E_BADARG, "circuit input map: a source outside words || extra");
     }
     SIPP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    void* q = nullptr;
-    if (hipMalloc(&q, (n ? 2 * n : 1) * 8) != hipSuccess) return sipp_fail(ctx, SIPP_E_NOMEM, "circuit input map: hipMalloc failed");
-    uint64_t* d_new = reinterpret_cast<uint64_t*>(q);
-    if (n && (hipMemcpy(d_new, cells, n * 8, hipMemcpyHostToDevice) != hipSuccess ||
-              hipMemcpy(d_new + n, sources, n * 8, hipMemcpyHostToDevice) != hipSuccess)) {
-        (void)hipFree(q);
-        return sipp_fail(ctx, SIPP_E_HIP, "circuit input map: upload failed");
-    }
-    // the old map goes only now: every refusal above has left it in force.  No kernel reads it any more: a proof ends on the host
-    if (cd->d_map) {
-        (void)hipStreamSynchronize(ctx->stream);
-        (void)hipFree(cd->d_map);
-    }
-    cd->d_map = d_new; cd->map_n = n; cd->map_words = n_words; cd->map_extra = n_extra; cd->has_map = true;
+    SIPP_TRY(replace_block(cd, &cd->d_map, {cells, sources}, n, "circuit input map"));
+    cd->map_n = n; cd->map_words = n_words; cd->map_extra = n_extra; cd->has_map = true;
     return SIPP_OK;
 }
 
 extern "C" int sipp_circuit_set_lookup(sipp_circuit_data* cd, const uint32_t* lookup) {
     if (!cd) return SIPP_E_BADARG;
     sipp_ctx* ctx = cd->ctx;
-    SIPP_TRY(sipp_lookup_check(ctx, lookup, cd->circ.num_wires, cd->circ.num_constants, cd->circ.num_selectors));
+    plonk_desc::Lookup l;
+    SIPP_TRY(sipp_lookup_check(ctx, lookup, cd->circ.num_wires, cd->circ.num_constants, cd->circ.num_selectors, &l));
     SIPP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    const bool empty = lookup[2] == 0 && lookup[6] == 0;
-    uint64_t* d_new = nullptr;
     std::vector<uint64_t> index;
-    if (!empty) {
+    if (!l.empty()) {
         if (sipp_plonk_gates_lookup_proof_size(cd->log_n, &cd->p, &cd->fp, &cd->circ, 0, lookup) == 0)
             return sipp_fail(ctx, SIPP_E_BADARG, "circuit lookup: the description does not fit the parameters");
-        SIPP_TRY(sipp_lookup_index_host(ctx, cd->d_cs, cd->log_n, lookup, &index));
-        void* q = nullptr;
-        if (hipMalloc(&q, (index.empty() ? 1 : index.size()) * 8) != hipSuccess) return sipp_fail(ctx, SIPP_E_NOMEM, "circuit lookup: hipMalloc failed");
-        d_new = reinterpret_cast<uint64_t*>(q);
-        if (!index.empty() && hipMemcpy(d_new, index.data(), index.size() * 8, hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipFree(q);
-            return sipp_fail(ctx, SIPP_E_HIP, "circuit lookup: upload failed");
-        }
-    }
-    // the old index goes only now: every refusal above has left the description before in force.  No kernel reads it: a proof ends on the host
-    if (cd->d_index) {
+        SIPP_TRY(sipp_lookup_index_host(ctx, cd->d_cs, cd->log_n, l, &index));
+        SIPP_TRY(replace_block(cd, &cd->d_index, {index.data()}, index.size(), "circuit lookup"));
+    } else if (cd->d_index) {      // back to no lookups: the index goes, behind every refusal like a replaced one
         (void)hipStreamSynchronize(ctx->stream);
         (void)hipFree(cd->d_index);
+        cd->d_index = nullptr;
     }
-    cd->d_index = d_new; cd->n_index = (uint32_t)(index.size() / 4);
-    for (int q = 0; q < 8; q++) cd->lookup[q] = empty ? 0 : lookup[q];
+    cd->n_index = (uint32_t)(index.size() / 4);
+    cd->lk = l.empty() ? plonk_desc::Lookup{} : l;
+    for (int q = 0; q < 8; q++) cd->lookup[q] = l.empty() ? 0 : lookup[q];
     return SIPP_OK;
 }
 
@@ -311,22 +327,12 @@ extern "C" int sipp_circuit_prove_inputs(sipp_circuit_data* cd, const uint64_t* 
         uint64_t* d_pairs = arena_alloc_t<uint64_t>(ctx, 2 * n_inputs + 1);          // cells, values, the flag's word
         if (!d_pairs) return SIPP_E_NOMEM;
         uint64_t *d_cells = d_pairs, *d_values = d_pairs + n_inputs;
-        unsigned int* d_conflict = reinterpret_cast<unsigned int*>(d_pairs + 2 * n_inputs);
-        SIPP_CHECK_HIP(ctx, hipMemsetAsync(cd->d_wires, 0, total * 8, ctx->stream));
         if (n_inputs) {
-            SIPP_CHECK_HIP(ctx, hipMemsetAsync(d_conflict, 0, 8, ctx->stream));
             SIPP_CHECK_HIP(ctx, hipMemcpyAsync(d_cells, cells, n_inputs * 8, hipMemcpyHostToDevice, ctx->stream));
             SIPP_CHECK_HIP(ctx, hipMemcpyAsync(d_values, values, n_inputs * 8, hipMemcpyHostToDevice, ctx->stream));
-            const size_t want = (n_inputs + 255) / 256;
-            const dim3 grid((unsigned)(want < 4096 ? want : 4096));
-            hipLaunchKernelGGL(circuit_scatter_inputs_kernel, grid, dim3(256), 0, ctx->stream, cd->d_wires, d_cells, d_values, n_inputs);
-            hipLaunchKernelGGL(circuit_check_inputs_kernel, grid, dim3(256), 0, ctx->stream, cd->d_wires, d_cells, d_values, n_inputs, d_conflict);
-            SIPP_CHECK_HIP(ctx, hipGetLastError());
-            unsigned int conflict = 0;
-            SIPP_CHECK_HIP(ctx, hipMemcpyAsync(&conflict, d_conflict, sizeof conflict, hipMemcpyDeviceToHost, ctx->stream));
-            SIPP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            if (conflict) return sipp_fail(ctx, SIPP_E_BADARG, "circuit prove inputs: one cell given two different values");
         }
+        SIPP_TRY(stage_inputs(cd, d_cells, nullptr, d_values, n_inputs, reinterpret_cast<unsigned int*>(d_pairs + 2 * n_inputs),
+                              "circuit prove inputs: one cell given two different values"));
     }
     return prove_uploaded(cd, public_inputs, n_public_inputs, proof_out, proof_cap, proof_len);
 }
@@ -341,30 +347,17 @@ extern "C" int sipp_circuit_prove_words(sipp_circuit_data* cd, const uint64_t* w
     if (!cd->has_map) return sipp_fail(ctx, SIPP_E_BADARG, "circuit prove words: no input map set (sipp_circuit_set_input_map)");
     if (n_words != cd->map_words || n_extra != cd->map_extra)
         return sipp_fail(ctx, SIPP_E_BADARG, "circuit prove words: n_words / n_extra differ from the input map's");
-    const size_t total = (size_t)cd->circ.num_wires << cd->log_n, n = cd->map_n;
+    const size_t n = cd->map_n;
     SIPP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
     {
         // as in sipp_circuit_prove_inputs: the staging goes back before witness generation, behind the wait for the flag
         ArenaScope scope(ctx);
         uint64_t* d_staged = arena_alloc_t<uint64_t>(ctx, n_words + n_extra + 1);        // words, extra, the flag's word
         if (!d_staged) return SIPP_E_NOMEM;
-        unsigned int* d_conflict = reinterpret_cast<unsigned int*>(d_staged + n_words + n_extra);
-        SIPP_CHECK_HIP(ctx, hipMemsetAsync(cd->d_wires, 0, total * 8, ctx->stream));
-        if (n) {
-            SIPP_CHECK_HIP(ctx, hipMemsetAsync(d_conflict, 0, 8, ctx->stream));
-            if (n_words) SIPP_CHECK_HIP(ctx, hipMemcpyAsync(d_staged, words, n_words * 8, hipMemcpyHostToDevice, ctx->stream));
-            if (n_extra) SIPP_CHECK_HIP(ctx, hipMemcpyAsync(d_staged + n_words, extra, n_extra * 8, hipMemcpyHostToDevice, ctx->stream));
-            const uint64_t *d_cells = cd->d_map, *d_sources = cd->d_map + n;
-            const size_t want = (n + 255) / 256;
-            const dim3 grid((unsigned)(want < 4096 ? want : 4096));
-            hipLaunchKernelGGL(circuit_scatter_words_kernel, grid, dim3(256), 0, ctx->stream, cd->d_wires, d_cells, d_sources, d_staged, n);
-            hipLaunchKernelGGL(circuit_check_words_kernel, grid, dim3(256), 0, ctx->stream, cd->d_wires, d_cells, d_sources, d_staged, n, d_conflict);
-            SIPP_CHECK_HIP(ctx, hipGetLastError());
-            unsigned int conflict = 0;
-            SIPP_CHECK_HIP(ctx, hipMemcpyAsync(&conflict, d_conflict, sizeof conflict, hipMemcpyDeviceToHost, ctx->stream));
-            SIPP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            if (conflict) return sipp_fail(ctx, SIPP_E_BADARG, "circuit prove words: one cell mapped to two different values");
-        }
+        if (n && n_words) SIPP_CHECK_HIP(ctx, hipMemcpyAsync(d_staged, words, n_words * 8, hipMemcpyHostToDevice, ctx->stream));
+        if (n && n_extra) SIPP_CHECK_HIP(ctx, hipMemcpyAsync(d_staged + n_words, extra, n_extra * 8, hipMemcpyHostToDevice, ctx->stream));
+        SIPP_TRY(stage_inputs(cd, cd->d_map, cd->d_map + n, d_staged, n, reinterpret_cast<unsigned int*>(d_staged + n_words + n_extra),
+                              "circuit prove words: one cell mapped to two different values"));
     }
     return prove_uploaded(cd, public_inputs, n_public_inputs, proof_out, proof_cap, proof_len);
 }

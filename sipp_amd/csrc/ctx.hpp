@@ -20,6 +20,7 @@
 
 #include "../../include/sipp_hip.h"
 #include "gl.hpp"
+#include "plonk_desc.hpp"
 
 // one-shot host-side gate between the proofs of one SIPP instance (sipp_instance_prove): the shortest proof starts once
 // the longest has its trace filled, so that the long proof's latency-bound first phase is not crowded out
@@ -258,17 +259,22 @@ int sipp_k_merkle_levels(sipp_ctx* ctx, uint64_t* d_tree, uint32_t log_leaves, u
 int sipp_k_poseidon_permute(sipp_ctx* ctx, uint64_t* d_states, size_t n);
 void sipp_witness_graph_release(sipp_ctx* ctx);   // witness.hip
 int sipp_plonk_circuit_check(sipp_ctx* ctx, const sipp_plonk_circuit* c, const sipp_plonk_params* p);   // plonk.hip
-// lookup.hip -- a lookup description is the eight words of include/sipp_hip.h.  _check: its refusals (an empty one passes);
-// _index_host: the sorted index of the table's distinct pairs (kx | ky | cell | kt, a quarter of the vector each), built once per circuit;
-// _multiplicities_indexed: sipp_plonk_lookup_multiplicities over an index the caller keeps on the device; _quotient_terms: adds
-// Z_H^-1 sum_k alpha^(terms_in_front + k) term_k over the quotient coset into d_qv [C][N D] (leaf order, in front of the coset iNTT).
-int sipp_lookup_check(sipp_ctx* ctx, const uint32_t* lookup, uint32_t num_wires, uint32_t num_constants, uint32_t num_selectors);
-int sipp_lookup_index_host(sipp_ctx* ctx, const uint64_t* d_constants, uint32_t log_n, const uint32_t* lookup, std::vector<uint64_t>* out);
-int sipp_lookup_multiplicities_indexed(sipp_ctx* ctx, uint64_t* d_wires, const uint64_t* d_constants, uint32_t log_n, const uint32_t* lookup,
+// lookup.hip -- a lookup description is the eight words of include/sipp_hip.h, read ONCE into plonk_desc::Lookup.  _check: that reading
+// and its refusals (an empty one passes); _index_host: the sorted index of the table's distinct pairs (kx | ky | cell | kt, a quarter of
+// the vector each), built once per circuit; _multiplicities_indexed: sipp_plonk_lookup_multiplicities over an index the caller keeps on
+// the device; _quotient_terms: adds Z_H^-1 sum_k alpha^(terms_in_front + k) term_k over the quotient coset into d_qv [C][N D] (leaf
+// order, in front of the coset iNTT; log_d = log2(max_degree), the caller has validated the description and the parameters).
+int sipp_lookup_check(sipp_ctx* ctx, const uint32_t* lookup, uint32_t num_wires, uint32_t num_constants, uint32_t num_selectors,
+                      plonk_desc::Lookup* out);
+int sipp_lookup_index_host(sipp_ctx* ctx, const uint64_t* d_constants, uint32_t log_n, const plonk_desc::Lookup& l, std::vector<uint64_t>* out);
+int sipp_lookup_multiplicities_indexed(sipp_ctx* ctx, uint64_t* d_wires, const uint64_t* d_constants, uint32_t log_n, const plonk_desc::Lookup& l,
                                        const uint64_t* d_index, uint32_t n_index);
+// _sums: sipp_plonk_lookup_sums behind its checks, for a non-empty description the caller has validated
+int sipp_lookup_sums(sipp_ctx* ctx, const uint64_t* d_wires, const uint64_t* d_constants, uint32_t log_n, const sipp_plonk_params* p,
+                     const plonk_desc::Lookup& l, const uint64_t* etas, const uint64_t* thetas, uint64_t* d_out);
 int sipp_lookup_quotient_terms(sipp_ctx* ctx, const uint64_t* d_wires_lde, const uint64_t* d_consts_lde, const uint64_t* d_sums_lde, uint32_t log_n,
-                               uint32_t rate_bits, const sipp_plonk_params* p, const uint32_t* lookup, const uint64_t* etas, const uint64_t* thetas,
-                               const uint64_t* alphas, uint64_t terms_in_front, uint64_t* d_qv);
+                               uint32_t rate_bits, uint32_t log_d, const sipp_plonk_params* p, const plonk_desc::Lookup& l, const uint64_t* etas,
+                               const uint64_t* thetas, const uint64_t* alphas, uint64_t terms_in_front, uint64_t* d_qv);
 
 // ---- AIR layer (trace.hip / quotient.hip / stark.hip) -----------------------------------------
 #include "air_tables.h"

@@ -21,36 +21,27 @@
 
 namespace {
 
-constexpr uint32_t MAX_SLOTS = 128, MAX_CH = 8, MAX_GROUPS = 128;   // groups: ceil(128 / 2) looking + ceil(128 / 2) table
+using plonk_desc::Lookup;
+using plonk_desc::lookup_of;
+using plonk_desc::MAX_CH;
+constexpr uint32_t MAX_GROUPS = 128;   // groups: ceil(128 / 2) looking + ceil(128 / 2) table
 
-struct Lookup {
-    uint32_t q_look, look_wire0, n_look, q_tab, tab_const0, tab_mult0, n_tab, tag_const0;
-    bool empty() const { return n_look == 0 && n_tab == 0; }
-    bool tagged() const { return tag_const0 != 0; }
-};
-Lookup lookup_of(const uint32_t* w) { return Lookup{w[0], w[1], w[2], w[3], w[4], w[5], w[6], w[7]}; }
-
-// the refusals of include/sipp_hip.h, in its order: sizes the build does not serve, then a description that does not fit the circuit
+// plonk_desc::lookup_check's reasons as the refusals of include/sipp_hip.h
 int lookup_check(sipp_ctx* ctx, const uint32_t* w, uint32_t num_wires, uint32_t num_constants, uint32_t num_selectors, Lookup* out) {
     if (!w) return sipp_fail(ctx, SIPP_E_BADARG, "lookup: no description");
-    const Lookup l = lookup_of(w);
-    *out = l;
-    if (l.n_look > MAX_SLOTS || l.n_tab > MAX_SLOTS) return sipp_fail(ctx, SIPP_E_UNSUPPORTED, "lookup: at most 128 looking slots and 128 table slots a row");
-    if (l.empty() && l.tagged()) return sipp_fail(ctx, SIPP_E_BADARG, "lookup: an empty description names no tag columns");
-    if (l.empty()) return SIPP_OK;
-    if (l.n_look == 0 || l.n_tab == 0) return sipp_fail(ctx, SIPP_E_BADARG, "lookup: looking slots without table slots, or the reverse");
-    if (num_wires > 4096 || num_constants > 1024 || num_selectors > num_constants)
-        return sipp_fail(ctx, SIPP_E_BADARG, "lookup: malformed circuit sizes");
-    // (every sum below stays far inside 32 bits: the counts are <= 128, the columns are checked first)
-    if (l.q_look >= num_constants || l.q_tab >= num_constants || l.look_wire0 >= num_wires || l.look_wire0 + 2 * l.n_look > num_wires ||
-        l.tab_const0 >= num_constants || l.tab_const0 + 2 * l.n_tab > num_constants || l.tab_mult0 >= num_wires ||
-        l.tab_mult0 + l.n_tab > num_wires)
-        return sipp_fail(ctx, SIPP_E_BADARG, "lookup: the description names a column outside the circuit");
-    if (l.q_look < num_selectors || l.q_tab < num_selectors)
-        return sipp_fail(ctx, SIPP_E_BADARG, "lookup: q_look and q_tab are constant columns behind the selector columns");
-    if (l.tagged() && (l.tag_const0 < num_selectors || (uint64_t)l.tag_const0 + 1 >= num_constants))
-        return sipp_fail(ctx, SIPP_E_BADARG, "lookup: tag_const0 names two constant columns behind the selector columns");
-    return SIPP_OK;
+    *out = lookup_of(w);
+    using R = plonk_desc::LookupReason;
+    switch (plonk_desc::lookup_check(*out, num_wires, num_constants, num_selectors)) {
+    case R::ok: return SIPP_OK;
+    case R::too_many_slots: return sipp_fail(ctx, SIPP_E_UNSUPPORTED, "lookup: at most 128 looking slots and 128 table slots a row");
+    case R::empty_with_tag: return sipp_fail(ctx, SIPP_E_BADARG, "lookup: an empty description names no tag columns");
+    case R::one_sided: return sipp_fail(ctx, SIPP_E_BADARG, "lookup: looking slots without table slots, or the reverse");
+    case R::circuit_sizes: return sipp_fail(ctx, SIPP_E_BADARG, "lookup: malformed circuit sizes");
+    case R::column_outside: return sipp_fail(ctx, SIPP_E_BADARG, "lookup: the description names a column outside the circuit");
+    case R::marker_is_selector: return sipp_fail(ctx, SIPP_E_BADARG, "lookup: q_look and q_tab are constant columns behind the selector columns");
+    case R::tag_columns: return sipp_fail(ctx, SIPP_E_BADARG, "lookup: tag_const0 names two constant columns behind the selector columns");
+    }
+    return SIPP_E_BADARG;
 }
 
 // ---- multiplicities ------------------------------------------------------------------------------------------------------------------
@@ -235,30 +226,6 @@ __global__ void __launch_bounds__(256) lookup_group_kernel(SumArgs a) {
     a.tot[(size_t)c * n + i] = t;
 }
 
-// exclusive prefix sum over the rows: one block per challenge, every thread owns n / 1024 consecutive rows (plonk_scan_kernel's shape)
-__global__ void __launch_bounds__(1024) lookup_scan_kernel(const uint64_t* tot, uint64_t* s, uint32_t log_n) {
-    __shared__ uint64_t part[1024];
-    const uint32_t n = 1u << log_n, c = blockIdx.x, T = blockDim.x;
-    const uint32_t per = (n + T - 1) / T, lo = min(threadIdx.x * per, n), hi = min(lo + per, n);
-    const uint64_t* t = tot + (size_t)c * n;
-    uint64_t* z = s + (size_t)c * n;
-    uint64_t acc = 0;
-    for (uint32_t i = lo; i < hi; i++) acc = gl::add(acc, t[i]);
-    part[threadIdx.x] = acc;
-    __syncthreads();
-    for (uint32_t d = 1; d < T; d <<= 1) {          // Hillis-Steele inclusive scan of the 1024 partial sums
-        const uint64_t v = threadIdx.x >= d ? part[threadIdx.x - d] : 0;
-        __syncthreads();
-        part[threadIdx.x] = gl::add(part[threadIdx.x], v);
-        __syncthreads();
-    }
-    acc = threadIdx.x ? part[threadIdx.x - 1] : 0;
-    for (uint32_t i = lo; i < hi; i++) {
-        z[i] = acc;                                   // S(w^i) = the sum of the rows before i; S(1) = 0
-        acc = gl::add(acc, t[i]);
-    }
-}
-
 // U_j = S + the first j + 1 group sums, j < J - 1 (the last group closes onto S(g x))
 __global__ void __launch_bounds__(256) lookup_u_kernel(const uint64_t* grp, uint64_t* out, uint32_t log_n, uint32_t J, uint32_t C) {
     const uint32_t n = 1u << log_n, i = blockIdx.x * blockDim.x + threadIdx.x, c = blockIdx.y;
@@ -270,23 +237,23 @@ __global__ void __launch_bounds__(256) lookup_u_kernel(const uint64_t* grp, uint
     }
 }
 
-uint32_t groups(uint32_t slots, uint32_t D) { return (slots + D - 1) / D; }
-
-// the chunk size: sipp_plonk_params' own range
+// the chunk size and the challenges: sipp_plonk_params' own range, without the permutation argument's needs (no routed wire, no chunk cap)
 int params_check(sipp_ctx* ctx, const sipp_plonk_params* p, uint32_t log_n) {
-    if (!p || p->num_challenges == 0 || log_n < 1 || log_n > 24) return sipp_fail(ctx, SIPP_E_BADARG, "lookup: bad parameters");
-    if (p->max_degree < 2 || p->max_degree > 64 || (p->max_degree & (p->max_degree - 1)) || p->num_challenges > MAX_CH)
-        return sipp_fail(ctx, SIPP_E_UNSUPPORTED, "lookup: the chunk size must be a power of two in 2 .. 64, with at most 8 challenges");
-    return SIPP_OK;
+    uint32_t log_d, m;
+    switch (plonk_desc::params_check(p, log_n, 0, &log_d, &m)) {
+    case plonk_desc::Params::ok: return SIPP_OK;
+    case plonk_desc::Params::bad_argument: return sipp_fail(ctx, SIPP_E_BADARG, "lookup: bad parameters");
+    default: return sipp_fail(ctx, SIPP_E_UNSUPPORTED, "lookup: the chunk size must be a power of two in 2 .. 64, with at most 8 challenges");
+    }
 }
 
 }  // namespace
 
 uint32_t sipp_plonk_lookup_num_columns(const sipp_plonk_params* p, const uint32_t* lookup) {
     if (!p || !lookup || params_check(nullptr, p, 1) != SIPP_OK) return 0;
-    const uint32_t n_look = lookup[2], n_tab = lookup[6];
-    if (n_look == 0 || n_tab == 0 || n_look > MAX_SLOTS || n_tab > MAX_SLOTS) return 0;
-    return p->num_challenges * (groups(n_look, p->max_degree) + groups(n_tab, p->max_degree));
+    const Lookup l = lookup_of(lookup);
+    if (l.n_look == 0 || l.n_tab == 0 || l.n_look > plonk_desc::MAX_SLOTS || l.n_tab > plonk_desc::MAX_SLOTS) return 0;
+    return l.columns(p->max_degree, p->num_challenges);
 }
 
 int sipp_plonk_lookup_multiplicities(sipp_ctx* ctx, uint64_t* d_wires, const uint64_t* d_constants, uint32_t log_n, uint32_t num_wires,
@@ -315,13 +282,19 @@ int sipp_plonk_lookup_sums(sipp_ctx* ctx, const uint64_t* d_wires, const uint64_
     SIPP_TRY(lookup_check(ctx, lookup, num_wires, num_constants, num_selectors, &l));
     if (l.empty()) return SIPP_OK;                   // no columns
     if (!d_out) return sipp_fail(ctx, SIPP_E_BADARG, "lookup: bad parameters");
+    return sipp_lookup_sums(ctx, d_wires, d_constants, log_n, p, l, etas, thetas, d_out);
+}
+
+// (a non-empty description the caller has validated against the circuit, parameters in params_check's range)
+int sipp_lookup_sums(sipp_ctx* ctx, const uint64_t* d_wires, const uint64_t* d_constants, uint32_t log_n, const sipp_plonk_params* p, const Lookup& l,
+                     const uint64_t* etas, const uint64_t* thetas, uint64_t* d_out) {
     SIPP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
     ArenaScope scope(ctx, true);
     const size_t n = (size_t)1 << log_n;
     const uint32_t C = p->num_challenges;
     SumArgs a{};
     a.wires = d_wires; a.consts = d_constants; a.log_n = log_n; a.D = p->max_degree; a.C = C; a.l = l;
-    a.Jl = groups(l.n_look, a.D); a.Jt = groups(l.n_tab, a.D);
+    a.Jl = l.Jl(a.D); a.Jt = l.Jt(a.D);
     const uint32_t J = a.Jl + a.Jt;
     for (uint32_t c = 0; c < C; c++) { a.eta[c] = gl::canon(etas[c]); a.theta[c] = gl::canon(thetas[c]); }
     a.grp = arena_alloc_t<uint64_t>(ctx, (size_t)C * J * n);
@@ -333,7 +306,7 @@ int sipp_plonk_lookup_sums(sipp_ctx* ctx, const uint64_t* d_wires, const uint64_
         ProfScope ps(ctx, "lookup_sums");
         hipLaunchKernelGGL(l.tagged() ? lookup_group_kernel<true> : lookup_group_kernel<false>, dim3((unsigned)((n + 255) / 256), C), dim3(256), 0,
                            ctx->stream, a);
-        hipLaunchKernelGGL(lookup_scan_kernel, dim3(C), dim3(1024), 0, ctx->stream, a.tot, d_out, log_n);
+        hipLaunchKernelGGL(sipp_scan_kernel<ScanSum>, dim3(C), dim3(1024), 0, ctx->stream, a.tot, d_out, log_n);
         hipLaunchKernelGGL(lookup_u_kernel, dim3((unsigned)((n + 255) / 256), C), dim3(256), 0, ctx->stream, a.grp, d_out, log_n, J, C);
     }
     SIPP_CHECK_HIP(ctx, hipGetLastError());
@@ -428,49 +401,36 @@ __global__ void __launch_bounds__(256) lookup_quotient_kernel(LqArgs a) {
 }  // namespace
 
 // ---- what plonk.hip and circuit_data.hip call (ctx.hpp) ------------------------------------------------------------------------------
-int sipp_lookup_check(sipp_ctx* ctx, const uint32_t* lookup, uint32_t num_wires, uint32_t num_constants, uint32_t num_selectors) {
-    Lookup l;
-    return lookup_check(ctx, lookup, num_wires, num_constants, num_selectors, &l);
+int sipp_lookup_check(sipp_ctx* ctx, const uint32_t* lookup, uint32_t num_wires, uint32_t num_constants, uint32_t num_selectors, Lookup* out) {
+    return lookup_check(ctx, lookup, num_wires, num_constants, num_selectors, out);
 }
 
-int sipp_lookup_index_host(sipp_ctx* ctx, const uint64_t* d_constants, uint32_t log_n, const uint32_t* lookup, std::vector<uint64_t>* out) {
-    const Lookup l = lookup_of(lookup);
+int sipp_lookup_index_host(sipp_ctx* ctx, const uint64_t* d_constants, uint32_t log_n, const Lookup& l, std::vector<uint64_t>* out) {
     return index_host(ctx, d_constants, log_n, l, out);
 }
 
-int sipp_lookup_multiplicities_indexed(sipp_ctx* ctx, uint64_t* d_wires, const uint64_t* d_constants, uint32_t log_n, const uint32_t* lookup,
+int sipp_lookup_multiplicities_indexed(sipp_ctx* ctx, uint64_t* d_wires, const uint64_t* d_constants, uint32_t log_n, const Lookup& l,
                                        const uint64_t* d_index, uint32_t n_index) {
-    const Lookup l = lookup_of(lookup);
     return multiplicities_indexed(ctx, d_wires, d_constants, log_n, l, d_index, n_index);
 }
 
-// (the caller has validated the description against the circuit and the parameters; 2^rate_bits >= max_degree)
+// (the caller has validated the description against the circuit and the parameters; log_d = log2(max_degree) <= rate_bits)
 int sipp_lookup_quotient_terms(sipp_ctx* ctx, const uint64_t* d_wires_lde, const uint64_t* d_consts_lde, const uint64_t* d_sums_lde, uint32_t log_n,
-                               uint32_t rate_bits, const sipp_plonk_params* p, const uint32_t* lookup, const uint64_t* etas, const uint64_t* thetas,
-                               const uint64_t* alphas, uint64_t terms_in_front, uint64_t* d_qv) {
+                               uint32_t rate_bits, uint32_t log_d, const sipp_plonk_params* p, const Lookup& l, const uint64_t* etas,
+                               const uint64_t* thetas, const uint64_t* alphas, uint64_t terms_in_front, uint64_t* d_qv) {
     const size_t n = (size_t)1 << log_n;
-    uint32_t log_d = 0;
-    while ((1u << log_d) < p->max_degree) log_d++;
     LqArgs a{};
     a.wl = d_wires_lde; a.cl = d_consts_lde; a.sl = d_sums_lde; a.stride = n << rate_bits;
     a.log_n = log_n; a.rate_bits = rate_bits; a.log_d = log_d; a.D = p->max_degree; a.C = p->num_challenges;
-    a.l = lookup_of(lookup);
-    a.Jl = groups(a.l.n_look, a.D); a.Jt = groups(a.l.n_tab, a.D);
+    a.l = l;
+    a.Jl = l.Jl(a.D); a.Jt = l.Jt(a.D);
     for (uint32_t c = 0; c < a.C; c++) {
         a.eta[c] = gl::canon(etas[c]); a.theta[c] = gl::canon(thetas[c]); a.alpha[c] = gl::canon(alphas[c]);
         a.apow0[c] = gl::pow(a.alpha[c], terms_in_front);
     }
     a.w_nd = gl::root_of_unity(log_n + log_d);
     a.n_field = (uint64_t)n;
-    {   // x^n = 7^n w_D^(i mod D) on the coset, as in plonk.hip
-        const uint64_t g_n = gl::pow(gl::GEN, (uint64_t)n), w_d = gl::root_of_unity(log_d);
-        uint64_t f = g_n;
-        for (uint32_t d = 0; d < p->max_degree; d++) {
-            a.zh[d] = gl::sub(f, 1);
-            a.zh_inv[d] = gl::inv(a.zh[d]);
-            f = gl::mul(f, w_d);
-        }
-    }
+    sipp_coset_zh(log_n, log_d, a.zh, a.zh_inv);
     a.qv = d_qv;
     const size_t nd = n << log_d;
     {

@@ -20,7 +20,9 @@
 
 namespace {
 
-constexpr uint32_t MAX_CHUNKS = 32, MAX_CH = 8;
+using plonk_desc::Lookup;
+using plonk_desc::MAX_CH;
+using plonk_desc::MAX_CHUNKS;
 
 struct ZsArgs {
     const uint64_t* wires;    // [R][n]
@@ -67,30 +69,6 @@ __global__ void __launch_bounds__(256) plonk_chunk_kernel(ZsArgs a) {
         t = gl::mul(t, qv);
     }
     a.tot[(size_t)c * n + i] = t;
-}
-
-// exclusive prefix product over the rows: one block per challenge, every thread owns n / 1024 consecutive rows
-__global__ void __launch_bounds__(1024) plonk_scan_kernel(const uint64_t* tot, uint64_t* zs, uint32_t log_n) {
-    __shared__ uint64_t part[1024];
-    const uint32_t n = 1u << log_n, c = blockIdx.x, T = blockDim.x;
-    const uint32_t per = (n + T - 1) / T, lo = threadIdx.x * per, hi = min(lo + per, n);
-    const uint64_t* t = tot + (size_t)c * n;
-    uint64_t* z = zs + (size_t)c * n;
-    uint64_t acc = 1;
-    for (uint32_t i = lo; i < hi; i++) acc = gl::mul(acc, t[i]);
-    part[threadIdx.x] = acc;
-    __syncthreads();
-    for (uint32_t d = 1; d < T; d <<= 1) {          // Hillis-Steele inclusive scan of the 1024 partial products
-        const uint64_t v = threadIdx.x >= d ? part[threadIdx.x - d] : 1;
-        __syncthreads();
-        part[threadIdx.x] = gl::mul(part[threadIdx.x], v);
-        __syncthreads();
-    }
-    acc = threadIdx.x ? part[threadIdx.x - 1] : 1;
-    for (uint32_t i = lo; i < hi; i++) {
-        z[i] = acc;                                   // Z(w^i) = product of the rows before i; Z(1) = 1
-        acc = gl::mul(acc, t[i]);
-    }
 }
 
 __global__ void __launch_bounds__(256) plonk_pp_kernel(const uint64_t* chunk, uint64_t* out, uint32_t log_n, uint32_t m, uint32_t C) {
@@ -243,20 +221,16 @@ __global__ void __launch_bounds__(256) plonk_quotient_kernel(QuotArgs a) {
     for (uint32_t c = 0; c < C; c++) a.qv[(size_t)c * nd + pos] = gl::mul(acc[c], zhi);
 }
 
+// plonk_desc::params_check for the permutation argument (routed wires, at most 32 chunks of them) as this file's refusals
 int check(sipp_ctx* ctx, const sipp_plonk_params* p, uint32_t log_n, uint32_t* log_d, uint32_t* m) {
-    if (!p || p->num_routed_wires == 0 || p->num_challenges == 0 || log_n < 1 || log_n > 24) return sipp_fail(ctx, SIPP_E_BADARG, "plonk: bad parameters");
-    if (p->max_degree < 2 || p->max_degree > 64)      // before the loop below: 1u << 32 is undefined
+    switch (plonk_desc::params_check(p, log_n, plonk_desc::ROUTED | plonk_desc::CHUNK_CAP, log_d, m)) {
+    case plonk_desc::Params::ok: return SIPP_OK;
+    case plonk_desc::Params::bad_argument: return sipp_fail(ctx, SIPP_E_BADARG, "plonk: bad parameters");
+    case plonk_desc::Params::chunk_size:
         return sipp_fail(ctx, SIPP_E_UNSUPPORTED, "plonk: the chunk size (quotient degree factor) must be a power of two in 2 .. 64");
-    uint32_t ld = 0;
-    while ((1u << ld) < p->max_degree) ld++;
-    if ((1u << ld) != p->max_degree)
-        return sipp_fail(ctx, SIPP_E_UNSUPPORTED, "plonk: the chunk size (quotient degree factor) must be a power of two in 2 .. 64");
-    const uint32_t chunks = (p->num_routed_wires + p->max_degree - 1) / p->max_degree;
-    if (chunks > MAX_CHUNKS || p->num_challenges > MAX_CH)
-        return sipp_fail(ctx, SIPP_E_UNSUPPORTED, "plonk: at most 32 chunks of routed wires and 8 challenges");
-    *log_d = ld;
-    *m = chunks;
-    return SIPP_OK;
+    case plonk_desc::Params::counts: return sipp_fail(ctx, SIPP_E_UNSUPPORTED, "plonk: at most 32 chunks of routed wires and 8 challenges");
+    }
+    return SIPP_E_BADARG;
 }
 
 // beta_c 7^j on the device (released with the caller's arena scope)
@@ -303,7 +277,7 @@ int sipp_plonk_zs_partial_products(sipp_ctx* ctx, const uint64_t* d_wires, const
     {
         ProfScope ps(ctx, "plonk_zs");
         hipLaunchKernelGGL(plonk_chunk_kernel, dim3((unsigned)((n + 255) / 256), C), dim3(256), 0, ctx->stream, a);
-        hipLaunchKernelGGL(plonk_scan_kernel, dim3(C), dim3(1024), 0, ctx->stream, a.tot, d_out, log_n);
+        hipLaunchKernelGGL(sipp_scan_kernel<ScanProduct>, dim3(C), dim3(1024), 0, ctx->stream, a.tot, d_out, log_n);
         hipLaunchKernelGGL(plonk_pp_kernel, dim3((unsigned)((n + 255) / 256), C), dim3(256), 0, ctx->stream, a.chunk, d_out, log_n, m, C);
     }
     SIPP_CHECK_HIP(ctx, hipGetLastError());
@@ -325,7 +299,7 @@ struct GateSet {
 };
 // the lookup argument's terms behind the gate constraints (lookup.hip): the description, its challenges, the S / U columns' LDE
 struct LookupSet {
-    const uint32_t* words;
+    const Lookup* l;
     const uint64_t *etas, *thetas;
     const uint64_t* d_sums_lde;
 };
@@ -417,37 +391,20 @@ uint32_t num_gate_constraints(const sipp_plonk_circuit* c) {
     return m;
 }
 
-// every operand in range, every program inside program_words: an index out of range would be a read outside the LDE buffers
+// plonk_desc's walk over the gate programs, then the prover's size caps, as this file's refusals
 int circuit_check(sipp_ctx* ctx, const sipp_plonk_circuit* c, const sipp_plonk_params* p) {
-    if (!c || !p || c->num_wires < p->num_routed_wires || c->num_wires > 4096 || c->num_selectors == 0 || c->num_selectors > c->num_constants ||
-        c->num_constants > 1024 || c->num_gates == 0 || c->num_gates > 4096 || !c->gates || (!c->programs && c->program_words))
-        return sipp_fail(ctx, SIPP_E_BADARG, "plonk: malformed circuit description");
-    for (uint32_t g = 0; g < c->num_gates; g++) {
-        const sipp_plonk_gate& ga = c->gates[g];
-        if (ga.selector_index >= c->num_selectors || ga.group_lo > ga.row || ga.row >= ga.group_hi || ga.group_hi > c->num_gates ||
-            ga.group_hi - ga.group_lo > 64 || ga.num_constraints > 4096)
-            return sipp_fail(ctx, SIPP_E_BADARG, "plonk: a gate's selector group is malformed");
-        size_t w = ga.prog_offset;
-        for (uint32_t j = 0; j < ga.num_constraints; j++) {
-            if (w >= c->program_words) return sipp_fail(ctx, SIPP_E_BADARG, "plonk: a gate program runs past program_words");
-            const int64_t nm = c->programs[w++];
-            if (nm < 0 || nm > 4096) return sipp_fail(ctx, SIPP_E_BADARG, "plonk: a gate program is malformed");
-            for (int64_t m = 0; m < nm; m++) {
-                if (w + 2 > c->program_words) return sipp_fail(ctx, SIPP_E_BADARG, "plonk: a gate program runs past program_words");
-                const int64_t nf = c->programs[w + 1];
-                w += 2;
-                if (nf < 0 || nf > 64 || w + 2 * (size_t)nf > c->program_words)
-                    return sipp_fail(ctx, SIPP_E_BADARG, "plonk: a gate program runs past program_words");
-                for (int64_t f = 0; f < nf; f++, w += 2) {
-                    const int64_t kind = c->programs[w], idx = c->programs[w + 1];
-                    if (kind < 0 || kind > 2 || idx < 0 || (kind == 0 && idx >= c->num_wires) || (kind == 1 && idx >= c->num_constants) ||
-                        (kind == 2 && idx >= 4))
-                        return sipp_fail(ctx, SIPP_E_BADARG, "plonk: a gate program names an operand out of range");
-                }
-            }
-        }
+    using R = plonk_desc::Circuit;
+    R r = plonk_desc::circuit_walk(c, p);
+    if (r == R::ok) r = plonk_desc::circuit_caps(*c);
+    switch (r) {
+    case R::ok: return SIPP_OK;
+    case R::description: return sipp_fail(ctx, SIPP_E_BADARG, "plonk: malformed circuit description");
+    case R::selector_group: return sipp_fail(ctx, SIPP_E_BADARG, "plonk: a gate's selector group is malformed");
+    case R::past_program_words: return sipp_fail(ctx, SIPP_E_BADARG, "plonk: a gate program runs past program_words");
+    case R::program: return sipp_fail(ctx, SIPP_E_BADARG, "plonk: a gate program is malformed");
+    case R::operand: return sipp_fail(ctx, SIPP_E_BADARG, "plonk: a gate program names an operand out of range");
     }
-    return SIPP_OK;
+    return SIPP_E_BADARG;
 }
 
 int quotient_chunks_impl(sipp_ctx* ctx, const uint64_t* d_wires_lde, const uint64_t* d_sigmas_lde, const uint64_t* d_zs_lde, uint32_t log_n,
@@ -469,15 +426,7 @@ int quotient_chunks_impl(sipp_ctx* ctx, const uint64_t* d_wires_lde, const uint6
     for (uint32_t c = 0; c < C; c++) { a.beta[c] = gl::canon(betas[c]); a.gamma[c] = gl::canon(gammas[c]); a.alpha[c] = gl::canon(alphas[c]); }
     a.w_nd = gl::root_of_unity(log_n + log_d);
     a.n_field = (uint64_t)n;
-    {   // x^n = 7^n w_D^(i mod D) on the coset
-        const uint64_t g_n = gl::pow(gl::GEN, (uint64_t)n), w_d = gl::root_of_unity(log_d);
-        uint64_t f = g_n;
-        for (uint32_t d = 0; d < p->max_degree; d++) {
-            a.zh[d] = gl::sub(f, 1);
-            a.zh_inv[d] = gl::inv(a.zh[d]);
-            f = gl::mul(f, w_d);
-        }
-    }
+    sipp_coset_zh(log_n, log_d, a.zh, a.zh_inv);
     a.bk = upload_bk(ctx, p, betas);
     if (!a.bk) return SIPP_E_NOMEM;
     a.qv = d_chunks;           // [C][n D]: values in leaf order, transformed in place
@@ -521,7 +470,7 @@ int quotient_chunks_impl(sipp_ctx* ctx, const uint64_t* d_wires_lde, const uint6
     }
     SIPP_CHECK_HIP(ctx, hipGetLastError());
     if (ls)      // the lookup terms follow the gate constraints in the one reduce_with_powers list: a kernel of its own adds them
-        SIPP_TRY(sipp_lookup_quotient_terms(ctx, d_wires_lde, gs->d_consts_lde, ls->d_sums_lde, log_n, rate_bits, p, ls->words, ls->etas, ls->thetas,
+        SIPP_TRY(sipp_lookup_quotient_terms(ctx, d_wires_lde, gs->d_consts_lde, ls->d_sums_lde, log_n, rate_bits, log_d, p, *ls->l, ls->etas, ls->thetas,
                                             alphas, (uint64_t)C + (uint64_t)C * m + num_gate_terms + num_gate_constraints(gs->c), d_chunks));
     // coset_ifft(7): leaf-order values -> natural coefficients; [C][n D] natural == [C D][n] chunks
     SIPP_TRY(sipp_ntt_dit(ctx, d_chunks, nd, log_n + log_d, C, true, NttDiag{gl::inv(gl::GEN), 0}));
@@ -551,7 +500,7 @@ struct PlonkExtra {
     const sipp_plonk_circuit* circ = nullptr;
     // a NON-EMPTY lookup description ("SIPPPLK4", with circ): the S / U columns behind the permutation's in the zs_partial_products
     // oracle, eta / theta drawn behind the gammas, the lookup terms behind the gate constraints
-    const uint32_t* lookup = nullptr;
+    const Lookup* lookup = nullptr;
 };
 int plonk_prove_impl(sipp_ctx* ctx, const uint64_t* d_wires, const uint64_t* d_sigmas, uint32_t log_n, const sipp_plonk_params* p,
                      const sipp_fri_params* fp, const uint64_t circuit_digest[4], const uint64_t public_inputs_hash[4], const PlonkExtra& ex,
@@ -565,9 +514,9 @@ struct PlonkLayout {
     sipp_poly_range at_zeta[4], at_gzeta[2];
     uint32_t n_gzeta;         // 1, or 2 with lookups: the S columns behind the Z columns
     size_t header_words;      // 8, 16 with the gates as data ("SIPPPLK3"), 24 with a lookup description ("SIPPPLK4")
-    PlonkLayout(const sipp_plonk_params* p, uint32_t m, const sipp_plonk_circuit* circ, const uint32_t* lookup = nullptr) {
+    PlonkLayout(const sipp_plonk_params* p, uint32_t m, const sipp_plonk_circuit* circ, const Lookup* lookup = nullptr) {
         const uint32_t R = p->num_routed_wires, C = p->num_challenges;
-        const uint32_t n_lk = lookup ? sipp_plonk_lookup_num_columns(p, lookup) : 0;
+        const uint32_t n_lk = lookup ? lookup->columns(p->max_degree, C) : 0;
         const uint32_t nc[4] = {(circ ? circ->num_constants : 0) + R, circ ? circ->num_wires : R, C * m + n_lk, C * p->max_degree};
         for (uint32_t o = 0; o < 4; o++) {
             ncols[o] = nc[o];
@@ -597,7 +546,7 @@ struct PlonkLayout {
 };
 // words of a whole proof; 0 when check() refuses the parameters or the FRI parameters do not fit
 size_t plonk_proof_words(uint32_t log_n, const sipp_plonk_params* p, const sipp_fri_params* fp, const sipp_plonk_circuit* circ,
-                         uint32_t n_public_inputs, const uint32_t* lookup = nullptr) {
+                         uint32_t n_public_inputs, const Lookup* lookup = nullptr) {
     uint32_t log_d, m;
     if (!fp || check(nullptr, p, log_n, &log_d, &m) != SIPP_OK) return 0;
     const PlonkLayout lay(p, m, circ, lookup);
@@ -688,7 +637,7 @@ int plonk_prove_impl(sipp_ctx* ctx, const uint64_t* d_wires, const uint64_t* d_s
         if (!zs) return SIPP_E_NOMEM;
         SIPP_TRY(sipp_plonk_zs_partial_products(ctx, d_wires, d_sigma_vals, log_n, p, betas, gammas, zs));
         if (ex.lookup)
-            SIPP_TRY(sipp_plonk_lookup_sums(ctx, d_wires, d_sigmas, log_n, Wn, K, ex.circ->num_selectors, p, ex.lookup, etas, thetas, zs + (size_t)nz * n));
+            SIPP_TRY(sipp_lookup_sums(ctx, d_wires, d_sigmas, log_n, p, *ex.lookup, etas, thetas, zs + (size_t)nz * n));
         SIPP_TRY(sipp_commit_batch_ex(ctx, zs, 0, co[2], lde[2], tree[2], ncols[2], log_n, fp->rate_bits, fp->cap_height, nullptr, 0, cap_of(2)));
     }
     ch.observe_many(cap_of(2), cap_n * 4);
@@ -717,7 +666,7 @@ int plonk_prove_impl(sipp_ctx* ctx, const uint64_t* d_wires, const uint64_t* d_s
     if (ex.lookup) {
         uint64_t h[24] = {0x344b4c5050504953ULL /* "SIPPPLK4" */, log_n, R, D, C, head + op_len + tail, Wn, K, ex.circ->num_selectors,
                           ex.circ->num_gates, num_gate_constraints(ex.circ), tail, 0, 0, 0, 0};
-        for (int q = 0; q < 8; q++) h[16 + q] = ex.lookup[q];
+        for (int q = 0; q < 8; q++) h[16 + q] = plonk_desc::lookup_word(*ex.lookup, q);
         memcpy(proof_out, h, sizeof h);
     } else if (ex.circ) {
         const uint64_t h[16] = {0x334b4c5050504953ULL /* "SIPPPLK3" */, log_n, R, D, C, head + op_len + tail, Wn, K, ex.circ->num_selectors,
@@ -741,22 +690,23 @@ size_t sipp_plonk_perm_proof_size(uint32_t log_n, const sipp_plonk_params* p, co
     return plonk_proof_words(log_n, p, fp, nullptr, 0);
 }
 
+namespace {
+// (the circuit's own bounds: circuit_check)
+bool sizes_ok(const sipp_plonk_circuit* c, const sipp_plonk_params* p) {
+    return c && p && c->num_wires >= p->num_routed_wires && plonk_desc::sizes_within_caps(c->num_wires, c->num_constants);
+}
+}  // namespace
+
 size_t sipp_plonk_gates_proof_size(uint32_t log_n, const sipp_plonk_params* p, const sipp_fri_params* fp, const sipp_plonk_circuit* c,
                                    uint32_t n_public_inputs) {
-    // (the circuit's own bounds: circuit_check)
-    if (!c || !p || c->num_wires < p->num_routed_wires || c->num_wires > 4096 || c->num_constants > 1024) return 0;
-    return plonk_proof_words(log_n, p, fp, c, n_public_inputs);
+    return sizes_ok(c, p) ? plonk_proof_words(log_n, p, fp, c, n_public_inputs) : 0;
 }
-
-namespace {
-bool lookup_empty(const uint32_t* lookup) { return !lookup || (lookup[2] == 0 && lookup[6] == 0); }
-}  // namespace
 
 size_t sipp_plonk_gates_lookup_proof_size(uint32_t log_n, const sipp_plonk_params* p, const sipp_fri_params* fp, const sipp_plonk_circuit* c,
                                           uint32_t n_public_inputs, const uint32_t* lookup) {
-    if (!c || !p || c->num_wires < p->num_routed_wires || c->num_wires > 4096 || c->num_constants > 1024) return 0;
-    if (sipp_lookup_check(nullptr, lookup, c->num_wires, c->num_constants, c->num_selectors) != SIPP_OK) return 0;
-    return plonk_proof_words(log_n, p, fp, c, n_public_inputs, lookup_empty(lookup) ? nullptr : lookup);
+    Lookup l;
+    if (!sizes_ok(c, p) || sipp_lookup_check(nullptr, lookup, c->num_wires, c->num_constants, c->num_selectors, &l) != SIPP_OK) return 0;
+    return plonk_proof_words(log_n, p, fp, c, n_public_inputs, l.empty() ? nullptr : &l);
 }
 
 int sipp_plonk_prove_gates(sipp_ctx* ctx, const uint64_t* d_wires, const uint64_t* d_constants_sigmas, const sipp_oracle* wires_oracle,
@@ -773,12 +723,12 @@ int sipp_plonk_prove_gates_lookup(sipp_ctx* ctx, const uint64_t* d_wires, const 
                                   const sipp_plonk_params* p, const sipp_fri_params* fp, const sipp_plonk_circuit* c,
                                   const uint64_t circuit_digest[4], const uint64_t* public_inputs, uint32_t n_public_inputs,
                                   const uint32_t* lookup, uint64_t* proof_out, size_t proof_cap, size_t* proof_len) {
-    if (!lookup) return SIPP_E_BADARG;
-    if (!ctx || !d_wires || !d_constants_sigmas || !fp || !p || !c || !circuit_digest || !proof_out || !proof_len ||
+    if (!ctx || !lookup || !d_wires || !d_constants_sigmas || !fp || !p || !c || !circuit_digest || !proof_out || !proof_len ||
         (n_public_inputs && !public_inputs) || (wires_oracle != nullptr) != (wires_cap != nullptr) || n_public_inputs > (1u << 24))
         return SIPP_E_BADARG;
     SIPP_TRY(circuit_check(ctx, c, p));
-    SIPP_TRY(sipp_lookup_check(ctx, lookup, c->num_wires, c->num_constants, c->num_selectors));
+    Lookup l;
+    SIPP_TRY(sipp_lookup_check(ctx, lookup, c->num_wires, c->num_constants, c->num_selectors, &l));
     if ((wires_oracle && (wires_oracle->n_polys != c->num_wires || wires_oracle->n_salt || !wires_oracle->d_coeffs || !wires_oracle->d_lde ||
                           !wires_oracle->d_tree)) ||
         (constants_sigmas_oracle &&
@@ -790,6 +740,6 @@ int sipp_plonk_prove_gates_lookup(sipp_ctx* ctx, const uint64_t* d_wires, const 
     PlonkExtra ex;
     ex.public_inputs = public_inputs; ex.n_public_inputs = n_public_inputs; ex.v2 = true;
     ex.sigmas_oracle = constants_sigmas_oracle; ex.wires_oracle = wires_oracle; ex.wires_cap = wires_cap; ex.circ = c;
-    ex.lookup = lookup_empty(lookup) ? nullptr : lookup;      // an empty description: "SIPPPLK3", word for word
+    ex.lookup = l.empty() ? nullptr : &l;      // an empty description: "SIPPPLK3", word for word
     return plonk_prove_impl(ctx, d_wires, d_constants_sigmas, log_n, p, fp, circuit_digest, pih, ex, proof_out, proof_cap, proof_len);
 }

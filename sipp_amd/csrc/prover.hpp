@@ -71,6 +71,52 @@ inline gl::E2 sipp_pow_limbs(gl::E2 base, size_t count, uint32_t* out) {
     }
     return x;
 }
+// Exclusive prefix scan over the rows of [C][n] under a monoid of the field: one block of 1024 threads per challenge, every thread owns
+// ceil(n / 1024) consecutive rows; out[i] = the combination of the rows before i, out[0] = the identity.  The outer prover's Z is the
+// product instantiation (plonk.hip), the lookup argument's S the sum (lookup.hip).
+struct ScanProduct {
+    static constexpr uint64_t identity = 1;
+    static __device__ uint64_t op(uint64_t a, uint64_t b) { return gl::mul(a, b); }
+};
+struct ScanSum {
+    static constexpr uint64_t identity = 0;
+    static __device__ uint64_t op(uint64_t a, uint64_t b) { return gl::add(a, b); }
+};
+template <typename Op>
+static __global__ void __launch_bounds__(1024) sipp_scan_kernel(const uint64_t* tot, uint64_t* out, uint32_t log_n) {
+    __shared__ uint64_t part[1024];
+    const uint32_t n = 1u << log_n, c = blockIdx.x, T = blockDim.x;
+    const uint32_t per = (n + T - 1) / T, lo = min(threadIdx.x * per, n), hi = min(lo + per, n);
+    const uint64_t* t = tot + (size_t)c * n;
+    uint64_t* z = out + (size_t)c * n;
+    uint64_t acc = Op::identity;
+    for (uint32_t i = lo; i < hi; i++) acc = Op::op(acc, t[i]);
+    part[threadIdx.x] = acc;
+    __syncthreads();
+    for (uint32_t d = 1; d < T; d <<= 1) {          // Hillis-Steele inclusive scan of the 1024 partial results
+        const uint64_t v = threadIdx.x >= d ? part[threadIdx.x - d] : Op::identity;
+        __syncthreads();
+        part[threadIdx.x] = Op::op(part[threadIdx.x], v);
+        __syncthreads();
+    }
+    acc = threadIdx.x ? part[threadIdx.x - 1] : Op::identity;
+    for (uint32_t i = lo; i < hi; i++) {
+        z[i] = acc;
+        acc = Op::op(acc, t[i]);
+    }
+}
+
+// Z_H on the outer prover's quotient coset 7 <w_(n D)>, D = 2^log_d <= 64: x^n = 7^n w_D^(i mod D), so Z_H(x) = x^n - 1 takes D values;
+// zh[d] and its inverse by coset index mod D (plonk.hip and lookup.hip hand them to their quotient kernels)
+inline void sipp_coset_zh(uint32_t log_n, uint32_t log_d, uint64_t zh[64], uint64_t zh_inv[64]) {
+    const uint64_t w_d = gl::root_of_unity(log_d);
+    uint64_t f = gl::pow(gl::GEN, (uint64_t)1 << log_n);
+    for (uint32_t d = 0; d < (1u << log_d); d++) {
+        zh[d] = gl::sub(f, 1);
+        zh_inv[d] = gl::inv(zh[d]);
+        f = gl::mul(f, w_d);
+    }
+}
 // natural-order radix-2 NTT on the host (the public-input polynomials, the value-periodic columns: sizes up to a few thousand):
 // out[i] = sum_j a[j] w^(i j), w a primitive 2^log_n-th root (inverse: w^-1 and the factor 1 / n)
 inline void sipp_host_ntt(uint64_t* a, uint32_t log_n, bool inverse) {

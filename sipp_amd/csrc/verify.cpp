@@ -23,6 +23,7 @@
 #include "air_tables.h"
 #include "gl.hpp"
 #include "host_challenger.hpp"
+#include "plonk_desc.hpp"
 
 const air_spec_t* sipp_air_get(int kind, uint32_t log_n);   // trace.hip: the AIR of an API kind at a trace length
 
@@ -956,68 +957,33 @@ int fri_openings_verify(const uint64_t* sec, size_t sec_len, const uint64_t* con
     return rb.pos == sec_len ? 0 : 140;
 }
 
-// a gate set handed over as data: operands in range, programs inside program_words (what sipp_plonk_prove_gates refuses too)
-bool circuit_ok(const sipp_plonk_circuit& c, const sipp_plonk_params& p) {
-    if (c.num_wires < p.num_routed_wires || c.num_selectors == 0 || c.num_selectors > c.num_constants || c.num_gates == 0 || !c.gates ||
-        (!c.programs && c.program_words))
-        return false;
-    for (uint32_t g = 0; g < c.num_gates; g++) {
-        const sipp_plonk_gate& ga = c.gates[g];
-        if (ga.selector_index >= c.num_selectors || ga.group_lo > ga.row || ga.row >= ga.group_hi || ga.group_hi > c.num_gates) return false;
-        size_t w = ga.prog_offset;
-        for (uint32_t j = 0; j < ga.num_constraints; j++) {
-            if (w >= c.program_words) return false;
-            const int64_t nm = c.programs[w++];
-            if (nm < 0 || nm > 4096) return false;
-            for (int64_t mo = 0; mo < nm; mo++) {
-                if (w + 2 > c.program_words) return false;
-                const int64_t nf = c.programs[w + 1];
-                w += 2;
-                if (nf < 0 || nf > 64 || w + 2 * (size_t)nf > c.program_words) return false;
-                for (int64_t f = 0; f < nf; f++, w += 2) {
-                    const int64_t kind = c.programs[w], idx = c.programs[w + 1];
-                    if (kind < 0 || kind > 2 || idx < 0 || (kind == 0 && idx >= c.num_wires) || (kind == 1 && idx >= c.num_constants) ||
-                        (kind == 2 && idx >= 4))
-                        return false;
-                }
-            }
-        }
-    }
-    return true;
-}
-
 // plonk/verifier.rs with the gate constraints evaluated at zeta from the OPENED constants and wires (gates as data: per gate a selector
 // filter and one polynomial per constraint), the permutation argument's Z(1) = 1 and partial-product terms, one reduce_with_powers per
 // challenge against the quotient chunks, then the opening proof
 // `lk`: the caller's NON-EMPTY lookup description (nullptr: none, the proof is "SIPPPLK3").  With one the proof is "SIPPPLK4": eta, theta
 // behind the gammas, the S / U columns behind the permutation's (S again at g zeta), the lookup terms behind the gate constraints.
-bool lookup_ok(const uint32_t* w, const sipp_plonk_circuit& c) {
-    // every bound before anything is sized by these words (the refusals of sipp_plonk_prove_gates_lookup)
-    if (w[2] == 0 || w[6] == 0 || w[2] > 128 || w[6] > 128 || c.num_wires > 4096 || c.num_constants > 1024) return false;
-    if (w[7] != 0 && (w[7] < c.num_selectors || (uint64_t)w[7] + 1 >= c.num_constants)) return false;      // the two tag columns
-    if (w[0] >= c.num_constants || w[3] >= c.num_constants || w[0] < c.num_selectors || w[3] < c.num_selectors) return false;
-    if (w[1] >= c.num_wires || w[1] + 2 * w[2] > c.num_wires || w[5] >= c.num_wires || w[5] + w[6] > c.num_wires) return false;
-    return w[4] < c.num_constants && w[4] + 2 * w[6] <= c.num_constants;
-}
-
+// The three descriptions are read by plonk_desc.hpp, as the prover reads them: the parameters (routed wires needed; no cap on the chunks,
+// and log_n is the proof's own word, stage 202 below), the gate set's structure (the prover's size caps are NOT the verifier's), and with
+// a lookup description its validator -- which does apply the caps on wires and constants, before anything is sized by these words.
 int plonk_verify(const uint64_t* proof, size_t len, const uint64_t* cs_cap, const sipp_plonk_params& p, const sipp_fri_params& fp,
-                 const sipp_plonk_circuit& c, const uint64_t digest[4], const uint32_t* lk) {
-    if (lk && !lookup_ok(lk, c)) return 201;
-    if (p.num_routed_wires == 0 || p.max_degree < 2 || p.max_degree > 64 || (p.max_degree & (p.max_degree - 1)) || p.num_challenges == 0 ||
-        p.num_challenges > 8 || !circuit_ok(c, p))
+                 const sipp_plonk_circuit& c, const uint64_t digest[4], const plonk_desc::Lookup* lk) {
+    uint32_t log_d, m;
+    if (plonk_desc::params_check(&p, 1, plonk_desc::ROUTED, &log_d, &m) != plonk_desc::Params::ok ||
+        plonk_desc::circuit_walk(&c, &p) != plonk_desc::Circuit::ok ||
+        (lk && (lk->empty() || plonk_desc::lookup_check(*lk, c.num_wires, c.num_constants, c.num_selectors) != plonk_desc::LookupReason::ok)))
         return 201;
-    const uint32_t R = p.num_routed_wires, D = p.max_degree, C = p.num_challenges, np = (R + D - 1) / D - 1, nz = C * (1 + np), m = np + 1;
+    const uint32_t R = p.num_routed_wires, D = p.max_degree, C = p.num_challenges, np = m - 1, nz = C * m;
     const uint32_t W = c.num_wires, K = c.num_constants;
     uint32_t ngc = 0;
     for (uint32_t g = 0; g < c.num_gates; g++) ngc = c.gates[g].num_constraints > ngc ? c.gates[g].num_constraints : ngc;
     if (fp.cap_height > 16) return 201;
     const size_t cap_n = (size_t)1 << fp.cap_height;
     const size_t hw = lk ? 24 : 16;
-    const uint32_t Jl = lk ? (lk[2] + D - 1) / D : 0, Jt = lk ? (lk[6] + D - 1) / D : 0, J = Jl + Jt, nlk = C * J, nzl = nz + nlk;
+    const uint32_t Jl = lk ? lk->Jl(D) : 0, Jt = lk ? lk->Jt(D) : 0, J = Jl + Jt, nzl = nz + C * J;
     if (lk) {      // the header's description is the caller's, word for word
         if (len < hw) return 201;
         for (int q = 0; q < 8; q++)
-            if (proof[16 + q] != lk[q]) return 201;
+            if (proof[16 + q] != plonk_desc::lookup_word(*lk, q)) return 201;
     }
     if (len < hw + 3 * cap_n * 4 || proof[0] != (lk ? PLONK_MAGIC4 : PLONK_MAGIC3) || proof[2] != R || proof[3] != D || proof[4] != C || proof[5] != len || proof[6] != W ||
         proof[7] != K || proof[8] != c.num_selectors || proof[9] != c.num_gates || proof[10] != ngc || (proof[12] | proof[13] | proof[14] | proof[15]))
@@ -1103,20 +1069,22 @@ int plonk_verify(const uint64_t* proof, size_t len, const uint64_t* cs_cap, cons
             // with U_(-1) = S(zeta), U_(J-1) = S(g zeta)
             for (uint32_t cc = 0; cc < C; cc++) terms.push_back(gl::mul(l0, ss[cc]));
             // several tables (word 7): a combination is x + eta y + eta^2 tag, the tag of the looking / the table row a constant column
-            const E2 ql = cv[lk[0]], qt = cv[lk[3]], tag_l = lk[7] ? cv[lk[7]] : e2(0), tag_t = lk[7] ? cv[lk[7] + 1] : e2(0);
+            const E2 ql = cv[lk->q_look], qt = cv[lk->q_tab], tag_l = lk->tagged() ? cv[lk->tag_const0] : e2(0),
+                     tag_t = lk->tagged() ? cv[lk->tag_const0 + 1] : e2(0);
             for (uint32_t cc = 0; cc < C; cc++) {
                 const uint64_t eta2 = gl::mul(etas[cc], etas[cc]);
                 E2 prev = ss[cc];
                 for (uint32_t j = 0; j < J; j++) {
                     const bool look = j < Jl;
-                    const uint32_t jj = look ? j : j - Jl, cnt = look ? lk[2] : lk[6];
+                    const uint32_t jj = look ? j : j - Jl, cnt = look ? lk->n_look : lk->n_tab;
                     E2 N = e2(0), Dn = e2(1);
                     for (uint32_t k = jj * D; k < (jj + 1) * D && k < cnt; k++) {
-                        const E2 vx = look ? wv[lk[1] + 2 * k] : cv[lk[4] + 2 * k], vy = look ? wv[lk[1] + 2 * k + 1] : cv[lk[4] + 2 * k + 1];
+                        const E2 vx = look ? wv[lk->look_wire0 + 2 * k] : cv[lk->tab_const0 + 2 * k],
+                                 vy = look ? wv[lk->look_wire0 + 2 * k + 1] : cv[lk->tab_const0 + 2 * k + 1];
                         E2 comb = gl::add(vx, gl::scale(vy, etas[cc]));
-                        if (lk[7]) comb = gl::add(comb, gl::scale(look ? tag_l : tag_t, eta2));
+                        if (lk->tagged()) comb = gl::add(comb, gl::scale(look ? tag_l : tag_t, eta2));
                         const E2 d = gl::sub(e2(thetas[cc]), comb);
-                        N = gl::add(gl::mul(N, d), look ? Dn : gl::mul(wv[lk[5] + k], Dn));
+                        N = gl::add(gl::mul(N, d), look ? Dn : gl::mul(wv[lk->tab_mult0 + k], Dn));
                         Dn = gl::mul(Dn, d);
                     }
                     const E2 next = j + 1 == J ? ss_next[cc] : us[cc * (J - 1) + j];
@@ -1184,10 +1152,10 @@ extern "C" int sipp_plonk_verify_gates_lookup(const uint64_t* proof, size_t len,
                                               const uint32_t* lookup, int* reason) {
     if (reason) *reason = 0;
     if (!proof || !constants_sigmas_cap || !p || !fp || !c || !circuit_digest || !lookup) return SIPP_E_BADARG;
-    const bool empty = lookup[2] == 0 && lookup[6] == 0;      // an empty description: a "SIPPPLK3" proof
+    const plonk_desc::Lookup l = plonk_desc::lookup_of(lookup);      // an empty description: a "SIPPPLK3" proof
     int r;
     try {
-        r = plonk_verify(proof, len, constants_sigmas_cap, *p, *fp, *c, circuit_digest, empty ? nullptr : lookup);
+        r = plonk_verify(proof, len, constants_sigmas_cap, *p, *fp, *c, circuit_digest, l.empty() ? nullptr : &l);
     } catch (...) {
         return SIPP_E_NOMEM;
     }

@@ -337,6 +337,10 @@ REFUSALS = [
     ("n_look_129", (2, 0, 129, 3, 4, 4, 2, 0), E_UNSUPPORTED),
     ("n_tab_129", (2, 0, 2, 3, 4, 4, 129, 0), E_UNSUPPORTED),
 ]
+# served on the same circuit, one step inside a refusal above: look_wire0 + 2 n_look == num_wires (looking_wires_run_outside is one past)
+SERVED_AT_THE_EDGE = [
+    ("looking_wires_end_at_the_last_wire", (2, 4, 2, 3, 4, 4, 2, 0)),
+]
 
 
 # ---- whole proofs: the shape, and the verifier's vanishing equation read from the opened values ------------------------------------------
