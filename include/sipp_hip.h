@@ -731,6 +731,55 @@ int sipp_plonk_verify_gates_lookup(const uint64_t *proof, size_t len, const uint
                                    const uint32_t *lookup, int *reason);
 int sipp_circuit_set_lookup(sipp_circuit_data *cd, const uint32_t *lookup);
 
+/* ---- ZERO KNOWLEDGE: salted oracles and blinding rows, the randomness drawn on the device from a seed ---------
+ * What plonky2's `zero_knowledge` switch does, as recalled: the wires, Z / partial-products and quotient oracles carry SIPP_SALT_SIZE
+ * salt words per leaf (FriParams::hiding), and the circuit carries blinding rows.  ONE random function serves both:
+ *   block(seed[4], counter, stream, index) = the first 8 words of hash_n_to_m_no_pad([seed0..3, counter, stream, index], 8), that is one
+ *   Poseidon permutation of [seed0, seed1, seed2, seed3, counter, stream, index, 0, 0, 0, 0, 0]; every output is canonical.
+ *   seed: four canonical words, secret and fresh per prover (a word >= p: SIPP_E_BADARG; the same for a counter >= p);
+ *   counter: the number of the proof under this seed -- two proofs never share blinding;
+ *   stream: 0 = blinding rows, 1 = wires salt, 2 = Z / partial-products salt, 3 = quotient salt.
+ *   Salt: leaf j of stream s, in LEAF order (the order of d_lde), takes words 4 (j & 1) .. 4 (j & 1) + 3 of block(seed, counter, s, j >> 1).
+ *   Blinding rows: wire w of table row r takes word w & 7 of block(seed, counter, 0, r 2^9 + (w >> 3))  (num_wires <= 4096).
+ * sipp_blind_salt: the four salt columns of one oracle, written behind its ncols polynomial columns: d_lde [ncols + 4][2^log_m] in leaf
+ * order, 16-byte aligned, stream 1 .. 3.  For callers that commit their wires themselves.
+ * SIPP_GEN_RANDOM (p = first wire, number of wires; first + number <= num_wires): on its rows those wires take the blinding-row words.
+ * It depends on no other cell: both witness calls fill its rows with a kernel of their own before anything else runs.  The seed reaches
+ * it through the _blind siblings of the two witness calls (the plain names pass NULL); a SIPP_GEN_RANDOM generator without a seed is
+ * SIPP_E_BADARG, as a PublicInput generator without its hash.
+ * sipp_plonk_prove_gates_zk: sipp_plonk_prove_gates_lookup with `blind`.  NULL: that call, byte for byte.  Not NULL: fp->hiding must be 1
+ * (and blind must not be NULL under a hiding fp): SIPP_E_BADARG otherwise.  Oracles 1 .. 3 then hold four salt columns behind their
+ * polynomials, filled by one launch before the first commitment, and are opened with n_salt = 4; constants_sigmas is never salted.  A
+ * pre-committed wires oracle brings its own salt: n_salt must be 4 under blinding and 0 without.
+ * Flat proof "SIPPPLK5": the 24 header words of "SIPPPLK4" with the new magic and header[12] = 1; the eight description words are all
+ * zero without lookups.  Caps, opening section and public inputs follow as before.
+ * Verification: sipp_plonk_verify_gates / _verify_gates_lookup decide by fp->hiding which proof they accept: under hiding = 1 only
+ * "SIPPPLK5" with header[12] = 1, opened with n_salt = {0, 4, 4, 4}; under hiding = 0 only "SIPPPLK3" / "SIPPPLK4".  Anything else is
+ * stage 201.
+ * Circuit data: sipp_circuit_build accepts a hiding fp.  sipp_circuit_set_blinding sets the seed and zeroes the counter; every
+ * sipp_circuit_prove / _prove_inputs / _prove_words uses the current counter, then increments it (a refusal increments it too).  A hiding
+ * circuit data without a seed proves nothing (SIPP_E_BADARG); a seed on a non-hiding one is SIPP_E_BADARG. */
+#define SIPP_GEN_RANDOM 18
+/* `blind` below: FIVE u64 words -- seed[0 .. 3], then the counter -- which is the memory of this struct (a caller that holds one passes
+ * its address, cast); NULL where the text above allows none */
+typedef struct sipp_blinding { uint64_t seed[4]; uint64_t counter; } sipp_blinding;
+int sipp_blind_salt(sipp_ctx *ctx, uint64_t *d_lde, uint32_t ncols, uint32_t log_m, const uint64_t *blind, uint32_t stream);
+int sipp_plonk_generate_witness_blind(sipp_ctx *ctx, uint64_t *d_wires, const uint64_t *d_constants, uint32_t log_n, uint32_t num_wires,
+                                      uint32_t num_constants, const sipp_plonk_generator *gens, size_t n_gens,
+                                      const uint64_t public_inputs_hash[4], const uint64_t *blind);
+int sipp_plonk_generate_witness_levels_blind(sipp_ctx *ctx, uint64_t *d_wires, const uint64_t *d_constants, uint32_t log_n,
+                                             uint32_t num_wires, uint32_t num_constants, const sipp_plonk_generator *gens, size_t n_gens,
+                                             const uint64_t public_inputs_hash[4], const sipp_plonk_schedule *sched,
+                                             const uint64_t *blind);
+size_t sipp_plonk_gates_zk_proof_size(uint32_t log_n, const sipp_plonk_params *p, const sipp_fri_params *fp, const sipp_plonk_circuit *c,
+                                      uint32_t n_public_inputs, const uint32_t *lookup);
+int sipp_plonk_prove_gates_zk(sipp_ctx *ctx, const uint64_t *d_wires, const uint64_t *d_constants_sigmas, const sipp_oracle *wires_oracle,
+                              const uint64_t *wires_cap, const sipp_oracle *constants_sigmas_oracle, uint32_t log_n,
+                              const sipp_plonk_params *p, const sipp_fri_params *fp, const sipp_plonk_circuit *c,
+                              const uint64_t circuit_digest[4], const uint64_t *public_inputs, uint32_t n_public_inputs,
+                              const uint32_t *lookup, const uint64_t *blind, uint64_t *proof_out, size_t proof_cap, size_t *proof_len);
+int sipp_circuit_set_blinding(sipp_circuit_data *cd, const uint64_t seed[4]);
+
 /* ---- verification of the generic proofs (host code like sipp_stark_verify; stages in *reason, may be NULL) -------------------------
  * sipp_fri_verify_openings: PolynomialBatch::verify_openings over a proof of sipp_fri_prove_openings -- caps[o] = the cap of oracle o
  * (2^cap_height x 4 words), ncols / n_salt (may be NULL = 0) per oracle, the batches as proved; the caller's transcript goes in and

@@ -137,6 +137,15 @@ pub const SIPP_GEN_POSEIDON_MDS: u32 = 16;
 /// SIPP_GEN_*: a looking row's y cells from a dense lookup table (p = look_wire0, n_look, tab_const0, n_tab, base_col)
 pub const SIPP_GEN_LOOKUP: u32 = 17;
 
+/// the seed of a zero-knowledge prover (four canonical words, secret) and the number of the proof under it (include/sipp_hip.h,
+/// "ZERO KNOWLEDGE"); the calls take it as its five words: `&b as *const SippBlinding as *const u64`
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct SippBlinding {
+    pub seed: [u64; 4],
+    pub counter: u64,
+}
+
 /// one gate family's witness generator with its layout (include/sipp_hip.h, "WITNESS GENERATORS"): kind = SIPP_GEN_*
 #[repr(C)]
 #[derive(Clone, Copy)]
@@ -312,6 +321,23 @@ extern "C" {
                                           fp: *const SippFriParams, c: *const SippPlonkCircuit, circuit_digest: *const u64,
                                           lookup: *const u32, reason: *mut c_int) -> c_int;
     pub fn sipp_circuit_set_lookup(cd: *mut SippCircuitDataOpaque, lookup: *const u32) -> c_int;
+    /// zero knowledge: salt columns and blinding rows drawn on the device from a seed; the "SIPPPLK5" prover (blind null: the lookup call)
+    pub fn sipp_blind_salt(ctx: *mut SippCtxOpaque, d_lde: *mut u64, ncols: u32, log_m: u32, blind: *const u64, stream: u32) -> c_int;
+    pub fn sipp_plonk_generate_witness_blind(ctx: *mut SippCtxOpaque, d_wires: *mut u64, d_constants: *const u64, log_n: u32, num_wires: u32,
+                                             num_constants: u32, gens: *const SippPlonkGenerator, n_gens: usize,
+                                             public_inputs_hash: *const u64, blind: *const u64) -> c_int;
+    pub fn sipp_plonk_generate_witness_levels_blind(ctx: *mut SippCtxOpaque, d_wires: *mut u64, d_constants: *const u64, log_n: u32,
+                                                    num_wires: u32, num_constants: u32, gens: *const SippPlonkGenerator, n_gens: usize,
+                                                    public_inputs_hash: *const u64, sched: *const SippPlonkSchedule,
+                                                    blind: *const u64) -> c_int;
+    pub fn sipp_plonk_gates_zk_proof_size(log_n: u32, p: *const SippPlonkParams, fp: *const SippFriParams, c: *const SippPlonkCircuit,
+                                          n_public_inputs: u32, lookup: *const u32) -> usize;
+    pub fn sipp_plonk_prove_gates_zk(ctx: *mut SippCtxOpaque, d_wires: *const u64, d_constants_sigmas: *const u64,
+                                     wires_oracle: *const SippOracle, wires_cap: *const u64, constants_sigmas_oracle: *const SippOracle,
+                                     log_n: u32, p: *const SippPlonkParams, fp: *const SippFriParams, c: *const SippPlonkCircuit,
+                                     circuit_digest: *const u64, public_inputs: *const u64, n_public_inputs: u32, lookup: *const u32,
+                                     blind: *const u64, proof_out: *mut u64, proof_cap: usize, proof_len: *mut usize) -> c_int;
+    pub fn sipp_circuit_set_blinding(cd: *mut SippCircuitDataOpaque, seed: *const u64) -> c_int;
     pub fn sipp_ntt_batch(ctx: *mut SippCtxOpaque, d_cols: *mut u64, col_stride: usize, ncols: usize, log_n: u32, inverse: c_int) -> c_int;
     pub fn sipp_lde_batch(ctx: *mut SippCtxOpaque, d_values: *const u64, d_coeffs: *mut u64, d_lde: *mut u64, ncols: usize, log_n: u32) -> c_int;
     pub fn sipp_poseidon_leaves(ctx: *mut SippCtxOpaque, d_lde: *const u64, ncols: usize, log_leaves: u32, d_digests: *mut u64) -> c_int;

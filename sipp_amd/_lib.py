@@ -111,6 +111,16 @@ class PlonkScheduleHost(C.Structure):
         return s
 
 
+class Blinding(C.Structure):
+    """sipp_blinding: the seed of a zero-knowledge prover (four canonical words, secret) and the number of the proof under it; the C
+    calls take its five words (C.byref of one)"""
+    _fields_ = [("seed", C.c_uint64 * 4), ("counter", C.c_uint64)]
+
+    @classmethod
+    def of(cls, seed, counter=0):
+        return cls((C.c_uint64 * 4)(*[int(x) for x in seed]), int(counter))
+
+
 class Challenger(C.Structure):
     _fields_ = [("state", C.c_uint64 * 12), ("in_buf", C.c_uint64 * 8), ("n_in", C.c_uint64), ("out_buf", C.c_uint64 * 8),
                 ("n_out", C.c_uint64)]
@@ -189,6 +199,17 @@ SIGNATURES = {
     "sipp_plonk_verify_gates_lookup": (C.c_int, [u64p, C.c_size_t, u64p, C.POINTER(PlonkParams), C.POINTER(FriParams), C.POINTER(PlonkCircuit), u64p,
                                                  u32p, C.POINTER(C.c_int)]),
     "sipp_circuit_set_lookup": (C.c_int, [vp, u32p]),
+    "sipp_blind_salt": (C.c_int, [vp, vp, C.c_uint32, C.c_uint32, vp, C.c_uint32]),
+    "sipp_plonk_gates_zk_proof_size": (C.c_size_t, [C.c_uint32, C.POINTER(PlonkParams), C.POINTER(FriParams), C.POINTER(PlonkCircuit), C.c_uint32,
+                                                    u32p]),
+    "sipp_plonk_prove_gates_zk": (C.c_int, [vp, vp, vp, C.POINTER(Oracle), u64p, C.POINTER(Oracle), C.c_uint32, C.POINTER(PlonkParams),
+                                            C.POINTER(FriParams), C.POINTER(PlonkCircuit), u64p, u64p, C.c_uint32, u32p, vp, vp,
+                                            C.c_size_t, C.POINTER(C.c_size_t)]),
+    "sipp_circuit_set_blinding": (C.c_int, [vp, u64p]),
+    "sipp_plonk_generate_witness_blind": (C.c_int, [vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(PlonkGenerator), C.c_size_t, u64p,
+                                                    vp]),
+    "sipp_plonk_generate_witness_levels_blind": (C.c_int, [vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(PlonkGenerator), C.c_size_t,
+                                                           u64p, C.POINTER(PlonkSchedule), vp]),
     "sipp_plonk_generate_witness": (C.c_int, [vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(PlonkGenerator), C.c_size_t, u64p]),
     "sipp_plonk_generate_witness_levels": (C.c_int, [vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(PlonkGenerator), C.c_size_t, u64p,
                                                      C.POINTER(PlonkSchedule)]),
@@ -249,7 +270,8 @@ SIPP_E_VERIFY = -9
 
 def plonk_verify_gates_lookup(proof, constants_sigmas_cap, p, fp, circuit, digest, lookup):
     """sipp_plonk_verify_gates_lookup: the library's own check of a "SIPPPLK4" proof (host code; no ctx, no GPU) against the caller's
-    lookup description (eight words; an empty one: a "SIPPPLK3" proof).  Returns 0 for an accepted proof, else the refusing stage."""
+    lookup description (eight words; an empty one: a "SIPPPLK3" proof).  Under fp.hiding = 1 it accepts a "SIPPPLK5" proof alone, under
+    hiding = 0 none.  Returns 0 for an accepted proof, else the refusing stage."""
     pf = np.ascontiguousarray(proof, dtype=np.uint64)
     cap = np.ascontiguousarray(constants_sigmas_cap, dtype=np.uint64).reshape(-1)
     reason = C.c_int(0)
@@ -538,20 +560,44 @@ class Ctx:
         return self._plonk_prove("plonk_prove_gates_lookup", "sipp_plonk_gates_lookup_proof_size", cap, wires, constants_sigmas, wires_oracle,
                                  wires_cap, cs_oracle, log_n, p, fp, circuit, digest, pis, [words])
 
-    def plonk_generate_witness(self, wires, constants, log_n, gens, pih=None):
+    def plonk_generate_witness(self, wires, constants, log_n, gens, pih=None, blind=None):
         """sipp_plonk_generate_witness: the gates' witness generators, in place on the device wire table [num_wires][N]; constants
-        [>= num_constants][N] device tensor (the front of constants_sigmas); gens = [(kind, selector_index, row, p0 .. p4)]"""
+        [>= num_constants][N] device tensor (the front of constants_sigmas); gens = [(kind, selector_index, row, p0 .. p4)];
+        blind = Blinding (sipp_plonk_generate_witness_blind: what a SIPP_GEN_RANDOM generator needs) or None"""
         arr = (PlonkGenerator * len(gens))(*[PlonkGenerator(int(g[0]), int(g[1]), int(g[2]), (C.c_uint32 * 5)(*[int(x) for x in g[3:8]])) for g in gens])
-        self._ck(self.L.sipp_plonk_generate_witness(self.h, wires.data_ptr(), constants.data_ptr(), log_n, wires.shape[0], constants.shape[0], arr,
-                                                    len(gens), None if pih is None else self._u64([int(x) for x in pih])), "plonk_generate_witness")
+        args = [self.h, wires.data_ptr(), constants.data_ptr(), log_n, wires.shape[0], constants.shape[0], arr, len(gens),
+                None if pih is None else self._u64([int(x) for x in pih])]
+        if blind is None:
+            self._ck(self.L.sipp_plonk_generate_witness(*args), "plonk_generate_witness")
+        else:
+            self._ck(self.L.sipp_plonk_generate_witness_blind(*args, C.byref(blind)), "plonk_generate_witness_blind")
 
-    def plonk_generate_witness_levels(self, wires, constants, log_n, gens, pih, sched):
+    def plonk_generate_witness_levels(self, wires, constants, log_n, gens, pih, sched, blind=None):
         """sipp_plonk_generate_witness_levels: the generators level by level with the copies between levels (sched = PlonkSchedule);
-        synchronises the ctx stream (the schedule's bounds are checked on the device)"""
+        synchronises the ctx stream (the schedule's bounds are checked on the device).  blind: as in plonk_generate_witness"""
         arr = (PlonkGenerator * len(gens))(*[PlonkGenerator(int(g[0]), int(g[1]), int(g[2]), (C.c_uint32 * 5)(*[int(x) for x in g[3:8]])) for g in gens])
-        self._ck(self.L.sipp_plonk_generate_witness_levels(self.h, wires.data_ptr(), constants.data_ptr(), log_n, wires.shape[0], constants.shape[0],
-                                                           arr, len(gens), None if pih is None else self._u64([int(x) for x in pih]), C.byref(sched)),
-                 "plonk_generate_witness_levels")
+        args = [self.h, wires.data_ptr(), constants.data_ptr(), log_n, wires.shape[0], constants.shape[0], arr, len(gens),
+                None if pih is None else self._u64([int(x) for x in pih]), C.byref(sched)]
+        if blind is None:
+            self._ck(self.L.sipp_plonk_generate_witness_levels(*args), "plonk_generate_witness_levels")
+        else:
+            self._ck(self.L.sipp_plonk_generate_witness_levels_blind(*args, C.byref(blind)), "plonk_generate_witness_levels_blind")
+
+    def plonk_prove_gates_zk(self, wires, constants_sigmas, log_n, p, fp, circuit, digest, public_inputs, lookup, blind, wires_oracle=None,
+                             wires_cap=None, cs_oracle=None):
+        """sipp_plonk_prove_gates_zk: plonk_prove_gates_lookup with blind = Blinding (fp.hiding = 1: salted wires, Z / partial-products
+        and quotient oracles, the flat "SIPPPLK5" proof) or None (that call, byte for byte)"""
+        pis = [int(x) for x in public_inputs]
+        words = self._lookup_words(lookup)
+        cap = self.L.sipp_plonk_gates_zk_proof_size(log_n, C.byref(p), C.byref(fp), C.byref(circuit), len(pis), words)
+        return self._plonk_prove("plonk_prove_gates_zk", "sipp_plonk_gates_zk_proof_size", cap, wires, constants_sigmas, wires_oracle, wires_cap,
+                                 cs_oracle, log_n, p, fp, circuit, digest, pis, [words, None if blind is None else C.byref(blind)])
+
+    def blind_salt(self, lde, ncols, log_m, blind, stream):
+        """sipp_blind_salt: the four salt columns of stream 1 .. 3 behind the ncols polynomial columns of lde [ncols + 4, 2^log_m] (device
+        int64, leaf order), in place"""
+        assert lde.is_contiguous() and lde.shape[0] >= ncols + 4 and lde.shape[1] == 1 << log_m
+        self._ck(self.L.sipp_blind_salt(self.h, lde.data_ptr(), ncols, log_m, C.byref(blind), stream), "blind_salt")
 
     def plonk_perm_prove(self, wires, sigmas, log_n, p, fp, digest=(1, 2, 3, 4), pih=(0, 0, 0, 0)):
         cap = self.L.sipp_plonk_perm_proof_size(log_n, C.byref(p), C.byref(fp))
@@ -912,6 +958,11 @@ class CircuitData:
                                                      pis.ctypes.data_as(C.POINTER(C.c_uint64)) if len(pis) else None, len(pis), out.ctypes.data, cap,
                                                      C.byref(n)), "circuit_prove_words")
         return out[: n.value]
+
+    def set_blinding(self, seed):
+        """sipp_circuit_set_blinding: the seed (four canonical words) of a circuit data built with fri.hiding = 1; the counter restarts
+        at 0 and every prove call uses the next number"""
+        self.ctx._ck(self.L.sipp_circuit_set_blinding(self.h, self.ctx._u64(seed)), "circuit_set_blinding")
 
     def set_lookup(self, lookup):
         """sipp_circuit_set_lookup: the eight-word lookup description; every later prove call runs the multiplicities behind witness

@@ -16,6 +16,9 @@ gate programs more than one of them uses, the builder that turns rows and feeds 
                             declare_lookup(tables=True): several tables told apart by a tag (description word 7), and function tables --
                             function_table(values) is the dense table t -> values[t], function_lookup(table, xs) places looking rows
                             whose y cells SIPP_GEN_LOOKUP fills on the device and returns those cells as sources
+                            Blinding (include/sipp_hip.h "ZERO KNOWLEDGE"), off by default: declare_blinding() names a zero-constraint
+                            gate whose generator is SIPP_GEN_RANDOM; finish() then appends blinding_counts() rows of it
+  blinding_counts           plonky2's rule for the number of blinding rows, as recalled; overridable by keyword
   _Challenger               plonky2's RecursiveChallenger on a builder (sipp_amd/fri_proof.py says how it buffers and duplexes)
   CircuitProver             a built circuit through the library's CircuitData
 
@@ -34,6 +37,7 @@ GEN_ARITHMETIC_EXT, GEN_EXPONENTIATION, GEN_COSET_INTERPOLATION, GEN_REDUCING_EX
 GEN_BASE_SUM = 15
 GEN_POSEIDON_MDS = 16
 GEN_LOOKUP = 17
+GEN_RANDOM = 18
 # program factor kinds
 _W, _K, _PIH = 0, 1, 2
 # upstream's PoseidonGate layout (SIPP_GEN_POSEIDON_SWAP): 135 wires
@@ -148,6 +152,26 @@ def fri_params(log_n, rate_bits=3, cap_height=4, pow_bits=16, num_queries=28, ar
     return p
 
 
+def _fri_shape(fri):
+    """(num_queries, the rounds' arity bits) of a sipp_fri_params struct or of a dict with the same names"""
+    get = fri.get if isinstance(fri, dict) else lambda k: getattr(fri, k)
+    return int(get("num_queries")), [int(a) for a in list(get("arity_bits"))[:int(get("n_rounds"))]]
+
+
+def blinding_counts(fri, log_n, regular=None, z=None):
+    """(regular, z): the blinding rows of a circuit of 2^log_n rows under the FRI parameters `fri` -- plonky2's rule (circuit_builder.rs
+    blind_and_pad) as RECALLED, not pinned against upstream; the keywords override either count.  With D = 2 (the extension degree):
+        fri_openings = num_queries (1 + D sum_rounds (2^arity_bits - 1) + final_poly_len),  final_poly_len = 2^(log_n - sum arity_bits)
+        regular = D + fri_openings      rows whose wires are all random: every wire polynomial is opened at zeta (D values) and at the
+                                        queried leaves
+        z = 2 D + fri_openings          PAIRS of rows for the permutation argument: Z is opened at zeta and g zeta"""
+    D = 2
+    q, arity = _fri_shape(fri)
+    assert sum(arity) <= log_n
+    openings = q * (1 + D * sum((1 << a) - 1 for a in arity) + (1 << (log_n - sum(arity))))
+    return (D + openings if regular is None else int(regular)), (2 * D + openings if z is None else int(z))
+
+
 # ---- the gate programs more than one circuit uses ---------------------------------------------------------------------------------------
 def public_input_into(pr):
     for i in range(4):
@@ -220,6 +244,8 @@ class CircuitBuilder:
         self._pi_cells = [None] * n_pi                          # one cell of public input t: every cell of its cycle takes its value
         self._in_cells = []                                     # the same for the witness inputs
         self._lk = None                                         # declare_lookup()'s layout; without one nothing below changes
+        self._blind = None                                      # declare_blinding()'s gate and rule; without one nothing below changes
+        self.blinding, self.blind_rows = (0, 0), {"regular": [], "pairs": []}
 
     # ---- gates ----
     def declare(self, index, degree, gen=None, fill=None, *args):
@@ -429,10 +455,48 @@ class CircuitBuilder:
             return (0,) * 8
         return (lk["q_look"], lk["look_wire0"], lk["n_look"], lk["q_tab"], lk["tab_const0"], lk["tab_mult0"], lk["n_tab"], lk["tag_const0"])
 
+    # ---- blinding rows ----
+    def declare_blinding(self, gate, fri_of=None, **counts):
+        """gate: a gate of its own, declared with no constraints (declare(index, 0)); it gets the generator SIPP_GEN_RANDOM over every
+        wire.  finish() appends the blinding rows behind the circuit's: blinding_counts(fri_of(log_n), log_n, **counts) -- fri_of maps
+        the degree bits to the FRI parameters the circuit will be proved under (default: fri_params), counts overrides the rule
+        (regular=, z=).  `regular` rows have every wire random; each of `z` PAIRS has a first row like that and a second whose routed
+        wires are copies of the first's (scheduled like every copy; its other wires stay random): the sigmas swap the two cells, which
+        randomises Z.  Padding rows stay Noop rows of zeros."""
+        assert self._blind is None and gate != NOOP and self.gates[gate][5] == 0, "the blinding gate has no constraints and is not Noop"
+        self._generators.append((GEN_RANDOM, self._group[gate], gate, 0, self.num_wires, 0, 0, 0))
+        self._blind = {"gate": gate, "fri_of": fri_of if fri_of is not None else fri_params, "counts": counts}
+
+    def _blinding_rows(self, min_log_n):
+        """plonky2's loop: the counts for the degree the rows reach; if the blinding rows push the table over a power of two, again for
+        the larger degree, until they fit"""
+        bl, base = self._blind, len(self._rows)
+        log_n = max(min_log_n, (base - 1).bit_length())
+        while True:
+            regular, z = blinding_counts(bl["fri_of"](log_n), log_n, **bl["counts"])
+            need = max(min_log_n, (base + regular + 2 * z - 1).bit_length())
+            if need <= log_n:
+                break
+            log_n = need
+        g, R = bl["gate"], self.num_routed
+        for _ in range(regular):
+            r = self.new_row(g)
+            self.place(r)
+            self.blind_rows["regular"].append(r)
+        for _ in range(z):
+            a, b = self.new_row(g), self.new_row(g)
+            self.place(a)
+            self.place(b, [(w, (w, a)) for w in range(R)])
+            self.blind_rows["pairs"].append((a, b))
+        self.blinding = (regular, z)
+        return log_n
+
     def finish(self, min_log_n):
         """N is known: cells become wire * N + row.  min_log_n: the device prover's FRI takes degree bits 10 .. 24; smaller circuits
         are padded with Noop rows"""
         self.flush_lookups()
+        if self._blind is not None:
+            min_log_n = self._blinding_rows(min_log_n)
         assert len(self.gates) == len(self.gate_names)
         self.programs = np.array(self._prog.words, dtype=np.int64)
         rows = self._rows
@@ -561,17 +625,30 @@ class CircuitProver:
     """A circuit through the library's CircuitData (sipp_circuit_build / _prove / _verify): the constants_sigmas commitment and the schedule
     go to the device once; prove(inputs) generates the witness there and returns the flat proof."""
 
-    def __init__(self, ctx, circ, fri=None, params=None, digest=None):
+    def __init__(self, ctx, circ, fri=None, params=None, digest=None, zero_knowledge=False, seed=None):
+        """zero_knowledge: prove under fri.hiding = 1 -- salted oracles, and the circuit's blinding rows filled from `seed` (four canonical
+        words; None: drawn from `secrets`), proof k under the seed with counter k.  ValueError if the FRI parameters need more blinding
+        rows than the circuit carries (CircuitBuilder.declare_blinding)."""
         from . import _lib
         self.circ = c = circ
         self.params = params if params is not None else _lib.PlonkParams(c.num_routed, 8, 2)
         self.fri = fri if fri is not None else fri_params(c.log_n)
+        if zero_knowledge:
+            need, have = blinding_counts(self.fri, c.log_n), getattr(c, "blinding", (0, 0))
+            if need[0] > have[0] or need[1] > have[1]:
+                raise ValueError("zero knowledge: these FRI parameters need %d + 2 * %d blinding rows, the circuit carries %d + 2 * %d" % (need + have))
+            hiding = _lib.FriParams.from_buffer_copy(self.fri)
+            hiding.hiding = 1
+            self.fri = hiding
         self.circuit = c.circuit()
         self._pc = _lib.PlonkCircuit.from_dict(self.circuit)
         self.data = _lib.CircuitData(ctx, c.log_n, self.params, self.fri, self._pc, c.constants_sigmas(), c.generators(), sched=c.schedule(),
                                      digest=digest)
         if "lookup" in self.circuit:      # the description rides in circuit(): the multiplicities and the argument on every prove path
             self.data.set_lookup(self.circuit["lookup"])
+        if zero_knowledge:
+            import secrets
+            self.data.set_blinding([secrets.randbelow(P) for _ in range(4)] if seed is None else seed)
         self.cap, self.digest = self.data.cap, self.data.digest
 
     def prove(self, *inputs):

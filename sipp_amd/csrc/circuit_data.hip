@@ -3,6 +3,7 @@
 // and :254 (`data.verify(proof)`), for a caller that holds no device memory of its own (the Rust shim; include/sipp_host.hpp's CircuitData).
 // Nothing new is computed here: build = sipp_commit_batch_ex over the uploaded constants_sigmas; prove = upload of the wire table with its
 // input cells (or a scatter of the input cells alone into a zeroed table), sipp_plonk_generate_witness[_levels], sipp_plonk_prove_gates; verify = sipp_plonk_verify_gates with the data's own cap / digest.
+// Under a hiding fp (zero knowledge) the same through the _blind witness calls and sipp_plonk_prove_gates_zk, with the data's seed and the number of the proof.
 // Device memory of a circuit data is its own (hipMalloc at build: the arena of the ctx is the provers' scratch and empties after each proof).
 #include "ctx.hpp"
 #include "host_challenger.hpp"
@@ -36,6 +37,9 @@ struct sipp_circuit_data {
     plonk_desc::Lookup lk{};
     uint64_t* d_index = nullptr;
     uint32_t n_index = 0;
+    // zero knowledge (a hiding fp): the seed of sipp_circuit_set_blinding and the number of the next proof under it
+    sipp_blinding blind{};
+    bool has_blind = false;
     ~sipp_circuit_data() {
         if (ctx) (void)hipSetDevice(ctx->device);
         for (void* q : dev) (void)hipFree(q);
@@ -91,7 +95,9 @@ extern "C" size_t sipp_circuit_workspace_bytes(uint32_t log_n, const sipp_plonk_
     // every oracle the prover commits inside the call (wires, Z / partial products, quotient chunks): coefficients + LDE, and the
     // quotient's own working set; the constants_sigmas oracle lives outside the arena
     const size_t n = (size_t)1 << log_n, cols = (size_t)c->num_wires + zs_columns(p) + (size_t)p->num_challenges * p->max_degree;
-    return 8 * n * (((size_t)1 + ((size_t)1 << fp->rate_bits)) * (cols + c->num_constants + p->num_routed_wires) + 64) + ((size_t)4 << 30);
+    // (a hiding fp: four salt columns behind the LDE of each of the three)
+    const size_t salt = fp->hiding ? (size_t)3 * SIPP_SALT_SIZE << fp->rate_bits : 0;
+    return 8 * n * (((size_t)1 + ((size_t)1 << fp->rate_bits)) * (cols + c->num_constants + p->num_routed_wires) + salt + 64) + ((size_t)4 << 30);
 }
 
 extern "C" void sipp_circuit_destroy(sipp_circuit_data* cd) {
@@ -190,22 +196,45 @@ extern "C" int sipp_circuit_verifier_data(const sipp_circuit_data* cd, uint64_t*
 }
 
 extern "C" size_t sipp_circuit_proof_size(const sipp_circuit_data* cd, uint32_t n_public_inputs) {
-    return cd ? sipp_plonk_gates_lookup_proof_size(cd->log_n, &cd->p, &cd->fp, &cd->circ, n_public_inputs, cd->lookup) : 0;
+    return cd ? sipp_plonk_gates_zk_proof_size(cd->log_n, &cd->p, &cd->fp, &cd->circ, n_public_inputs, cd->lookup) : 0;
 }
 
 namespace {
+// The blinding of ONE prove call: the data's seed with the current counter, which moves on at once -- so a call that is refused
+// further down has used its number up as well.  `use` is nullptr for a data that is not hiding.
+struct BlindTicket {
+    sipp_blinding b{};
+    const uint64_t* use = nullptr;      // its five words, as the C calls take them
+    explicit BlindTicket(sipp_circuit_data* cd) {
+        if (!cd->has_blind) return;
+        b = cd->blind;
+        use = b.seed;
+        cd->blind.counter++;
+    }
+};
+// a hiding circuit data proves only with a seed
+int blind_ready(sipp_circuit_data* cd) {
+    return cd->fp.hiding && !cd->has_blind ? sipp_fail(cd->ctx, SIPP_E_BADARG, "circuit prove: hiding FRI parameters and no seed (sipp_circuit_set_blinding)")
+                                           : SIPP_OK;
+}
+
 // what both prove calls do once the device wire table holds the input cells
-int prove_uploaded(sipp_circuit_data* cd, const uint64_t* public_inputs, uint32_t n_public_inputs, uint64_t* proof_out, size_t proof_cap,
-                   size_t* proof_len) {
+int prove_uploaded(sipp_circuit_data* cd, const uint64_t* blind, const uint64_t* public_inputs, uint32_t n_public_inputs, uint64_t* proof_out,
+                   size_t proof_cap, size_t* proof_len) {
     sipp_ctx* ctx = cd->ctx;
     uint64_t pih[4];
     host::Challenger::hash_no_pad(public_inputs, n_public_inputs, pih);
     if (cd->has_sched)
-        SIPP_TRY(sipp_plonk_generate_witness_levels(ctx, cd->d_wires, cd->d_cs, cd->log_n, cd->circ.num_wires, cd->circ.num_constants, cd->gens.data(),
-                                                    cd->gens.size(), pih, &cd->sched));
+        SIPP_TRY(sipp_plonk_generate_witness_levels_blind(ctx, cd->d_wires, cd->d_cs, cd->log_n, cd->circ.num_wires, cd->circ.num_constants,
+                                                          cd->gens.data(), cd->gens.size(), pih, &cd->sched, blind));
     else
-        SIPP_TRY(sipp_plonk_generate_witness(ctx, cd->d_wires, cd->d_cs, cd->log_n, cd->circ.num_wires, cd->circ.num_constants, cd->gens.data(),
-                                             cd->gens.size(), pih));
+        SIPP_TRY(sipp_plonk_generate_witness_blind(ctx, cd->d_wires, cd->d_cs, cd->log_n, cd->circ.num_wires, cd->circ.num_constants,
+                                                   cd->gens.data(), cd->gens.size(), pih, blind));
+    if (blind) {
+        if (!cd->lk.empty()) SIPP_TRY(sipp_lookup_multiplicities_indexed(ctx, cd->d_wires, cd->d_cs, cd->log_n, cd->lk, cd->d_index, cd->n_index));
+        return sipp_plonk_prove_gates_zk(ctx, cd->d_wires, cd->d_cs, nullptr, nullptr, &cd->cs_oracle, cd->log_n, &cd->p, &cd->fp, &cd->circ,
+                                         cd->digest, public_inputs, n_public_inputs, cd->lookup, blind, proof_out, proof_cap, proof_len);
+    }
     if (cd->lk.empty())
         return sipp_plonk_prove_gates(ctx, cd->d_wires, cd->d_cs, nullptr, nullptr, &cd->cs_oracle, cd->log_n, &cd->p, &cd->fp, &cd->circ, cd->digest,
                                       public_inputs, n_public_inputs, proof_out, proof_cap, proof_len);
@@ -274,6 +303,18 @@ extern "C" int sipp_circuit_set_input_map(sipp_circuit_data* cd, const uint64_t*
     return SIPP_OK;
 }
 
+extern "C" int sipp_circuit_set_blinding(sipp_circuit_data* cd, const uint64_t seed[4]) {
+    if (!cd) return SIPP_E_BADARG;
+    sipp_ctx* ctx = cd->ctx;
+    if (!seed) return sipp_fail(ctx, SIPP_E_BADARG, "circuit blinding: no seed");
+    if (!cd->fp.hiding) return sipp_fail(ctx, SIPP_E_BADARG, "circuit blinding: the circuit data was built without hiding FRI parameters");
+    const sipp_blinding b{{seed[0], seed[1], seed[2], seed[3]}, 0};
+    SIPP_TRY(sipp_blind_check(ctx, &b));
+    cd->blind = b;
+    cd->has_blind = true;
+    return SIPP_OK;
+}
+
 extern "C" int sipp_circuit_set_lookup(sipp_circuit_data* cd, const uint32_t* lookup) {
     if (!cd) return SIPP_E_BADARG;
     sipp_ctx* ctx = cd->ctx;
@@ -303,10 +344,12 @@ extern "C" int sipp_circuit_prove(sipp_circuit_data* cd, const uint64_t* wires, 
     sipp_ctx* ctx = cd->ctx;
     if (!wires || !proof_out || !proof_len || (n_public_inputs && !public_inputs) || n_public_inputs > (1u << 24))
         return sipp_fail(ctx, SIPP_E_BADARG, "circuit prove: null argument");
+    SIPP_TRY(blind_ready(cd));
+    const BlindTicket ticket(cd);
     SIPP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
     const size_t n = (size_t)1 << cd->log_n;
     SIPP_CHECK_HIP(ctx, hipMemcpyAsync(cd->d_wires, wires, (size_t)cd->circ.num_wires * n * 8, hipMemcpyHostToDevice, ctx->stream));
-    return prove_uploaded(cd, public_inputs, n_public_inputs, proof_out, proof_cap, proof_len);
+    return prove_uploaded(cd, ticket.use, public_inputs, n_public_inputs, proof_out, proof_cap, proof_len);
 }
 
 extern "C" int sipp_circuit_prove_inputs(sipp_circuit_data* cd, const uint64_t* cells, const uint64_t* values, size_t n_inputs,
@@ -316,6 +359,8 @@ extern "C" int sipp_circuit_prove_inputs(sipp_circuit_data* cd, const uint64_t* 
     sipp_ctx* ctx = cd->ctx;
     if ((n_inputs && (!cells || !values)) || !proof_out || !proof_len || (n_public_inputs && !public_inputs) || n_public_inputs > (1u << 24))
         return sipp_fail(ctx, SIPP_E_BADARG, "circuit prove inputs: null argument");
+    SIPP_TRY(blind_ready(cd));
+    const BlindTicket ticket(cd);
     const size_t total = (size_t)cd->circ.num_wires << cd->log_n;
     if (n_inputs > ((size_t)1 << 40)) return sipp_fail(ctx, SIPP_E_BADARG, "circuit prove inputs: too many pairs");
     for (size_t k = 0; k < n_inputs; k++)
@@ -334,7 +379,7 @@ extern "C" int sipp_circuit_prove_inputs(sipp_circuit_data* cd, const uint64_t* 
         SIPP_TRY(stage_inputs(cd, d_cells, nullptr, d_values, n_inputs, reinterpret_cast<unsigned int*>(d_pairs + 2 * n_inputs),
                               "circuit prove inputs: one cell given two different values"));
     }
-    return prove_uploaded(cd, public_inputs, n_public_inputs, proof_out, proof_cap, proof_len);
+    return prove_uploaded(cd, ticket.use, public_inputs, n_public_inputs, proof_out, proof_cap, proof_len);
 }
 
 extern "C" int sipp_circuit_prove_words(sipp_circuit_data* cd, const uint64_t* words, size_t n_words, const uint64_t* extra, size_t n_extra,
@@ -344,6 +389,8 @@ extern "C" int sipp_circuit_prove_words(sipp_circuit_data* cd, const uint64_t* w
     sipp_ctx* ctx = cd->ctx;
     if ((n_words && !words) || (n_extra && !extra) || !proof_out || !proof_len || (n_public_inputs && !public_inputs) || n_public_inputs > (1u << 24))
         return sipp_fail(ctx, SIPP_E_BADARG, "circuit prove words: null argument");
+    SIPP_TRY(blind_ready(cd));
+    const BlindTicket ticket(cd);
     if (!cd->has_map) return sipp_fail(ctx, SIPP_E_BADARG, "circuit prove words: no input map set (sipp_circuit_set_input_map)");
     if (n_words != cd->map_words || n_extra != cd->map_extra)
         return sipp_fail(ctx, SIPP_E_BADARG, "circuit prove words: n_words / n_extra differ from the input map's");
@@ -359,7 +406,7 @@ extern "C" int sipp_circuit_prove_words(sipp_circuit_data* cd, const uint64_t* w
         SIPP_TRY(stage_inputs(cd, cd->d_map, cd->d_map + n, d_staged, n, reinterpret_cast<unsigned int*>(d_staged + n_words + n_extra),
                               "circuit prove words: one cell mapped to two different values"));
     }
-    return prove_uploaded(cd, public_inputs, n_public_inputs, proof_out, proof_cap, proof_len);
+    return prove_uploaded(cd, ticket.use, public_inputs, n_public_inputs, proof_out, proof_cap, proof_len);
 }
 
 extern "C" int sipp_circuit_verify(const sipp_circuit_data* cd, const uint64_t* proof, size_t len, int* reason) {

@@ -36,8 +36,8 @@ int commit_launch(sipp_ctx* ctx, const CommitParams& cp, const uint64_t* d_in, b
     const uint32_t log_m = log_n + cp.rate_bits;
     const size_t m = (size_t)1 << log_m;
     SIPP_TRY(commit_lde(ctx, d_in, from_coeffs, d_coeffs, d_lde, ncols, log_n, cp.rate_bits));
-    // salt columns: natural LDE order in, leaf order (= bit-reversed rows) behind the polynomial columns
-    if (cp.n_salt) SIPP_TRY(sipp_bitrev_cols(ctx, cp.d_salt, m, d_lde + ncols * m, m, log_m, cp.n_salt));
+    // salt columns: natural LDE order in, leaf order (= bit-reversed rows) behind the polynomial columns -- unless they are there already
+    if (cp.n_salt && !cp.salt_in_place) SIPP_TRY(sipp_bitrev_cols(ctx, cp.d_salt, m, d_lde + ncols * m, m, log_m, cp.n_salt));
     SIPP_TRY(sipp_k_poseidon_leaves(ctx, d_lde, m, ncols + cp.n_salt, log_m, d_tree));
     return sipp_k_merkle_levels(ctx, d_tree, log_m, cp.cap_height);
 }

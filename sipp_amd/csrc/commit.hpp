@@ -11,6 +11,8 @@ struct CommitParams {
     uint32_t rate_bits, cap_height;
     const uint64_t* d_salt = nullptr;   // n_salt columns of n << rate_bits words in natural LDE order, hashed behind the polynomials'
     uint32_t n_salt = 0;
+    // the n_salt columns already sit behind the polynomial columns of d_lde, in LEAF order (blind.hip filled them): d_salt is not read
+    bool salt_in_place = false;
 };
 
 // u64 words of a Merkle tree over 2^log_leaves leaves, levels back to back: 2 * leaves * 4

@@ -275,6 +275,26 @@ int sipp_lookup_sums(sipp_ctx* ctx, const uint64_t* d_wires, const uint64_t* d_c
 int sipp_lookup_quotient_terms(sipp_ctx* ctx, const uint64_t* d_wires_lde, const uint64_t* d_consts_lde, const uint64_t* d_sums_lde, uint32_t log_n,
                                uint32_t rate_bits, uint32_t log_d, const sipp_plonk_params* p, const plonk_desc::Lookup& l, const uint64_t* etas,
                                const uint64_t* thetas, const uint64_t* alphas, uint64_t terms_in_front, uint64_t* d_qv);
+// blind.hip -- the randomness of a zero-knowledge proof (include/sipp_hip.h "ZERO KNOWLEDGE").  _check: a seed with canonical words and
+// counter; _salt_launch: ONE launch fills the four salt columns at bases[t] (the first salt column of an oracle's LDE buffer of 2^log_m
+// leaves) from stream streams[t], for up to three oracles; _rows_launch: the cells of a SIPP_GEN_RANDOM generator's rows.  Launches only.
+int sipp_blind_check(sipp_ctx* ctx, const sipp_blinding* b);
+// the C ABI hands a seed and counter over as five u64 words (include/sipp_hip.h): a copy as the struct, p = nullptr for NULL
+static_assert(sizeof(sipp_blinding) == 5 * sizeof(uint64_t), "sipp_blinding is five words");
+struct BlindArg {
+    sipp_blinding b{};
+    const sipp_blinding* p = nullptr;
+    explicit BlindArg(const uint64_t* words) {
+        if (!words) return;
+        memcpy(&b, words, sizeof b);
+        p = &b;
+    }
+    BlindArg(const BlindArg&) = delete;
+};
+int sipp_blind_salt_launch(sipp_ctx* ctx, const sipp_blinding& b, uint64_t* const* bases, const uint32_t* streams, uint32_t n_targets,
+                           uint32_t log_m);
+int sipp_blind_rows_launch(sipp_ctx* ctx, uint64_t* d_wires, const uint64_t* d_constants, uint32_t log_n, const sipp_plonk_generator& g,
+                           const sipp_blinding& b);
 
 // ---- AIR layer (trace.hip / quotient.hip / stark.hip) -----------------------------------------
 #include "air_tables.h"

@@ -13,6 +13,7 @@
 // denominators; a denominator that is 0 stays out of the trick and makes its own chunk 0, as the oracle's cell-by-cell 1 / 0 = 0), a
 // two-level prefix product over the rows for Z, one lane per coset point for the quotient.  All HBM-streaming with O(R) products per
 // cell read -- integer VALU bound like the STARK quotient kernels.
+#include "commit.hpp"
 #include "ctx.hpp"
 #include "prover.hpp"
 #include <algorithm>
@@ -501,6 +502,8 @@ struct PlonkExtra {
     // a NON-EMPTY lookup description ("SIPPPLK4", with circ): the S / U columns behind the permutation's in the zs_partial_products
     // oracle, eta / theta drawn behind the gammas, the lookup terms behind the gate constraints
     const Lookup* lookup = nullptr;
+    // zero knowledge ("SIPPPLK5", with circ and a hiding fp): oracles 1 .. 3 carry four salt columns drawn from this seed (blind.hip)
+    const sipp_blinding* blind = nullptr;
 };
 int plonk_prove_impl(sipp_ctx* ctx, const uint64_t* d_wires, const uint64_t* d_sigmas, uint32_t log_n, const sipp_plonk_params* p,
                      const sipp_fri_params* fp, const uint64_t circuit_digest[4], const uint64_t public_inputs_hash[4], const PlonkExtra& ex,
@@ -513,19 +516,21 @@ struct PlonkLayout {
     uint32_t ncols[4];
     sipp_poly_range at_zeta[4], at_gzeta[2];
     uint32_t n_gzeta;         // 1, or 2 with lookups: the S columns behind the Z columns
-    size_t header_words;      // 8, 16 with the gates as data ("SIPPPLK3"), 24 with a lookup description ("SIPPPLK4")
-    PlonkLayout(const sipp_plonk_params* p, uint32_t m, const sipp_plonk_circuit* circ, const Lookup* lookup = nullptr) {
+    size_t header_words;      // 8, 16 with the gates as data ("SIPPPLK3"), 24 with a lookup description ("SIPPPLK4") or salt ("SIPPPLK5")
+    uint32_t n_salt[4];       // salt words per leaf: 4 on the wires, zs_partial_products and quotient oracles of a zero-knowledge proof
+    PlonkLayout(const sipp_plonk_params* p, uint32_t m, const sipp_plonk_circuit* circ, const Lookup* lookup = nullptr, bool zk = false) {
         const uint32_t R = p->num_routed_wires, C = p->num_challenges;
         const uint32_t n_lk = lookup ? lookup->columns(p->max_degree, C) : 0;
         const uint32_t nc[4] = {(circ ? circ->num_constants : 0) + R, circ ? circ->num_wires : R, C * m + n_lk, C * p->max_degree};
         for (uint32_t o = 0; o < 4; o++) {
             ncols[o] = nc[o];
             at_zeta[o] = sipp_poly_range{o, 0, nc[o]};
+            n_salt[o] = zk && o ? SIPP_SALT_SIZE : 0;
         }
         at_gzeta[0] = sipp_poly_range{2, 0, C};
         at_gzeta[1] = sipp_poly_range{2, C * m, C * m + C};
         n_gzeta = n_lk ? 2 : 1;
-        header_words = n_lk ? 24 : circ ? 16 : 8;
+        header_words = n_lk || zk ? 24 : circ ? 16 : 8;
     }
     void batches(gl::E2 zeta, gl::E2 gzeta, sipp_fri_batch out[2]) const {
         out[0] = sipp_fri_batch{{zeta.c0, zeta.c1}, 4, at_zeta};
@@ -538,7 +543,7 @@ struct PlonkLayout {
     }
     size_t opening_words(uint32_t log_n, const sipp_fri_params* fp) const {
         sipp_oracle oracles[4];
-        for (int o = 0; o < 4; o++) oracles[o] = sipp_oracle{nullptr, nullptr, nullptr, ncols[o], 0};
+        for (int o = 0; o < 4; o++) oracles[o] = sipp_oracle{nullptr, nullptr, nullptr, ncols[o], n_salt[o]};
         sipp_fri_batch b[2];
         batches(gl::e2(0), gl::e2(0), b);
         return sipp_fri_proof_size(oracles, 4, b, 2, log_n, fp);
@@ -546,10 +551,10 @@ struct PlonkLayout {
 };
 // words of a whole proof; 0 when check() refuses the parameters or the FRI parameters do not fit
 size_t plonk_proof_words(uint32_t log_n, const sipp_plonk_params* p, const sipp_fri_params* fp, const sipp_plonk_circuit* circ,
-                         uint32_t n_public_inputs, const Lookup* lookup = nullptr) {
+                         uint32_t n_public_inputs, const Lookup* lookup = nullptr, bool zk = false) {
     uint32_t log_d, m;
     if (!fp || check(nullptr, p, log_n, &log_d, &m) != SIPP_OK) return 0;
-    const PlonkLayout lay(p, m, circ, lookup);
+    const PlonkLayout lay(p, m, circ, lookup, zk);
     const size_t op = lay.opening_words(log_n, fp);
     return op ? lay.head_words(log_n, fp) + op + n_public_inputs : 0;
 }
@@ -588,14 +593,15 @@ int plonk_prove_impl(sipp_ctx* ctx, const uint64_t* d_wires, const uint64_t* d_s
                      uint64_t* proof_out, size_t proof_cap, size_t* proof_len) {
     uint32_t log_d, m;
     SIPP_TRY(check(ctx, p, log_n, &log_d, &m));
-    if (fp->rate_bits < log_d || fp->rate_bits > 3 || fp->cap_height > 8 || fp->hiding)
+    if (fp->rate_bits < log_d || fp->rate_bits > 3 || fp->cap_height > 8 || (fp->hiding && !ex.blind))
         return sipp_fail(ctx, SIPP_E_UNSUPPORTED, "plonk: blowup 2^rate_bits >= quotient degree factor, <= 8, unsalted oracles");
     SIPP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
     ArenaScope scope(ctx);
     const uint32_t R = p->num_routed_wires, D = p->max_degree, C = p->num_challenges, nz = C * m;
     const size_t n = (size_t)1 << log_n, M = n << fp->rate_bits, cap_n = (size_t)1 << std::min(fp->cap_height, log_n + fp->rate_bits);
     const uint32_t K = ex.circ ? ex.circ->num_constants : 0, Wn = ex.circ ? ex.circ->num_wires : R;
-    const PlonkLayout lay(p, m, ex.circ, ex.lookup);
+    const bool zk = ex.blind != nullptr;
+    const PlonkLayout lay(p, m, ex.circ, ex.lookup, zk);
     const uint32_t* ncols = lay.ncols;             // (ncols[2] = nz + the S / U columns of a lookup description)
     const uint64_t* d_sigma_vals = d_sigmas + (size_t)K * n;      // the sigmas behind the constant columns
     uint64_t *co[4], *lde[4], *tree[4];
@@ -608,16 +614,32 @@ int plonk_prove_impl(sipp_ctx* ctx, const uint64_t* d_wires, const uint64_t* d_s
             continue;
         }
         co[o] = arena_alloc_t<uint64_t>(ctx, (size_t)ncols[o] * n);
-        lde[o] = arena_alloc_t<uint64_t>(ctx, (size_t)ncols[o] * M);
+        lde[o] = arena_alloc_t<uint64_t>(ctx, (size_t)(ncols[o] + lay.n_salt[o]) * M);
         tree[o] = arena_alloc_t<uint64_t>(ctx, tree_words(log_n + fp->rate_bits));
         if (!co[o] || !lde[o] || !tree[o]) return SIPP_E_NOMEM;
     }
     std::vector<uint64_t> caps(4 * cap_n * 4);
     auto cap_of = [&](int o) { return caps.data() + (size_t)o * cap_n * 4; };
-    if (!pre[0])
-        SIPP_TRY(sipp_commit_batch_ex(ctx, d_sigmas, 0, co[0], lde[0], tree[0], ncols[0], log_n, fp->rate_bits, fp->cap_height, nullptr, 0, cap_of(0)));
+    // oracle o from values (or coefficients); a salted one hashes the four columns that already sit behind its polynomials' in leaf order
+    auto commit = [&](int o, const uint64_t* d_in, int from_coeffs) -> int {
+        if (!lay.n_salt[o])
+            return sipp_commit_batch_ex(ctx, d_in, from_coeffs, co[o], lde[o], tree[o], ncols[o], log_n, fp->rate_bits, fp->cap_height, nullptr, 0,
+                                        cap_of(o));
+        const int rc = commit_batch(ctx, CommitParams{fp->rate_bits, fp->cap_height, nullptr, lay.n_salt[o], true}, d_in, from_coeffs != 0, co[o],
+                                    lde[o], tree[o], ncols[o], log_n, cap_of(o));
+        if (rc != SIPP_OK) (void)hipStreamSynchronize(ctx->stream);
+        return rc;
+    };
+    if (zk) {      // the salt depends on no challenge: one launch fills the twelve columns (a pre-committed wires oracle brings its own)
+        uint64_t* bases[3];
+        uint32_t streams[3], nt = 0;
+        for (uint32_t o = 1; o < 4; o++)
+            if (!pre[o]) bases[nt] = lde[o] + (size_t)ncols[o] * M, streams[nt++] = o;
+        SIPP_TRY(sipp_blind_salt_launch(ctx, *ex.blind, bases, streams, nt, log_n + fp->rate_bits));
+    }
+    if (!pre[0]) SIPP_TRY(commit(0, d_sigmas, 0));
     if (!pre[1])
-        SIPP_TRY(sipp_commit_batch_ex(ctx, d_wires, 0, co[1], lde[1], tree[1], ncols[1], log_n, fp->rate_bits, fp->cap_height, nullptr, 0, cap_of(1)));
+        SIPP_TRY(commit(1, d_wires, 0));
     else
         memcpy(cap_of(1), ex.wires_cap, cap_n * 32);
     host::Challenger ch;
@@ -638,7 +660,7 @@ int plonk_prove_impl(sipp_ctx* ctx, const uint64_t* d_wires, const uint64_t* d_s
         SIPP_TRY(sipp_plonk_zs_partial_products(ctx, d_wires, d_sigma_vals, log_n, p, betas, gammas, zs));
         if (ex.lookup)
             SIPP_TRY(sipp_lookup_sums(ctx, d_wires, d_sigmas, log_n, p, *ex.lookup, etas, thetas, zs + (size_t)nz * n));
-        SIPP_TRY(sipp_commit_batch_ex(ctx, zs, 0, co[2], lde[2], tree[2], ncols[2], log_n, fp->rate_bits, fp->cap_height, nullptr, 0, cap_of(2)));
+        SIPP_TRY(commit(2, zs, 0));
     }
     ch.observe_many(cap_of(2), cap_n * 4);
     for (uint32_t c = 0; c < C; c++) alphas[c] = ch.get();
@@ -648,11 +670,11 @@ int plonk_prove_impl(sipp_ctx* ctx, const uint64_t* d_wires, const uint64_t* d_s
         SIPP_TRY(quotient_chunks_impl(ctx, lde[1], lde[0] + (size_t)K * M, lde[2], log_n, fp->rate_bits, p, betas, gammas, alphas, ex.d_gate_terms,
                                       ex.n_gate_terms, ex.circ ? &gs : nullptr, ex.lookup ? &ls : nullptr, co[3]));
     }
-    SIPP_TRY(sipp_commit_batch_ex(ctx, co[3], 1, co[3], lde[3], tree[3], (size_t)C * D, log_n, fp->rate_bits, fp->cap_height, nullptr, 0, cap_of(3)));
+    SIPP_TRY(commit(3, co[3], 1));
     ch.observe_many(cap_of(3), cap_n * 4);
     const gl::E2 zeta = ch.get_ext();
     sipp_oracle oracles[4];
-    for (int o = 0; o < 4; o++) oracles[o] = sipp_oracle{co[o], lde[o], tree[o], ncols[o], 0};
+    for (int o = 0; o < 4; o++) oracles[o] = sipp_oracle{co[o], lde[o], tree[o], ncols[o], lay.n_salt[o]};
     sipp_fri_batch batches[2];
     lay.batches(zeta, gl::scale(zeta, gl::root_of_unity(log_n)), batches);
     const size_t op_cap = lay.opening_words(log_n, fp);
@@ -663,10 +685,10 @@ int plonk_prove_impl(sipp_ctx* ctx, const uint64_t* d_wires, const uint64_t* d_s
     ch.store(&cs);
     size_t op_len = 0;
     SIPP_TRY(sipp_fri_prove_openings(ctx, oracles, 4, batches, 2, log_n, fp, &cs, proof_out + head, proof_cap - head - tail, &op_len));
-    if (ex.lookup) {
-        uint64_t h[24] = {0x344b4c5050504953ULL /* "SIPPPLK4" */, log_n, R, D, C, head + op_len + tail, Wn, K, ex.circ->num_selectors,
-                          ex.circ->num_gates, num_gate_constraints(ex.circ), tail, 0, 0, 0, 0};
-        for (int q = 0; q < 8; q++) h[16 + q] = plonk_desc::lookup_word(*ex.lookup, q);
+    if (ex.lookup || zk) {      // "SIPPPLK5": header[12] = 1, the description words all zero without lookups
+        uint64_t h[24] = {zk ? 0x354b4c5050504953ULL /* "SIPPPLK5" */ : 0x344b4c5050504953ULL /* "SIPPPLK4" */, log_n, R, D, C, head + op_len + tail,
+                          Wn, K, ex.circ->num_selectors, ex.circ->num_gates, num_gate_constraints(ex.circ), tail, zk ? 1u : 0u, 0, 0, 0};
+        for (int q = 0; q < 8; q++) h[16 + q] = ex.lookup ? plonk_desc::lookup_word(*ex.lookup, q) : 0;
         memcpy(proof_out, h, sizeof h);
     } else if (ex.circ) {
         const uint64_t h[16] = {0x334b4c5050504953ULL /* "SIPPPLK3" */, log_n, R, D, C, head + op_len + tail, Wn, K, ex.circ->num_selectors,
@@ -709,6 +731,12 @@ size_t sipp_plonk_gates_lookup_proof_size(uint32_t log_n, const sipp_plonk_param
     return plonk_proof_words(log_n, p, fp, c, n_public_inputs, l.empty() ? nullptr : &l);
 }
 
+static int prove_gates_any(sipp_ctx* ctx, const uint64_t* d_wires, const uint64_t* d_constants_sigmas, const sipp_oracle* wires_oracle,
+                           const uint64_t* wires_cap, const sipp_oracle* constants_sigmas_oracle, uint32_t log_n, const sipp_plonk_params* p,
+                           const sipp_fri_params* fp, const sipp_plonk_circuit* c, const uint64_t circuit_digest[4], const uint64_t* public_inputs,
+                           uint32_t n_public_inputs, const uint32_t* lookup, const sipp_blinding* blind, bool zk_entry, uint64_t* proof_out,
+                           size_t proof_cap, size_t* proof_len);
+
 int sipp_plonk_prove_gates(sipp_ctx* ctx, const uint64_t* d_wires, const uint64_t* d_constants_sigmas, const sipp_oracle* wires_oracle,
                            const uint64_t* wires_cap, const sipp_oracle* constants_sigmas_oracle, uint32_t log_n, const sipp_plonk_params* p,
                            const sipp_fri_params* fp, const sipp_plonk_circuit* c, const uint64_t circuit_digest[4], const uint64_t* public_inputs,
@@ -723,23 +751,59 @@ int sipp_plonk_prove_gates_lookup(sipp_ctx* ctx, const uint64_t* d_wires, const 
                                   const sipp_plonk_params* p, const sipp_fri_params* fp, const sipp_plonk_circuit* c,
                                   const uint64_t circuit_digest[4], const uint64_t* public_inputs, uint32_t n_public_inputs,
                                   const uint32_t* lookup, uint64_t* proof_out, size_t proof_cap, size_t* proof_len) {
+    // (a hiding fp reaches plonk_prove_impl without a seed and is refused there, SIPP_E_UNSUPPORTED as before)
+    return prove_gates_any(ctx, d_wires, d_constants_sigmas, wires_oracle, wires_cap, constants_sigmas_oracle, log_n, p, fp, c, circuit_digest,
+                           public_inputs, n_public_inputs, lookup, nullptr, false, proof_out, proof_cap, proof_len);
+}
+
+size_t sipp_plonk_gates_zk_proof_size(uint32_t log_n, const sipp_plonk_params* p, const sipp_fri_params* fp, const sipp_plonk_circuit* c,
+                                      uint32_t n_public_inputs, const uint32_t* lookup) {
+    if (!fp || !fp->hiding) return sipp_plonk_gates_lookup_proof_size(log_n, p, fp, c, n_public_inputs, lookup);
+    Lookup l;
+    if (!sizes_ok(c, p) || sipp_lookup_check(nullptr, lookup, c->num_wires, c->num_constants, c->num_selectors, &l) != SIPP_OK) return 0;
+    return plonk_proof_words(log_n, p, fp, c, n_public_inputs, l.empty() ? nullptr : &l, true);
+}
+
+int sipp_plonk_prove_gates_zk(sipp_ctx* ctx, const uint64_t* d_wires, const uint64_t* d_constants_sigmas, const sipp_oracle* wires_oracle,
+                              const uint64_t* wires_cap, const sipp_oracle* constants_sigmas_oracle, uint32_t log_n, const sipp_plonk_params* p,
+                              const sipp_fri_params* fp, const sipp_plonk_circuit* c, const uint64_t circuit_digest[4],
+                              const uint64_t* public_inputs, uint32_t n_public_inputs, const uint32_t* lookup, const uint64_t* blind_words,
+                              uint64_t* proof_out, size_t proof_cap, size_t* proof_len) {
+    const BlindArg arg(blind_words);
+    const sipp_blinding* blind = arg.p;
+    return prove_gates_any(ctx, d_wires, d_constants_sigmas, wires_oracle, wires_cap, constants_sigmas_oracle, log_n, p, fp, c, circuit_digest,
+                           public_inputs, n_public_inputs, lookup, blind, true, proof_out, proof_cap, proof_len);
+}
+
+// the two entries above: `zk_entry` answers a hiding fp without a seed itself (SIPP_E_BADARG), the lookup entry leaves it to plonk_prove_impl
+static int prove_gates_any(sipp_ctx* ctx, const uint64_t* d_wires, const uint64_t* d_constants_sigmas, const sipp_oracle* wires_oracle,
+                           const uint64_t* wires_cap, const sipp_oracle* constants_sigmas_oracle, uint32_t log_n, const sipp_plonk_params* p,
+                           const sipp_fri_params* fp, const sipp_plonk_circuit* c, const uint64_t circuit_digest[4], const uint64_t* public_inputs,
+                           uint32_t n_public_inputs, const uint32_t* lookup, const sipp_blinding* blind, bool zk_entry, uint64_t* proof_out,
+                           size_t proof_cap, size_t* proof_len) {
     if (!ctx || !lookup || !d_wires || !d_constants_sigmas || !fp || !p || !c || !circuit_digest || !proof_out || !proof_len ||
         (n_public_inputs && !public_inputs) || (wires_oracle != nullptr) != (wires_cap != nullptr) || n_public_inputs > (1u << 24))
         return SIPP_E_BADARG;
     SIPP_TRY(circuit_check(ctx, c, p));
     Lookup l;
     SIPP_TRY(sipp_lookup_check(ctx, lookup, c->num_wires, c->num_constants, c->num_selectors, &l));
-    if ((wires_oracle && (wires_oracle->n_polys != c->num_wires || wires_oracle->n_salt || !wires_oracle->d_coeffs || !wires_oracle->d_lde ||
-                          !wires_oracle->d_tree)) ||
+    if (zk_entry && fp->hiding && !blind) return sipp_fail(ctx, SIPP_E_BADARG, "plonk: FRI parameters with hiding = 1 need a blinding seed");
+    if (blind) {
+        if (!fp->hiding) return sipp_fail(ctx, SIPP_E_BADARG, "plonk: a blinding seed needs FRI parameters with hiding = 1");
+        SIPP_TRY(sipp_blind_check(ctx, blind));
+    }
+    if ((wires_oracle && (wires_oracle->n_polys != c->num_wires || wires_oracle->n_salt != (blind ? SIPP_SALT_SIZE : 0u) || !wires_oracle->d_coeffs ||
+                          !wires_oracle->d_lde || !wires_oracle->d_tree)) ||
         (constants_sigmas_oracle &&
          (constants_sigmas_oracle->n_polys != c->num_constants + p->num_routed_wires || constants_sigmas_oracle->n_salt ||
           !constants_sigmas_oracle->d_coeffs || !constants_sigmas_oracle->d_lde || !constants_sigmas_oracle->d_tree)))
-        return sipp_fail(ctx, SIPP_E_BADARG, "plonk: a pre-committed oracle must hold every column of its batch, unsalted");
+        return sipp_fail(ctx, SIPP_E_BADARG, "plonk: a pre-committed oracle must hold every column of its batch, the wires salted under blinding alone");
     uint64_t pih[4];
     host::Challenger::hash_no_pad(public_inputs, n_public_inputs, pih);
     PlonkExtra ex;
     ex.public_inputs = public_inputs; ex.n_public_inputs = n_public_inputs; ex.v2 = true;
     ex.sigmas_oracle = constants_sigmas_oracle; ex.wires_oracle = wires_oracle; ex.wires_cap = wires_cap; ex.circ = c;
     ex.lookup = l.empty() ? nullptr : &l;      // an empty description: "SIPPPLK3", word for word
+    ex.blind = blind;
     return plonk_prove_impl(ctx, d_wires, d_constants_sigmas, log_n, p, fp, circuit_digest, pih, ex, proof_out, proof_cap, proof_len);
 }

@@ -906,6 +906,7 @@ int verify(const uint64_t* proof, size_t len, const sipp_stark_config& cfg) {
 constexpr uint64_t FRI_MAGIC = 0x5349505046524931ULL;    // "SIPPFRI1"
 constexpr uint64_t PLONK_MAGIC3 = 0x334b4c5050504953ULL;  // "SIPPPLK3" (as bytes in memory)
 constexpr uint64_t PLONK_MAGIC4 = 0x344b4c5050504953ULL;  // "SIPPPLK4": header[16] of PLK3, then the eight words of the lookup description
+constexpr uint64_t PLONK_MAGIC5 = 0x354b4c5050504953ULL;  // "SIPPPLK5": header[24] of PLK4 with header[12] = 1: salted oracles (zero knowledge)
 
 FriShape fri_shape_of(const sipp_fri_params& p) {
     FriShape f;
@@ -965,6 +966,8 @@ int fri_openings_verify(const uint64_t* sec, size_t sec_len, const uint64_t* con
 // The three descriptions are read by plonk_desc.hpp, as the prover reads them: the parameters (routed wires needed; no cap on the chunks,
 // and log_n is the proof's own word, stage 202 below), the gate set's structure (the prover's size caps are NOT the verifier's), and with
 // a lookup description its validator -- which does apply the caps on wires and constants, before anything is sized by these words.
+// fp.hiding decides which proof is accepted: 1 = "SIPPPLK5" alone (24 header words, header[12] = 1, the description words zero without
+// `lk`; the wires, zs_partial_products and quotient leaves carry four salt words), 0 = "SIPPPLK3" / "SIPPPLK4" alone.  Else stage 201.
 int plonk_verify(const uint64_t* proof, size_t len, const uint64_t* cs_cap, const sipp_plonk_params& p, const sipp_fri_params& fp,
                  const sipp_plonk_circuit& c, const uint64_t digest[4], const plonk_desc::Lookup* lk) {
     uint32_t log_d, m;
@@ -978,15 +981,17 @@ int plonk_verify(const uint64_t* proof, size_t len, const uint64_t* cs_cap, cons
     for (uint32_t g = 0; g < c.num_gates; g++) ngc = c.gates[g].num_constraints > ngc ? c.gates[g].num_constraints : ngc;
     if (fp.cap_height > 16) return 201;
     const size_t cap_n = (size_t)1 << fp.cap_height;
-    const size_t hw = lk ? 24 : 16;
+    const bool zk = fp.hiding != 0;
+    if (fp.hiding > 1) return 201;
+    const size_t hw = lk || zk ? 24 : 16;
     const uint32_t Jl = lk ? lk->Jl(D) : 0, Jt = lk ? lk->Jt(D) : 0, J = Jl + Jt, nzl = nz + C * J;
-    if (lk) {      // the header's description is the caller's, word for word
+    if (lk || zk) {      // the header's description is the caller's, word for word (all zero without one)
         if (len < hw) return 201;
         for (int q = 0; q < 8; q++)
-            if (proof[16 + q] != plonk_desc::lookup_word(*lk, q)) return 201;
+            if (proof[16 + q] != (lk ? plonk_desc::lookup_word(*lk, q) : 0u)) return 201;
     }
-    if (len < hw + 3 * cap_n * 4 || proof[0] != (lk ? PLONK_MAGIC4 : PLONK_MAGIC3) || proof[2] != R || proof[3] != D || proof[4] != C || proof[5] != len || proof[6] != W ||
-        proof[7] != K || proof[8] != c.num_selectors || proof[9] != c.num_gates || proof[10] != ngc || (proof[12] | proof[13] | proof[14] | proof[15]))
+    if (len < hw + 3 * cap_n * 4 || proof[0] != (zk ? PLONK_MAGIC5 : lk ? PLONK_MAGIC4 : PLONK_MAGIC3) || proof[2] != R || proof[3] != D || proof[4] != C || proof[5] != len || proof[6] != W ||
+        proof[7] != K || proof[8] != c.num_selectors || proof[9] != c.num_gates || proof[10] != ngc || proof[12] != (zk ? 1u : 0u) || (proof[13] | proof[14] | proof[15]))
         return 201;
     const size_t n_pi = (size_t)proof[11];
     if (proof[11] > len - (hw + 3 * cap_n * 4)) return 201;
@@ -1103,7 +1108,7 @@ int plonk_verify(const uint64_t* proof, size_t len, const uint64_t* cs_cap, cons
         if (!gl::eq(van, gl::mul(zh, acc))) return 210;
     }
     const uint64_t* caps[4] = {cs_cap, wcap, zcap, qcap};
-    const uint32_t ncols[4] = {K + R, W, nzl, C * D}, salt[4] = {0, 0, 0, 0};
+    const uint32_t ncols[4] = {K + R, W, nzl, C * D}, zs4 = zk ? SIPP_SALT_SIZE : 0, salt[4] = {0, zs4, zs4, zs4};
     const sipp_poly_range r0[4] = {{0, 0, K + R}, {1, 0, W}, {2, 0, nzl}, {3, 0, C * D}}, r1[2] = {{2, 0, C}, {2, nz, nz + C}};
     const FriBatchV batches[2] = {{zeta, 4, r0}, {gl::scale(zeta, gl::root_of_unity(log_n)), lk ? 2u : 1u, r1}};
     return fri_openings_verify(op, op_len, caps, ncols, salt, 4, batches, 2, log_n, fp, ch);

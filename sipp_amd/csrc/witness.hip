@@ -24,6 +24,8 @@
 // extension elements: a case of run_generator on one lane, wherever the row runs.
 // SIPP_GEN_LOOKUP is the library's own (no upstream gate): a looking row of the lookup argument (lookup.hip) takes its y cells from a dense
 // table in the constant columns, y = f(x) by address, no index; also one lane, wherever the row runs.
+// SIPP_GEN_RANDOM (blinding rows) is NOT computed here: its cells depend on no other cell and cost a whole permutation per eight wires, so
+// blind.hip fills them with a kernel of its own that both entry points launch first; in run_generator the kind does nothing.
 #include "ctx.hpp"
 #include "poseidon_constants.h"
 #include <mutex>
@@ -336,6 +338,7 @@ __device__ __forceinline__ void run_generator(uint64_t* wires, const uint64_t* c
     case SIPP_GEN_LOOKUP:
         lookup_row(wires, consts, n, i, g);
         break;
+    case SIPP_GEN_RANDOM:      // blinding rows depend on no cell: blind.hip has filled them before the first launch of either entry point
     default: break;
     }
 }
@@ -643,6 +646,7 @@ bool layout_ok(const sipp_plonk_generator& g, uint32_t num_wires, uint32_t num_c
     case SIPP_GEN_LOOKUP:
         return g.p[1] >= 1 && g.p[3] >= 1 && (uint64_t)g.p[0] + 2ull * g.p[1] <= nw && (uint64_t)g.p[2] + 2ull * g.p[3] <= num_constants &&
                (uint64_t)g.p[4] + 1 < num_constants;
+    case SIPP_GEN_RANDOM: return (uint64_t)g.p[0] + g.p[1] <= nw;
     case SIPP_GEN_POSEIDON_SWAP: {
         // written cells (out, sbox, delta) must not meet the read cells (in, swap): the two launch paths read and write in different orders
         const uint64_t in = g.p[0], out = g.p[1], sb = g.p[2], sw = g.p[3], dl = g.p[4];
@@ -662,24 +666,28 @@ const char* gen_name(uint32_t kind) {
                                   "witness_random_access", "witness_reducing", "witness_poseidon", "witness_poseidon_swap",
                                   "witness_arithmetic_ext", "witness_exponentiation", "witness_coset_interpolation",
                                   "witness_reducing_ext", "witness_quotient_ext", "witness_base_sum", "witness_poseidon_mds",
-                                  "witness_lookup"};
-    return kind <= SIPP_GEN_LOOKUP ? names[kind] : "witness";
+                                  "witness_lookup", "witness_random"};
+    return kind <= SIPP_GEN_RANDOM ? names[kind] : "witness";
 }
 
 }  // namespace
 
 // argument checks shared by both entry points; uploads this translation unit's round constants when a Poseidon generator is there
 static int witness_prepare(sipp_ctx* ctx, const uint64_t* d_wires, const uint64_t* d_constants, uint32_t log_n, uint32_t num_wires,
-                           uint32_t num_constants, const sipp_plonk_generator* gens, size_t n_gens, const uint64_t* public_inputs_hash) {
+                           uint32_t num_constants, const sipp_plonk_generator* gens, size_t n_gens, const uint64_t* public_inputs_hash,
+                           const sipp_blinding* blind) {
     if (!d_wires || !d_constants || (!gens && n_gens) || log_n < 1 || log_n > 26 || !num_wires || !num_constants)
         return sipp_fail(ctx, SIPP_E_BADARG, "plonk witness: null table, no columns or log_n outside 1 .. 26");
-    bool needs_pih = false, needs_rc = false;
+    bool needs_pih = false, needs_rc = false, needs_blind = false;
     for (size_t k = 0; k < n_gens; k++) {
         if (!layout_ok(gens[k], num_wires, num_constants))
             return sipp_fail(ctx, SIPP_E_BADARG, "plonk witness: a generator's layout leaves the wire table / the constants, or its family is unknown");
         needs_pih |= gens[k].kind == SIPP_GEN_PUBLIC_INPUT;
         needs_rc |= is_poseidon(gens[k].kind);
+        needs_blind |= gens[k].kind == SIPP_GEN_RANDOM;
     }
+    if (needs_blind && !blind) return sipp_fail(ctx, SIPP_E_BADARG, "plonk witness: a Random generator without the blinding seed");
+    if (needs_blind) SIPP_TRY(sipp_blind_check(ctx, blind));
     if (needs_pih && !public_inputs_hash) return sipp_fail(ctx, SIPP_E_BADARG, "plonk witness: a PublicInput generator without the public-inputs hash");
     SIPP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
     if (needs_rc) {      // the round constants of this translation unit, once per device (a blocking copy: complete before any launch below)
@@ -698,10 +706,28 @@ static int witness_prepare(sipp_ctx* ctx, const uint64_t* d_wires, const uint64_
 extern "C" int sipp_plonk_generate_witness(sipp_ctx* ctx, uint64_t* d_wires, const uint64_t* d_constants, uint32_t log_n, uint32_t num_wires,
                                            uint32_t num_constants, const sipp_plonk_generator* gens, size_t n_gens,
                                            const uint64_t public_inputs_hash[4]) {
+    return sipp_plonk_generate_witness_blind(ctx, d_wires, d_constants, log_n, num_wires, num_constants, gens, n_gens, public_inputs_hash, nullptr);
+}
+
+// the rows of every SIPP_GEN_RANDOM generator, in front of everything else on the stream (they read no cell)
+static int blind_rows_all(sipp_ctx* ctx, uint64_t* d_wires, const uint64_t* d_constants, uint32_t log_n, const sipp_plonk_generator* gens,
+                          size_t n_gens, const sipp_blinding* blind) {
+    for (size_t k = 0; k < n_gens; k++)
+        if (gens[k].kind == SIPP_GEN_RANDOM) SIPP_TRY(sipp_blind_rows_launch(ctx, d_wires, d_constants, log_n, gens[k], *blind));
+    return SIPP_OK;
+}
+
+extern "C" int sipp_plonk_generate_witness_blind(sipp_ctx* ctx, uint64_t* d_wires, const uint64_t* d_constants, uint32_t log_n,
+                                                 uint32_t num_wires, uint32_t num_constants, const sipp_plonk_generator* gens, size_t n_gens,
+                                                 const uint64_t public_inputs_hash[4], const uint64_t* blind_words) {
     if (!ctx) return SIPP_E_BADARG;
-    SIPP_TRY(witness_prepare(ctx, d_wires, d_constants, log_n, num_wires, num_constants, gens, n_gens, public_inputs_hash));
+    const BlindArg arg(blind_words);
+    const sipp_blinding* blind = arg.p;
+    SIPP_TRY(witness_prepare(ctx, d_wires, d_constants, log_n, num_wires, num_constants, gens, n_gens, public_inputs_hash, blind));
+    SIPP_TRY(blind_rows_all(ctx, d_wires, d_constants, log_n, gens, n_gens, blind));
     const uint32_t n = 1u << log_n;
     for (size_t k = 0; k < n_gens; k++) {
+        if (gens[k].kind == SIPP_GEN_RANDOM) continue;
         GenArgs a;
         a.wires = d_wires; a.consts = d_constants; a.n = n; a.g = gens[k];
         for (int l = 0; l < 4; l++) a.pih[l] = public_inputs_hash ? public_inputs_hash[l] : 0;
@@ -821,10 +847,20 @@ int witness_levels_run(sipp_ctx* ctx, uint64_t* d_wires, const uint64_t* d_const
 extern "C" int sipp_plonk_generate_witness_levels(sipp_ctx* ctx, uint64_t* d_wires, const uint64_t* d_constants, uint32_t log_n,
                                                   uint32_t num_wires, uint32_t num_constants, const sipp_plonk_generator* gens, size_t n_gens,
                                                   const uint64_t public_inputs_hash[4], const sipp_plonk_schedule* sched) {
+    return sipp_plonk_generate_witness_levels_blind(ctx, d_wires, d_constants, log_n, num_wires, num_constants, gens, n_gens, public_inputs_hash,
+                                                    sched, nullptr);
+}
+
+extern "C" int sipp_plonk_generate_witness_levels_blind(sipp_ctx* ctx, uint64_t* d_wires, const uint64_t* d_constants, uint32_t log_n,
+                                                        uint32_t num_wires, uint32_t num_constants, const sipp_plonk_generator* gens,
+                                                        size_t n_gens, const uint64_t public_inputs_hash[4], const sipp_plonk_schedule* sched,
+                                                        const uint64_t* blind_words) {
     if (!ctx) return SIPP_E_BADARG;
+    const BlindArg arg(blind_words);
+    const sipp_blinding* blind = arg.p;
     // the ceiling first: nothing is launched, copied or uploaded for a circuit past it
     if (n_gens > MAX_GENS) return sipp_fail(ctx, SIPP_E_BADARG, "plonk witness: more than 32 generators (the level kernels carry at most 32)");
-    SIPP_TRY(witness_prepare(ctx, d_wires, d_constants, log_n, num_wires, num_constants, gens, n_gens, public_inputs_hash));
+    SIPP_TRY(witness_prepare(ctx, d_wires, d_constants, log_n, num_wires, num_constants, gens, n_gens, public_inputs_hash, blind));
     if (!sched || !sched->n_levels || sched->n_levels > (1u << 20) || !sched->d_rows || !sched->level_offsets || !sched->copy_offsets)
         return sipp_fail(ctx, SIPP_E_BADARG, "plonk witness: no schedule or no level");
     const uint32_t n = 1u << log_n, L = sched->n_levels;
@@ -833,6 +869,8 @@ extern "C" int sipp_plonk_generate_witness_levels(sipp_ctx* ctx, uint64_t* d_wir
             return sipp_fail(ctx, SIPP_E_BADARG, "plonk witness: schedule offsets must not decrease");
     if (sched->level_offsets[L] > n || (sched->copy_offsets[L] && (!sched->d_copy_src || !sched->d_copy_dst)))
         return sipp_fail(ctx, SIPP_E_BADARG, "plonk witness: more scheduled rows than the table has, or copies without their cell lists");
+    // blinding rows first, outside the captured graph (the seed and counter change from proof to proof, the graph's arguments do not)
+    SIPP_TRY(blind_rows_all(ctx, d_wires, d_constants, log_n, gens, n_gens, blind));
     // a circuit at or below NARROW_GENS launches the kernels, with the arguments, it launched before the ceiling rose
     return n_gens <= NARROW_GENS
                ? witness_levels_run<LevelArgs>(ctx, d_wires, d_constants, log_n, num_wires, num_constants, gens, n_gens, public_inputs_hash, sched)
