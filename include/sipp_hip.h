@@ -796,6 +796,66 @@ int sipp_fri_verify_openings(const uint64_t *proof, size_t len, const uint64_t *
 int sipp_plonk_verify_gates(const uint64_t *proof, size_t len, const uint64_t *constants_sigmas_cap, const sipp_plonk_params *p,
                             const sipp_fri_params *fp, const sipp_plonk_circuit *c, const uint64_t circuit_digest[4], int *reason);
 
+/* ---- KECCAK-256 MERKLE TREES: plonky2's KeccakGoldilocksConfig for the generic commitments and the outer prover ----
+ * The tree hasher is an explicit argument of the _h entries: SIPP_HASH_POSEIDON (0) is the entry without the suffix, byte for byte;
+ * SIPP_HASH_KECCAK25 (1) hashes leaves, nodes and caps with Keccak-256 truncated to 25 bytes (KeccakHash<25>); anything else is
+ * SIPP_E_BADARG.  The challenger, the proof of work and the public-input hash stay Poseidon under either.  The hash, as recalled from
+ * plonky2 hash/keccak.rs:
+ *   keccak256 is original Keccak (rate 136 bytes, padding 0x01 .. 0x80, not SHA-3's 0x06);
+ *   hash_no_pad(elements): every element as its CANONICAL u64, 8 bytes little endian, concatenated; keccak256; the first 25 bytes;
+ *   hash_or_noop(elements): at most 3 elements (24 bytes): the bytes in a zeroed 25-byte array, nothing hashed; else hash_no_pad;
+ *   two_to_one(l, r): keccak256 of the 50 bytes l || r, the first 25 bytes;
+ *   a digest is FOUR u64 words -- bytes 0..6, 7..13, 14..20, 21..24, little endian (BytesHash::to_vec) -- so words 0 - 2 are below 2^56
+ *   and word 3 below 2^32: canonical field elements, observed by the Poseidon challenger like any cap.  Tree layout, cap sizes, proof
+ *   sizes and proof layouts are those of the Poseidon trees (the size functions serve both).  Salt words are leaf elements like any other.
+ * sipp_merkle_leaves_h: hash_or_noop of every leaf, d_lde [ncols][2^log_leaves] leaf order -> d_digests [2^log_leaves][4]; the words
+ *   of d_lde may be any u64 congruent to the element (they are reduced before they are hashed).  log_leaves <= 31 here and below
+ *   (one lane per leaf in one launch): SIPP_E_BADARG beyond.
+ * sipp_merkle_levels_h: the levels above the leaf digests up to the cap (min(cap_height, log_leaves)), cap_out as sipp_merkle_cap.
+ * sipp_fri_leaves_h: the leaves of a FRI layer tree: d_vals [2][len] (c0 row, c1 row; leaf order), leaf k = the 2^arity_bits values
+ *   from k 2^arity_bits, flattened (c0, c1) -> d_digests [len >> arity_bits][4].  Arity 2 (four words) is hashed under Keccak.
+ * sipp_host_keccak256: keccak256 of len bytes on the host, out32 = 32 bytes.  sipp_host_merkle_hash: the host verifier's node functions
+ *   under either hasher (host_tree_hash.hpp, the text verify.cpp climbs paths with; test surface): right == NULL: out4 = hash_or_noop(elements[0 .. n)); else n = 4 and out4 = two_to_one(elements, right).
+ * sipp_commit_batch_h / sipp_fri_prove_openings_h / sipp_fri_verify_openings_h: sipp_commit_batch_ex / sipp_fri_prove_openings /
+ *   sipp_fri_verify_openings with the hasher.  All oracles and all layer trees of one opening proof use one hasher (a tree committed with
+ *   the other fails verification at its Merkle stage).  Under Keccak the verifier refuses (141) a cap or sibling word outside its range
+ *   -- words 0 - 2 at or above 2^56, word 3 at or above 2^32 -- whose high bits the repacking would otherwise drop.
+ * sipp_plonk_prove_gates_h: sipp_plonk_prove_gates_zk (lookup description and blinding words, either may be NULL = none) with the
+ *   hasher; sipp_plonk_verify_gates_h: sipp_plonk_verify_gates_lookup (lookup may be NULL) with the hasher.  The flat "SIPPPLK3/4/5" proof
+ *   records the hasher in header[13] (zero before, zero under Poseidon); the verifier refuses (201) a header[13] that is not its argument.
+ *   Pre-committed oracles must have been committed with the same hasher.
+ * sipp_circuit_build_h: sipp_circuit_build with the hasher; the circuit data remembers it: its constants_sigmas commitment, the three
+ *   prove calls and sipp_circuit_verify follow it.  The derived circuit digest (circuit_digest == NULL) stays the Poseidon hash of the cap
+ *   and the common data (plonky2 would hash it with the tree hasher). */
+#define SIPP_HASH_POSEIDON 0u
+#define SIPP_HASH_KECCAK25 1u
+int sipp_merkle_leaves_h(sipp_ctx *ctx, const uint64_t *d_lde, size_t ncols, uint32_t log_leaves, uint32_t hasher, uint64_t *d_digests);
+int sipp_merkle_levels_h(sipp_ctx *ctx, uint64_t *d_tree, uint32_t log_leaves, uint32_t cap_height, uint32_t hasher, uint64_t *cap_out);
+int sipp_fri_leaves_h(sipp_ctx *ctx, const uint64_t *d_vals, size_t len, uint32_t arity_bits, uint32_t hasher, uint64_t *d_digests);
+int sipp_host_keccak256(const void *bytes, size_t len, void *out32);
+int sipp_host_merkle_hash(uint32_t hasher, const uint64_t *elements, size_t n, const uint64_t *right, uint64_t *out4);
+int sipp_commit_batch_h(sipp_ctx *ctx, const uint64_t *d_in, int from_coeffs, uint64_t *d_coeffs, uint64_t *d_lde,
+                        uint64_t *d_tree, size_t ncols, uint32_t log_n, uint32_t rate_bits, uint32_t cap_height,
+                        const uint64_t *d_salt, uint32_t n_salt, uint32_t hasher, uint64_t *cap_out);
+int sipp_fri_prove_openings_h(sipp_ctx *ctx, const sipp_oracle *oracles, size_t n_oracles, const sipp_fri_batch *batches,
+                              size_t n_batches, uint32_t log_n, const sipp_fri_params *p, uint32_t hasher, sipp_challenger *ch,
+                              uint64_t *proof_out, size_t proof_cap, size_t *proof_len);
+int sipp_fri_verify_openings_h(const uint64_t *proof, size_t len, const uint64_t *const *caps, const uint32_t *ncols, const uint32_t *n_salt,
+                               size_t n_oracles, const sipp_fri_batch *batches, size_t n_batches, uint32_t log_n, const sipp_fri_params *p,
+                               uint32_t hasher, sipp_challenger *ch, int *reason);
+int sipp_plonk_prove_gates_h(sipp_ctx *ctx, const uint64_t *d_wires, const uint64_t *d_constants_sigmas, const sipp_oracle *wires_oracle,
+                             const uint64_t *wires_cap, const sipp_oracle *constants_sigmas_oracle, uint32_t log_n,
+                             const sipp_plonk_params *p, const sipp_fri_params *fp, const sipp_plonk_circuit *c,
+                             const uint64_t circuit_digest[4], const uint64_t *public_inputs, uint32_t n_public_inputs,
+                             const uint32_t *lookup, const uint64_t *blind, uint32_t hasher, uint64_t *proof_out, size_t proof_cap,
+                             size_t *proof_len);
+int sipp_plonk_verify_gates_h(const uint64_t *proof, size_t len, const uint64_t *constants_sigmas_cap, const sipp_plonk_params *p,
+                              const sipp_fri_params *fp, const sipp_plonk_circuit *c, const uint64_t circuit_digest[4],
+                              const uint32_t *lookup, uint32_t hasher, int *reason);
+int sipp_circuit_build_h(sipp_ctx *ctx, uint32_t log_n, const sipp_plonk_params *p, const sipp_fri_params *fp, const sipp_plonk_circuit *c,
+                         const uint64_t *constants_sigmas, const sipp_plonk_generator *gens, size_t n_gens,
+                         const sipp_plonk_schedule_host *sched, const uint64_t *circuit_digest, uint32_t hasher, sipp_circuit_data **out);
+
 /* ---- building blocks (device buffers; used by the parity tests and bench.py) -- */
 /* plonky2 fft()/ifft(): natural order in, natural order out, in place.
  * d_cols is [ncols][col_stride] u64 with the first 2^log_n entries of each column used. */

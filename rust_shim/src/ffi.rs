@@ -36,6 +36,9 @@ pub const SIPP_PAIRING: c_int = 6;
 /// the version of include/sipp_hip.h these bindings were written against (sipp_ctx_create_checked refuses a library of another version)
 pub const SIPP_ABI_VERSION: u32 = 3;
 pub const SIPP_SALT_SIZE: usize = 4;
+/// the tree hasher of the `_h` entries: Poseidon, or Keccak-256 truncated to 25 bytes (plonky2's KeccakGoldilocksConfig)
+pub const SIPP_HASH_POSEIDON: u32 = 0;
+pub const SIPP_HASH_KECCAK25: u32 = 1;
 pub const SIPP_FRI_MAX_ROUNDS: usize = 32;
 
 #[repr(C)]
@@ -338,6 +341,32 @@ extern "C" {
                                      circuit_digest: *const u64, public_inputs: *const u64, n_public_inputs: u32, lookup: *const u32,
                                      blind: *const u64, proof_out: *mut u64, proof_cap: usize, proof_len: *mut usize) -> c_int;
     pub fn sipp_circuit_set_blinding(cd: *mut SippCircuitDataOpaque, seed: *const u64) -> c_int;
+    // Keccak-256 Merkle trees: the tree hasher as an argument
+    pub fn sipp_merkle_leaves_h(ctx: *mut SippCtxOpaque, d_lde: *const u64, ncols: usize, log_leaves: u32, hasher: u32, d_digests: *mut u64) -> c_int;
+    pub fn sipp_merkle_levels_h(ctx: *mut SippCtxOpaque, d_tree: *mut u64, log_leaves: u32, cap_height: u32, hasher: u32, cap_out: *mut u64) -> c_int;
+    pub fn sipp_fri_leaves_h(ctx: *mut SippCtxOpaque, d_vals: *const u64, len: usize, arity_bits: u32, hasher: u32, d_digests: *mut u64) -> c_int;
+    pub fn sipp_host_keccak256(bytes: *const c_void, len: usize, out32: *mut c_void) -> c_int;
+    pub fn sipp_host_merkle_hash(hasher: u32, elements: *const u64, n: usize, right: *const u64, out4: *mut u64) -> c_int;
+    pub fn sipp_commit_batch_h(ctx: *mut SippCtxOpaque, d_in: *const u64, from_coeffs: c_int, d_coeffs: *mut u64, d_lde: *mut u64,
+                               d_tree: *mut u64, ncols: usize, log_n: u32, rate_bits: u32, cap_height: u32, d_salt: *const u64,
+                               n_salt: u32, hasher: u32, cap_out: *mut u64) -> c_int;
+    pub fn sipp_fri_prove_openings_h(ctx: *mut SippCtxOpaque, oracles: *const SippOracle, n_oracles: usize, batches: *const SippFriBatch,
+                                     n_batches: usize, log_n: u32, p: *const SippFriParams, hasher: u32, ch: *mut SippChallenger,
+                                     proof_out: *mut u64, proof_cap: usize, proof_len: *mut usize) -> c_int;
+    pub fn sipp_fri_verify_openings_h(proof: *const u64, len: usize, caps: *const *const u64, ncols: *const u32, n_salt: *const u32, n_oracles: usize,
+                                      batches: *const SippFriBatch, n_batches: usize, log_n: u32, p: *const SippFriParams, hasher: u32,
+                                      ch: *mut SippChallenger, reason: *mut c_int) -> c_int;
+    pub fn sipp_plonk_prove_gates_h(ctx: *mut SippCtxOpaque, d_wires: *const u64, d_constants_sigmas: *const u64,
+                                    wires_oracle: *const SippOracle, wires_cap: *const u64, constants_sigmas_oracle: *const SippOracle,
+                                    log_n: u32, p: *const SippPlonkParams, fp: *const SippFriParams, c: *const SippPlonkCircuit,
+                                    circuit_digest: *const u64, public_inputs: *const u64, n_public_inputs: u32, lookup: *const u32,
+                                    blind: *const u64, hasher: u32, proof_out: *mut u64, proof_cap: usize, proof_len: *mut usize) -> c_int;
+    pub fn sipp_plonk_verify_gates_h(proof: *const u64, len: usize, constants_sigmas_cap: *const u64, p: *const SippPlonkParams,
+                                     fp: *const SippFriParams, c: *const SippPlonkCircuit, circuit_digest: *const u64, lookup: *const u32,
+                                     hasher: u32, reason: *mut c_int) -> c_int;
+    pub fn sipp_circuit_build_h(ctx: *mut SippCtxOpaque, log_n: u32, p: *const SippPlonkParams, fp: *const SippFriParams, c: *const SippPlonkCircuit,
+                                constants_sigmas: *const u64, gens: *const SippPlonkGenerator, n_gens: usize, sched: *const SippPlonkScheduleHost,
+                                circuit_digest: *const u64, hasher: u32, out: *mut *mut SippCircuitDataOpaque) -> c_int;
     pub fn sipp_ntt_batch(ctx: *mut SippCtxOpaque, d_cols: *mut u64, col_stride: usize, ncols: usize, log_n: u32, inverse: c_int) -> c_int;
     pub fn sipp_lde_batch(ctx: *mut SippCtxOpaque, d_values: *const u64, d_coeffs: *mut u64, d_lde: *mut u64, ncols: usize, log_n: u32) -> c_int;
     pub fn sipp_poseidon_leaves(ctx: *mut SippCtxOpaque, d_lde: *const u64, ncols: usize, log_leaves: u32, d_digests: *mut u64) -> c_int;

@@ -226,6 +226,24 @@ SIGNATURES = {
     "sipp_circuit_verify": (C.c_int, [vp, vp, C.c_size_t, C.POINTER(C.c_int)]),
     "sipp_plonk_perm_prove": (C.c_int, [vp, vp, vp, C.c_uint32, C.POINTER(PlonkParams), C.POINTER(FriParams), u64p, u64p, vp, C.c_size_t,
                                         C.POINTER(C.c_size_t)]),
+    # the tree hasher as an argument (Keccak-256 Merkle trees)
+    "sipp_merkle_leaves_h": (C.c_int, [vp, vp, C.c_size_t, C.c_uint32, C.c_uint32, vp]),
+    "sipp_merkle_levels_h": (C.c_int, [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp]),
+    "sipp_fri_leaves_h": (C.c_int, [vp, vp, C.c_size_t, C.c_uint32, C.c_uint32, vp]),
+    "sipp_host_keccak256": (C.c_int, [vp, C.c_size_t, vp]),
+    "sipp_host_merkle_hash": (C.c_int, [C.c_uint32, u64p, C.c_size_t, u64p, u64p]),
+    "sipp_commit_batch_h": (C.c_int, [vp, vp, C.c_int, vp, vp, vp, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_uint32, C.c_uint32, vp]),
+    "sipp_fri_prove_openings_h": (C.c_int, [vp, C.POINTER(Oracle), C.c_size_t, C.POINTER(FriBatch), C.c_size_t, C.c_uint32,
+                                            C.POINTER(FriParams), C.c_uint32, C.POINTER(Challenger), vp, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "sipp_fri_verify_openings_h": (C.c_int, [u64p, C.c_size_t, C.POINTER(u64p), u32p, u32p, C.c_size_t, C.POINTER(FriBatch), C.c_size_t, C.c_uint32,
+                                             C.POINTER(FriParams), C.c_uint32, C.POINTER(Challenger), C.POINTER(C.c_int)]),
+    "sipp_plonk_prove_gates_h": (C.c_int, [vp, vp, vp, C.POINTER(Oracle), u64p, C.POINTER(Oracle), C.c_uint32, C.POINTER(PlonkParams),
+                                           C.POINTER(FriParams), C.POINTER(PlonkCircuit), u64p, u64p, C.c_uint32, u32p, vp, C.c_uint32, vp,
+                                           C.c_size_t, C.POINTER(C.c_size_t)]),
+    "sipp_plonk_verify_gates_h": (C.c_int, [u64p, C.c_size_t, u64p, C.POINTER(PlonkParams), C.POINTER(FriParams), C.POINTER(PlonkCircuit), u64p,
+                                            u32p, C.c_uint32, C.POINTER(C.c_int)]),
+    "sipp_circuit_build_h": (C.c_int, [vp, C.c_uint32, C.POINTER(PlonkParams), C.POINTER(FriParams), C.POINTER(PlonkCircuit), vp,
+                                       C.POINTER(PlonkGenerator), C.c_size_t, C.POINTER(PlonkScheduleHost), u64p, C.c_uint32, C.POINTER(vp)]),
     "sipp_ntt_batch": (C.c_int, [vp, vp, C.c_size_t, C.c_size_t, C.c_uint32, C.c_int]),
     "sipp_lde_batch": (C.c_int, [vp, vp, vp, vp, C.c_size_t, C.c_uint32]),
     "sipp_poseidon_leaves": (C.c_int, [vp, vp, C.c_size_t, C.c_uint32, vp]),
@@ -266,6 +284,83 @@ def lib():
 
 
 SIPP_E_VERIFY = -9
+# the tree hasher of the _h entries (include/sipp_hip.h): Poseidon, or Keccak-256 truncated to 25 bytes (plonky2's KeccakGoldilocksConfig)
+HASH_POSEIDON, HASH_KECCAK25 = 0, 1
+HASHERS = {"poseidon": HASH_POSEIDON, "keccak": HASH_KECCAK25}
+PLONK_HEADER_HASHER_WORD = 13      # of a flat "SIPPPLK3/4/5" proof: 0 under Poseidon, as it always was
+
+
+def hasher_id(hasher):
+    """'poseidon' / 'keccak' (or the number itself) -> the uint32 the C calls take; anything else ValueError"""
+    if isinstance(hasher, str):
+        if hasher not in HASHERS:
+            raise ValueError("hasher must be 'poseidon' or 'keccak', not %r" % (hasher,))
+        return HASHERS[hasher]
+    return int(hasher)
+
+
+def plonk_proof_hasher(proof):
+    """the tree hasher a flat "SIPPPLK3/4/5" proof names in its header"""
+    return int(np.asarray(proof, dtype=np.uint64)[PLONK_HEADER_HASHER_WORD])
+
+
+def refuse_keccak_proof(proof, who):
+    """the recursion circuits verify Poseidon trees only: a proof whose header names another hasher is refused before anything is launched"""
+    pf = np.asarray(proof, dtype=np.uint64).reshape(-1)
+    if len(pf) > PLONK_HEADER_HASHER_WORD and int(pf[PLONK_HEADER_HASHER_WORD]) != HASH_POSEIDON:
+        raise ValueError("%s: the proof's Merkle trees are hashed with hasher %d (header word %d); the circuit verifies Poseidon trees only"
+                         % (who, int(pf[PLONK_HEADER_HASHER_WORD]), PLONK_HEADER_HASHER_WORD))
+
+
+def host_keccak256(data):
+    """sipp_host_keccak256: Keccak-256 (original padding) of a bytes object on the host -> 32 bytes"""
+    data = bytes(data)
+    out = C.create_string_buffer(32)
+    rc = lib().sipp_host_keccak256(C.c_char_p(data) if data else None, len(data), out)
+    if rc:
+        raise SippError(rc, "sipp_host_keccak256")
+    return out.raw
+
+
+def host_merkle_hash(hasher, elements, right=None):
+    """sipp_host_merkle_hash: the host verifier's hash_or_noop(elements), or two_to_one(elements, right) of two digests -> four words"""
+    e = np.ascontiguousarray(elements, dtype=np.uint64).reshape(-1)
+    r = None if right is None else np.ascontiguousarray(right, dtype=np.uint64).reshape(-1)
+    out = np.zeros(4, dtype=np.uint64)
+    rc = lib().sipp_host_merkle_hash(hasher_id(hasher), e.ctypes.data_as(u64p) if len(e) else None, len(e),
+                                     None if r is None else r.ctypes.data_as(u64p), out.ctypes.data_as(u64p))
+    if rc:
+        raise SippError(rc, "sipp_host_merkle_hash")
+    return out
+
+
+def plonk_verify_gates_h(proof, constants_sigmas_cap, p, fp, circuit, digest, lookup, hasher):
+    """sipp_plonk_verify_gates_h: plonk_verify_gates_lookup (lookup may be None) with the tree hasher.  Returns 0 or the refusing stage."""
+    pf = np.ascontiguousarray(proof, dtype=np.uint64)
+    cap = np.ascontiguousarray(constants_sigmas_cap, dtype=np.uint64).reshape(-1)
+    reason = C.c_int(0)
+    rc = lib().sipp_plonk_verify_gates_h(pf.ctypes.data_as(u64p), len(pf), cap.ctypes.data_as(u64p), C.byref(p), C.byref(fp), C.byref(circuit),
+                                         (C.c_uint64 * 4)(*[int(x) for x in digest]), None if lookup is None else Ctx._lookup_words(lookup),
+                                         hasher_id(hasher), C.byref(reason))
+    if rc not in (0, SIPP_E_VERIFY):
+        raise SippError(rc, "sipp_plonk_verify_gates_h")
+    return reason.value
+
+
+def fri_verify_openings_h(proof, caps, ncols, n_salt, batches, log_n, params, challenger, hasher):
+    """sipp_fri_verify_openings_h: caps = one array per oracle, batches as Ctx.fri_prove_openings takes them; `challenger` is advanced in
+    place.  Returns 0 or the refusing stage."""
+    pf = np.ascontiguousarray(proof, dtype=np.uint64)
+    keep = [np.ascontiguousarray(c, dtype=np.uint64).reshape(-1) for c in caps]
+    cp = (u64p * len(keep))(*[k.ctypes.data_as(u64p) for k in keep])
+    ba, keep2 = Ctx._batches(batches)
+    reason = C.c_int(0)
+    rc = lib().sipp_fri_verify_openings_h(pf.ctypes.data_as(u64p), len(pf), cp, (C.c_uint32 * len(keep))(*[int(x) for x in ncols]),
+                                          (C.c_uint32 * len(keep))(*[int(x) for x in n_salt]), len(keep), ba, len(batches), log_n,
+                                          C.byref(params), hasher_id(hasher), C.byref(challenger), C.byref(reason))
+    if rc not in (0, SIPP_E_VERIFY):
+        raise SippError(rc, "sipp_fri_verify_openings_h")
+    return reason.value
 
 
 def plonk_verify_gates_lookup(proof, constants_sigmas_cap, p, fp, circuit, digest, lookup):
@@ -395,6 +490,26 @@ class Ctx:
         self._ck(self.L.sipp_merkle_cap(self.h, tree.data_ptr(), log_leaves, cap.ctypes.data), "merkle_cap")
         return cap
 
+    def merkle_leaves_h(self, lde, log_leaves, hasher):
+        """sipp_merkle_leaves_h: lde [ncols, 2^log_leaves] device int64 (leaf order) -> digests [2^log_leaves, 4]"""
+        import torch
+        dig = torch.empty(((1 << log_leaves), 4), dtype=torch.int64, device=lde.device)
+        self._ck(self.L.sipp_merkle_leaves_h(self.h, lde.data_ptr(), lde.shape[0], log_leaves, hasher_id(hasher), dig.data_ptr()), "merkle_leaves_h")
+        return dig
+
+    def merkle_levels_h(self, tree, log_leaves, cap_height, hasher):
+        """sipp_merkle_levels_h: tree [2 << log_leaves, 4] device int64 with the leaf digests in front, completed in place -> the cap"""
+        cap = np.zeros((1 << min(cap_height, log_leaves), 4), dtype=np.uint64)
+        self._ck(self.L.sipp_merkle_levels_h(self.h, tree.data_ptr(), log_leaves, cap_height, hasher_id(hasher), cap.ctypes.data), "merkle_levels_h")
+        return cap
+
+    def fri_leaves_h(self, vals, arity_bits, hasher):
+        """sipp_fri_leaves_h: vals [2, len] device int64 (c0 row, c1 row) -> digests [len >> arity_bits, 4]"""
+        import torch
+        dig = torch.empty((vals.shape[1] >> arity_bits, 4), dtype=torch.int64, device=vals.device)
+        self._ck(self.L.sipp_fri_leaves_h(self.h, vals.data_ptr(), vals.shape[1], arity_bits, hasher_id(hasher), dig.data_ptr()), "fri_leaves_h")
+        return dig
+
     def commit(self, values, log_n, bufs=None):
         """PolynomialBatch::from_values on device.  Returns (coeffs, lde, tree, cap)."""
         import torch
@@ -414,8 +529,9 @@ class Ctx:
         return coeffs, lde, tree, cap
 
     # ---- generic PolynomialBatch / FRI opening proofs ----
-    def commit_ex(self, data, log_n, rate_bits, cap_height, from_coeffs=False, salt=None):
+    def commit_ex(self, data, log_n, rate_bits, cap_height, from_coeffs=False, salt=None, hasher=None):
         """sipp_commit_batch_ex: data [ncols, N] device int64 (values or coefficients), salt [4, N << rate_bits] or None.
+        hasher: None = that call; 'poseidon' / 'keccak' = sipp_commit_batch_h.
         Returns (Oracle struct, cap ndarray, (coeffs, lde, tree) tensors kept alive by the caller)."""
         import torch
         ncols = data.shape[0]
@@ -426,15 +542,17 @@ class Ctx:
         tree = torch.empty((2 * m, 4), dtype=torch.int64, device=data.device)
         ch = min(cap_height, log_n + rate_bits)
         cap = np.zeros((1 << ch, 4), dtype=np.uint64)
-        self._ck(self.L.sipp_commit_batch_ex(self.h, data.data_ptr(), int(from_coeffs), coeffs.data_ptr(), lde.data_ptr(), tree.data_ptr(),
-                                             ncols, log_n, rate_bits, cap_height, None if salt is None else salt.data_ptr(), n_salt,
-                                             cap.ctypes.data), "commit_batch_ex")
+        head = [self.h, data.data_ptr(), int(from_coeffs), coeffs.data_ptr(), lde.data_ptr(), tree.data_ptr(), ncols, log_n, rate_bits, cap_height,
+                None if salt is None else salt.data_ptr(), n_salt]
+        if hasher is None:
+            self._ck(self.L.sipp_commit_batch_ex(*head, cap.ctypes.data), "commit_batch_ex")
+        else:
+            self._ck(self.L.sipp_commit_batch_h(*head, hasher_id(hasher), cap.ctypes.data), "commit_batch_h")
         return Oracle(coeffs.data_ptr(), lde.data_ptr(), tree.data_ptr(), ncols, n_salt), cap, (coeffs, lde, tree)
 
-    def fri_prove_openings(self, oracles, batches, log_n, params, challenger):
-        """sipp_fri_prove_openings.  oracles: [Oracle], batches: [((c0, c1), [(oracle, col_begin, col_end), ...])];
-        `challenger` (Challenger struct) is advanced in place.  Returns the flat proof."""
-        oa = (Oracle * len(oracles))(*oracles)
+    @staticmethod
+    def _batches(batches):
+        """[((c0, c1), [(oracle, col_begin, col_end), ...])] -> (FriBatch array, what must stay alive beside it)"""
         ba = (FriBatch * len(batches))()
         keep = []
         for i, (pt, ranges) in enumerate(batches):
@@ -443,13 +561,25 @@ class Ctx:
             ba[i].point[0], ba[i].point[1] = int(pt[0]), int(pt[1])
             ba[i].n_ranges = len(ranges)
             ba[i].ranges = r
+        return ba, keep
+
+    def fri_prove_openings(self, oracles, batches, log_n, params, challenger, hasher=None):
+        """sipp_fri_prove_openings.  oracles: [Oracle], batches: [((c0, c1), [(oracle, col_begin, col_end), ...])];
+        `challenger` (Challenger struct) is advanced in place.  hasher: None = that call; 'poseidon' / 'keccak' =
+        sipp_fri_prove_openings_h (the oracles' trees committed with the same one).  Returns the flat proof."""
+        oa = (Oracle * len(oracles))(*oracles)
+        ba, keep = self._batches(batches)
         cap = self.L.sipp_fri_proof_size(oa, len(oracles), ba, len(batches), log_n, C.byref(params))
         if cap == 0:
             raise SippError(-1, "sipp_fri_proof_size")
         out = np.zeros(cap, dtype=np.uint64)
         n = C.c_size_t()
-        self._ck(self.L.sipp_fri_prove_openings(self.h, oa, len(oracles), ba, len(batches), log_n, C.byref(params),
-                                                C.byref(challenger), out.ctypes.data, cap, C.byref(n)), "fri_prove_openings")
+        if hasher is None:
+            self._ck(self.L.sipp_fri_prove_openings(self.h, oa, len(oracles), ba, len(batches), log_n, C.byref(params),
+                                                    C.byref(challenger), out.ctypes.data, cap, C.byref(n)), "fri_prove_openings")
+        else:
+            self._ck(self.L.sipp_fri_prove_openings_h(self.h, oa, len(oracles), ba, len(batches), log_n, C.byref(params), hasher_id(hasher),
+                                                      C.byref(challenger), out.ctypes.data, cap, C.byref(n)), "fri_prove_openings_h")
         return out[: n.value]
 
     # ---- plonky2's wire permutation argument ----
@@ -592,6 +722,17 @@ class Ctx:
         cap = self.L.sipp_plonk_gates_zk_proof_size(log_n, C.byref(p), C.byref(fp), C.byref(circuit), len(pis), words)
         return self._plonk_prove("plonk_prove_gates_zk", "sipp_plonk_gates_zk_proof_size", cap, wires, constants_sigmas, wires_oracle, wires_cap,
                                  cs_oracle, log_n, p, fp, circuit, digest, pis, [words, None if blind is None else C.byref(blind)])
+
+    def plonk_prove_gates_h(self, wires, constants_sigmas, log_n, p, fp, circuit, digest, public_inputs, lookup, blind, hasher, wires_oracle=None,
+                            wires_cap=None, cs_oracle=None):
+        """sipp_plonk_prove_gates_h: plonk_prove_gates_zk (lookup and blind may each be None) with the tree hasher 'poseidon' / 'keccak';
+        pre-committed oracles must have been committed with the same one.  The proof names the hasher in header word 13."""
+        pis = [int(x) for x in public_inputs]
+        words = self._lookup_words(lookup if lookup is not None else (0,) * 8)
+        cap = self.L.sipp_plonk_gates_zk_proof_size(log_n, C.byref(p), C.byref(fp), C.byref(circuit), len(pis), words)
+        return self._plonk_prove("plonk_prove_gates_h", "sipp_plonk_gates_zk_proof_size", cap, wires, constants_sigmas, wires_oracle, wires_cap,
+                                 cs_oracle, log_n, p, fp, circuit, digest, pis,
+                                 [None if lookup is None else words, None if blind is None else C.byref(blind), hasher_id(hasher)])
 
     def blind_salt(self, lde, ncols, log_m, blind, stream):
         """sipp_blind_salt: the four salt columns of stream 1 .. 3 behind the ncols polynomial columns of lde [ncols + 4, 2^log_m] (device
@@ -880,16 +1021,20 @@ class CircuitData:
     src/verifier_circuit.rs:225, :253, :254): the gate set, the generators with their level schedule and the constants_sigmas values go in
     once; prove() takes the wire table with its input cells set and the public inputs, both numpy, and returns the flat proof."""
 
-    def __init__(self, ctx, log_n, params, fri, circuit, constants_sigmas, gens, sched=None, digest=None):
+    def __init__(self, ctx, log_n, params, fri, circuit, constants_sigmas, gens, sched=None, digest=None, hasher=None):
+        """hasher: None = sipp_circuit_build; 'poseidon' / 'keccak' = sipp_circuit_build_h (the data's commitment, proofs and verify follow it)"""
         self.ctx, self.L = ctx, ctx.L                      # the ctx must outlive this object
         self.circuit, self.params, self.fri = circuit, params, fri
         cs = np.ascontiguousarray(constants_sigmas, dtype=np.uint64)
         arr = (PlonkGenerator * max(1, len(gens)))(*[PlonkGenerator(int(g[0]), int(g[1]), int(g[2]), (C.c_uint32 * 5)(*[int(x) for x in g[3:8]])) for g in gens])
         self._sched = None if sched is None else PlonkScheduleHost.from_dict(sched)
         h = C.c_void_p()
-        rc = self.L.sipp_circuit_build(ctx.h, log_n, C.byref(params), C.byref(fri), C.byref(circuit), cs.ctypes.data, arr, len(gens),
-                                       None if self._sched is None else C.byref(self._sched),
-                                       None if digest is None else ctx._u64([int(x) for x in digest]), C.byref(h))
+        head = [ctx.h, log_n, C.byref(params), C.byref(fri), C.byref(circuit), cs.ctypes.data, arr, len(gens),
+                None if self._sched is None else C.byref(self._sched), None if digest is None else ctx._u64([int(x) for x in digest])]
+        if hasher is None:
+            rc = self.L.sipp_circuit_build(*head, C.byref(h))
+        else:
+            rc = self.L.sipp_circuit_build_h(*head, hasher_id(hasher), C.byref(h))
         ctx._ck(rc, "circuit_build")
         self.h, self.num_wires, self.n = h, circuit.num_wires, 1 << log_n
         cap = np.zeros(((1 << min(fri.cap_height, log_n + fri.rate_bits)), 4), dtype=np.uint64)

@@ -625,12 +625,18 @@ class CircuitProver:
     """A circuit through the library's CircuitData (sipp_circuit_build / _prove / _verify): the constants_sigmas commitment and the schedule
     go to the device once; prove(inputs) generates the witness there and returns the flat proof."""
 
-    def __init__(self, ctx, circ, fri=None, params=None, digest=None, zero_knowledge=False, seed=None):
-        """zero_knowledge: prove under fri.hiding = 1 -- salted oracles, and the circuit's blinding rows filled from `seed` (four canonical
+    def __init__(self, ctx, circ, fri=None, params=None, digest=None, zero_knowledge=False, seed=None, hasher="poseidon"):
+        """hasher: "poseidon" (default: the circuit data as it always was) or "keccak" -- every Merkle tree of the commitment and of the
+        proofs hashed with Keccak-256 truncated to 25 bytes (plonky2's KeccakGoldilocksConfig; the challenger stays Poseidon); it combines
+        with zero_knowledge and with lookups.  ValueError for anything else.
+        zero_knowledge: prove under fri.hiding = 1 -- salted oracles, and the circuit's blinding rows filled from `seed` (four canonical
         words; None: drawn from `secrets`), proof k under the seed with counter k.  ValueError if the FRI parameters need more blinding
         rows than the circuit carries (CircuitBuilder.declare_blinding)."""
         from . import _lib
         self.circ = c = circ
+        if hasher not in _lib.HASHERS:
+            raise ValueError("hasher must be 'poseidon' or 'keccak', not %r" % (hasher,))
+        self.hasher = hasher
         self.params = params if params is not None else _lib.PlonkParams(c.num_routed, 8, 2)
         self.fri = fri if fri is not None else fri_params(c.log_n)
         if zero_knowledge:
@@ -643,7 +649,7 @@ class CircuitProver:
         self.circuit = c.circuit()
         self._pc = _lib.PlonkCircuit.from_dict(self.circuit)
         self.data = _lib.CircuitData(ctx, c.log_n, self.params, self.fri, self._pc, c.constants_sigmas(), c.generators(), sched=c.schedule(),
-                                     digest=digest)
+                                     digest=digest, hasher=None if hasher == "poseidon" else hasher)
         if "lookup" in self.circuit:      # the description rides in circuit(): the multiplicities and the argument on every prove path
             self.data.set_lookup(self.circuit["lookup"])
         if zero_knowledge:

@@ -4,6 +4,7 @@
 #include <string>
 
 #include "commit.hpp"
+#include "host_tree_hash.hpp"
 #include "host_poseidon.hpp"
 
 int sipp_poseidon_init_constants(sipp_ctx* ctx);  // poseidon.hip
@@ -297,6 +298,45 @@ int sipp_commit_batch(sipp_ctx* ctx, const uint64_t* d_values, uint64_t* d_coeff
     SIPP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
     return commit_batch(ctx, CommitParams{ctx->cfg.rate_bits, ctx->cfg.cap_height}, d_values, false, d_coeffs, d_lde, d_tree, ncols, log_n,
                         cap_out);
+}
+
+// ---- the tree hasher as an argument (keccak.hip; SIPP_HASH_POSEIDON = the two calls above with an explicit cap height) ----
+int sipp_merkle_leaves_h(sipp_ctx* ctx, const uint64_t* d_lde, size_t ncols, uint32_t log_leaves, uint32_t hasher, uint64_t* d_digests) {
+    if (!ctx || !d_lde || !d_digests || log_leaves > 31) return SIPP_E_BADARG;
+    SIPP_TRY(sipp_hasher_check(ctx, hasher));
+    SIPP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    SIPP_TRY(sipp_k_tree_leaves(ctx, hasher, d_lde, (size_t)1 << log_leaves, ncols, log_leaves, d_digests));
+    return sipp_sync(ctx);
+}
+
+int sipp_merkle_levels_h(sipp_ctx* ctx, uint64_t* d_tree, uint32_t log_leaves, uint32_t cap_height, uint32_t hasher, uint64_t* cap_out) {
+    if (!ctx || !d_tree || !cap_out || log_leaves > 31) return SIPP_E_BADARG;
+    SIPP_TRY(sipp_hasher_check(ctx, hasher));
+    SIPP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    SIPP_TRY(sipp_k_tree_levels(ctx, hasher, d_tree, log_leaves, cap_height));
+    return read_cap(ctx, d_tree, log_leaves, cap_height, cap_out);
+}
+
+int sipp_fri_leaves_h(sipp_ctx* ctx, const uint64_t* d_vals, size_t len, uint32_t arity_bits, uint32_t hasher, uint64_t* d_digests) {
+    if (!ctx || !d_vals || !d_digests || len == 0 || (len & (len - 1))) return SIPP_E_BADARG;
+    SIPP_TRY(sipp_hasher_check(ctx, hasher));
+    if (arity_bits < 1 || arity_bits > 4 || (len >> arity_bits) == 0) return sipp_fail(ctx, SIPP_E_BADARG, "fri_leaves: arity 2 .. 16, at least one leaf");
+    SIPP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    SIPP_TRY(sipp_k_tree_fri_leaves(ctx, hasher, d_vals, len, arity_bits, d_digests));
+    return sipp_sync(ctx);
+}
+
+int sipp_host_keccak256(const void* bytes, size_t len, void* out32) {
+    if ((!bytes && len) || !out32) return SIPP_E_BADARG;
+    keccak::keccak256(static_cast<const uint8_t*>(bytes), len, static_cast<uint8_t*>(out32));
+    return SIPP_OK;
+}
+
+int sipp_host_merkle_hash(uint32_t hasher, const uint64_t* elements, size_t n, const uint64_t* right, uint64_t* out4) {
+    if (!out4 || (!elements && n) || hasher > SIPP_HASH_KECCAK25 || (right && n != 4) || n > 0xffffffffull) return SIPP_E_BADARG;
+    if (right) host::tree_two_to_one(hasher, elements, right, out4);
+    else host::tree_hash_or_noop(hasher, elements, n, out4);
+    return SIPP_OK;
 }
 
 int sipp_host_poseidon_permute(uint64_t* states, size_t n, int impl) {

@@ -40,6 +40,8 @@ struct sipp_circuit_data {
     // zero knowledge (a hiding fp): the seed of sipp_circuit_set_blinding and the number of the next proof under it
     sipp_blinding blind{};
     bool has_blind = false;
+    // the tree hasher of sipp_circuit_build_h: of the constants_sigmas commitment below and of every proof and verification
+    uint32_t hasher = SIPP_HASH_POSEIDON;
     ~sipp_circuit_data() {
         if (ctx) (void)hipSetDevice(ctx->device);
         for (void* q : dev) (void)hipFree(q);
@@ -113,8 +115,16 @@ extern "C" void sipp_circuit_destroy(sipp_circuit_data* cd) {
 extern "C" int sipp_circuit_build(sipp_ctx* ctx, uint32_t log_n, const sipp_plonk_params* p, const sipp_fri_params* fp, const sipp_plonk_circuit* c,
                                   const uint64_t* constants_sigmas, const sipp_plonk_generator* gens, size_t n_gens,
                                   const sipp_plonk_schedule_host* sched, const uint64_t* circuit_digest, sipp_circuit_data** out) {
+    return sipp_circuit_build_h(ctx, log_n, p, fp, c, constants_sigmas, gens, n_gens, sched, circuit_digest, SIPP_HASH_POSEIDON, out);
+}
+
+extern "C" int sipp_circuit_build_h(sipp_ctx* ctx, uint32_t log_n, const sipp_plonk_params* p, const sipp_fri_params* fp, const sipp_plonk_circuit* c,
+                                    const uint64_t* constants_sigmas, const sipp_plonk_generator* gens, size_t n_gens,
+                                    const sipp_plonk_schedule_host* sched, const uint64_t* circuit_digest, uint32_t hasher,
+                                    sipp_circuit_data** out) {
     if (out) *out = nullptr;
     if (!ctx) return SIPP_E_BADARG;
+    SIPP_TRY(sipp_hasher_check(ctx, hasher));
     if (!out || !p || !fp || !c || !constants_sigmas || (!gens && n_gens) || log_n < 1 || log_n > 24 || !c->gates || (!c->programs && c->program_words) ||
         !c->num_gates || c->num_wires < p->num_routed_wires)
         return sipp_fail(ctx, SIPP_E_BADARG, "circuit build: null argument, log_n outside 1 .. 24 or an empty circuit");
@@ -132,7 +142,7 @@ extern "C" int sipp_circuit_build(sipp_ctx* ctx, uint32_t log_n, const sipp_plon
     sipp_circuit_data* cd = nullptr;
     try {
         owner.reset(cd = new sipp_circuit_data());
-        cd->ctx = ctx; cd->log_n = log_n; cd->p = *p; cd->fp = *fp;
+        cd->ctx = ctx; cd->log_n = log_n; cd->p = *p; cd->fp = *fp; cd->hasher = hasher;
         cd->gates.assign(c->gates, c->gates + c->num_gates);
         cd->programs.assign(c->programs, c->programs + c->program_words);
         cd->gens.assign(gens, gens + n_gens);
@@ -170,7 +180,7 @@ extern "C" int sipp_circuit_build(sipp_ctx* ctx, uint32_t log_n, const sipp_plon
     SIPP_TRY(dev_alloc(cd, 2 * m * 4, &d_tree));
     const uint32_t ch = fp->cap_height < log_n + fp->rate_bits ? fp->cap_height : log_n + fp->rate_bits;
     cd->cap.assign(((size_t)4) << ch, 0);
-    SIPP_TRY(sipp_commit_batch_ex(ctx, cd->d_cs, 0, d_coeffs, d_lde, d_tree, ncols, log_n, fp->rate_bits, fp->cap_height, nullptr, 0, cd->cap.data()));
+    SIPP_TRY(sipp_commit_batch_h(ctx, cd->d_cs, 0, d_coeffs, d_lde, d_tree, ncols, log_n, fp->rate_bits, fp->cap_height, nullptr, 0, hasher, cd->cap.data()));
     SIPP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     cd->cs_oracle.d_coeffs = d_coeffs; cd->cs_oracle.d_lde = d_lde; cd->cs_oracle.d_tree = d_tree;
     cd->cs_oracle.n_polys = (uint32_t)ncols; cd->cs_oracle.n_salt = 0;
@@ -230,6 +240,11 @@ int prove_uploaded(sipp_circuit_data* cd, const uint64_t* blind, const uint64_t*
     else
         SIPP_TRY(sipp_plonk_generate_witness_blind(ctx, cd->d_wires, cd->d_cs, cd->log_n, cd->circ.num_wires, cd->circ.num_constants,
                                                    cd->gens.data(), cd->gens.size(), pih, blind));
+    if (cd->hasher != SIPP_HASH_POSEIDON) {      // the one entry that takes a hasher serves all four kinds of proof
+        if (!cd->lk.empty()) SIPP_TRY(sipp_lookup_multiplicities_indexed(ctx, cd->d_wires, cd->d_cs, cd->log_n, cd->lk, cd->d_index, cd->n_index));
+        return sipp_plonk_prove_gates_h(ctx, cd->d_wires, cd->d_cs, nullptr, nullptr, &cd->cs_oracle, cd->log_n, &cd->p, &cd->fp, &cd->circ,
+                                        cd->digest, public_inputs, n_public_inputs, cd->lookup, blind, cd->hasher, proof_out, proof_cap, proof_len);
+    }
     if (blind) {
         if (!cd->lk.empty()) SIPP_TRY(sipp_lookup_multiplicities_indexed(ctx, cd->d_wires, cd->d_cs, cd->log_n, cd->lk, cd->d_index, cd->n_index));
         return sipp_plonk_prove_gates_zk(ctx, cd->d_wires, cd->d_cs, nullptr, nullptr, &cd->cs_oracle, cd->log_n, &cd->p, &cd->fp, &cd->circ,
@@ -411,5 +426,5 @@ extern "C" int sipp_circuit_prove_words(sipp_circuit_data* cd, const uint64_t* w
 
 extern "C" int sipp_circuit_verify(const sipp_circuit_data* cd, const uint64_t* proof, size_t len, int* reason) {
     if (!cd) return SIPP_E_BADARG;
-    return sipp_plonk_verify_gates_lookup(proof, len, cd->cap.data(), &cd->p, &cd->fp, &cd->circ, cd->digest, cd->lookup, reason);
+    return sipp_plonk_verify_gates_h(proof, len, cd->cap.data(), &cd->p, &cd->fp, &cd->circ, cd->digest, cd->lookup, cd->hasher, reason);
 }

@@ -1,4 +1,4 @@
-// sipp_amd/csrc/commit.hip -- see commit.hpp.  Host code only: the kernels are ntt.hip's, ntt_tree.hip's and poseidon.hip's.
+// sipp_amd/csrc/commit.hip -- see commit.hpp.  Host code only: the kernels are ntt.hip's, ntt_tree.hip's, poseidon.hip's and keccak.hip's.
 #include <algorithm>
 
 #include "commit.hpp"
@@ -38,8 +38,8 @@ int commit_launch(sipp_ctx* ctx, const CommitParams& cp, const uint64_t* d_in, b
     SIPP_TRY(commit_lde(ctx, d_in, from_coeffs, d_coeffs, d_lde, ncols, log_n, cp.rate_bits));
     // salt columns: natural LDE order in, leaf order (= bit-reversed rows) behind the polynomial columns -- unless they are there already
     if (cp.n_salt && !cp.salt_in_place) SIPP_TRY(sipp_bitrev_cols(ctx, cp.d_salt, m, d_lde + ncols * m, m, log_m, cp.n_salt));
-    SIPP_TRY(sipp_k_poseidon_leaves(ctx, d_lde, m, ncols + cp.n_salt, log_m, d_tree));
-    return sipp_k_merkle_levels(ctx, d_tree, log_m, cp.cap_height);
+    SIPP_TRY(sipp_k_tree_leaves(ctx, cp.hasher, d_lde, m, ncols + cp.n_salt, log_m, d_tree));
+    return sipp_k_tree_levels(ctx, cp.hasher, d_tree, log_m, cp.cap_height);
 }
 
 int read_cap(sipp_ctx* ctx, const uint64_t* d_tree, uint32_t log_leaves, uint32_t cap_height, uint64_t* cap_host) {

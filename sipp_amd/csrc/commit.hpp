@@ -1,5 +1,5 @@
 // sipp_amd/csrc/commit.hpp -- committing a PolynomialBatch (plonky2 fri/oracle.rs from_values / from_coeffs): values -> coefficients
-// -> coset LDE -> Poseidon leaves -> Merkle levels -> cap.  The ONE host path of the STARK prover (stark.hip), the building-block
+// -> coset LDE -> leaves (Poseidon, or Keccak where the caller names it) -> Merkle levels -> cap.  The ONE host path of the STARK prover (stark.hip), the building-block
 // ABI (api.hip) and the generic commitments of the outer prover and CircuitData (fri.hip sipp_commit_batch_ex).  The callers keep what
 // is theirs: argument checks, hipSetDevice, and whether they synchronise after a failure.
 #pragma once
@@ -13,6 +13,7 @@ struct CommitParams {
     uint32_t n_salt = 0;
     // the n_salt columns already sit behind the polynomial columns of d_lde, in LEAF order (blind.hip filled them): d_salt is not read
     bool salt_in_place = false;
+    uint32_t hasher = SIPP_HASH_POSEIDON;   // the tree hasher (keccak.hip: sipp_k_tree_leaves / sipp_k_tree_levels); 0 = the Poseidon launches
 };
 
 // u64 words of a Merkle tree over 2^log_leaves leaves, levels back to back: 2 * leaves * 4

@@ -257,6 +257,16 @@ int sipp_k_poseidon_leaves(sipp_ctx* ctx, const uint64_t* d_lde, size_t col_stri
                            uint64_t* d_digests);
 int sipp_k_merkle_levels(sipp_ctx* ctx, uint64_t* d_tree, uint32_t log_leaves, uint32_t cap_height);
 int sipp_k_poseidon_permute(sipp_ctx* ctx, uint64_t* d_states, size_t n);
+// the tree hasher of an _h entry: SIPP_OK, or SIPP_E_BADARG with the one message (every entry and every launcher asks here)
+inline int sipp_hasher_check(sipp_ctx* ctx, uint32_t hasher) {
+    return hasher <= SIPP_HASH_KECCAK25 ? SIPP_OK : sipp_fail(ctx, SIPP_E_BADARG, "hasher: 0 (Poseidon) or 1 (Keccak-256 truncated to 25 bytes)");
+}
+// keccak.hip: the tree hasher as an argument (SIPP_HASH_POSEIDON: the Poseidon launches above and prover.hpp's sipp_k_fri_leaves, unchanged;
+// SIPP_HASH_KECCAK25: the Keccak kernels; anything else SIPP_E_BADARG) -- leaves over an LDE, FRI layer leaves, levels to the cap
+int sipp_k_tree_leaves(sipp_ctx* ctx, uint32_t hasher, const uint64_t* d_lde, size_t col_stride, size_t ncols, uint32_t log_leaves,
+                       uint64_t* d_digests);
+int sipp_k_tree_fri_leaves(sipp_ctx* ctx, uint32_t hasher, const uint64_t* d_vals, size_t len, uint32_t arity_bits, uint64_t* d_digests);
+int sipp_k_tree_levels(sipp_ctx* ctx, uint32_t hasher, uint64_t* d_tree, uint32_t log_leaves, uint32_t cap_height);
 void sipp_witness_graph_release(sipp_ctx* ctx);   // witness.hip
 int sipp_plonk_circuit_check(sipp_ctx* ctx, const sipp_plonk_circuit* c, const sipp_plonk_params* p);   // plonk.hip
 // lookup.hip -- a lookup description is the eight words of include/sipp_hip.h, read ONCE into plonk_desc::Lookup.  _check: that reading

@@ -58,8 +58,8 @@ int sipp_fri_prove_core(sipp_ctx* ctx, const FriOracleDev* ors, int n_oracles, u
         if (!r_vals[r] || !r_tree[r] || !nxt) return SIPP_E_NOMEM;
         // coset NTT of the current polynomial (len_c = len >> rate_bits coefficients, zero padded to len)
         SIPP_TRY(sipp_ntt_dif(ctx, cur, len_c, log_len - p.rate_bits, r_vals[r], len, log_len, 2, false, NttDiag{shift, 0}));
-        SIPP_TRY(sipp_k_fri_leaves(ctx, r_vals[r], len, ab, r_tree[r]));
-        SIPP_TRY(sipp_k_merkle_levels(ctx, r_tree[r], log_len - ab, p.cap_height));
+        SIPP_TRY(sipp_k_tree_fri_leaves(ctx, p.hasher, r_vals[r], len, ab, r_tree[r]));
+        SIPP_TRY(sipp_k_tree_levels(ctx, p.hasher, r_tree[r], log_len - ab, p.cap_height));
         SIPP_TRY(read_cap(ctx, r_tree[r], log_len - ab, p.cap_height, cap_host));
         const size_t cw = (size_t)4 << std::min(p.cap_height, log_len - ab);
         ch.observe_many(cap_host, cw);
@@ -211,11 +211,19 @@ void sipp_fri_const_arity(sipp_fri_params* p, uint32_t arity_bits, uint32_t fina
 int sipp_commit_batch_ex(sipp_ctx* ctx, const uint64_t* d_in, int from_coeffs, uint64_t* d_coeffs, uint64_t* d_lde, uint64_t* d_tree,
                          size_t ncols, uint32_t log_n, uint32_t rate_bits, uint32_t cap_height, const uint64_t* d_salt,
                          uint32_t n_salt, uint64_t* cap_out) {
+    return sipp_commit_batch_h(ctx, d_in, from_coeffs, d_coeffs, d_lde, d_tree, ncols, log_n, rate_bits, cap_height, d_salt, n_salt,
+                               SIPP_HASH_POSEIDON, cap_out);
+}
+
+int sipp_commit_batch_h(sipp_ctx* ctx, const uint64_t* d_in, int from_coeffs, uint64_t* d_coeffs, uint64_t* d_lde, uint64_t* d_tree,
+                        size_t ncols, uint32_t log_n, uint32_t rate_bits, uint32_t cap_height, const uint64_t* d_salt, uint32_t n_salt,
+                        uint32_t hasher, uint64_t* cap_out) {
     if (!ctx || !d_in || !d_coeffs || !d_lde || !d_tree || !cap_out || ncols == 0) return SIPP_E_BADARG;
+    SIPP_TRY(sipp_hasher_check(ctx, hasher));
     if (rate_bits < 1 || rate_bits > 3 || cap_height > 8 || (n_salt != 0 && (n_salt != SIPP_SALT_SIZE || !d_salt)))
         return sipp_fail(ctx, SIPP_E_UNSUPPORTED, "commit_batch_ex: blowup 2 / 4 / 8, cap height <= 8, salt 0 or 4 columns");
     SIPP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    const int rc = commit_batch(ctx, CommitParams{rate_bits, cap_height, d_salt, n_salt}, d_in, from_coeffs != 0, d_coeffs, d_lde, d_tree, ncols,
+    const int rc = commit_batch(ctx, CommitParams{rate_bits, cap_height, d_salt, n_salt, false, hasher}, d_in, from_coeffs != 0, d_coeffs, d_lde, d_tree, ncols,
                                 log_n, cap_out);
     if (rc != SIPP_OK) (void)hipStreamSynchronize(ctx->stream);   // the caller may free its buffers after a failure as well
     return rc;
@@ -238,8 +246,16 @@ size_t sipp_fri_proof_size(const sipp_oracle* oracles, size_t n_oracles, const s
 int sipp_fri_prove_openings(sipp_ctx* ctx, const sipp_oracle* oracles, size_t n_oracles, const sipp_fri_batch* batches,
                             size_t n_batches, uint32_t log_n, const sipp_fri_params* p, sipp_challenger* chs, uint64_t* proof_out,
                             size_t proof_cap, size_t* proof_len) {
+    return sipp_fri_prove_openings_h(ctx, oracles, n_oracles, batches, n_batches, log_n, p, SIPP_HASH_POSEIDON, chs, proof_out, proof_cap,
+                                     proof_len);
+}
+
+int sipp_fri_prove_openings_h(sipp_ctx* ctx, const sipp_oracle* oracles, size_t n_oracles, const sipp_fri_batch* batches,
+                              size_t n_batches, uint32_t log_n, const sipp_fri_params* p, uint32_t hasher, sipp_challenger* chs,
+                              uint64_t* proof_out, size_t proof_cap, size_t* proof_len) {
     if (!ctx || !oracles || !batches || !p || !chs || !proof_out || !proof_len || n_oracles == 0 || n_oracles > 8 || n_batches == 0)
         return SIPP_E_BADARG;
+    SIPP_TRY(sipp_hasher_check(ctx, hasher));
     SIPP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
     SIPP_TRY(check_params(ctx, p, log_n));
     if (chs->n_in > 7 || chs->n_out > 8) return sipp_fail(ctx, SIPP_E_BADARG, "fri: malformed challenger state");
@@ -259,7 +275,8 @@ int sipp_fri_prove_openings(sipp_ctx* ctx, const sipp_oracle* oracles, size_t n_
         points[b] = gl::E2{batches[b].point[0], batches[b].point[1]};
         if (gl::eq(gl::pow(points[b], (uint64_t)n), gl::e2(1))) return sipp_fail(ctx, SIPP_E_SUBGROUP, "fri: opening point in the subgroup");
     }
-    const FriParamsDev fp(*p);
+    FriParamsDev fp(*p);
+    fp.hasher = hasher;
     host::Challenger ch(*chs);
     ArenaScope scope(ctx, /*sync_first=*/true);
     size_t pos = 0;

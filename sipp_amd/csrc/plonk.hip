@@ -504,6 +504,8 @@ struct PlonkExtra {
     const Lookup* lookup = nullptr;
     // zero knowledge ("SIPPPLK5", with circ and a hiding fp): oracles 1 .. 3 carry four salt columns drawn from this seed (blind.hip)
     const sipp_blinding* blind = nullptr;
+    // the tree hasher of every oracle and FRI layer (with circ): recorded in header word 13, which is zero under Poseidon
+    uint32_t hasher = SIPP_HASH_POSEIDON;
 };
 int plonk_prove_impl(sipp_ctx* ctx, const uint64_t* d_wires, const uint64_t* d_sigmas, uint32_t log_n, const sipp_plonk_params* p,
                      const sipp_fri_params* fp, const uint64_t circuit_digest[4], const uint64_t public_inputs_hash[4], const PlonkExtra& ex,
@@ -623,9 +625,9 @@ int plonk_prove_impl(sipp_ctx* ctx, const uint64_t* d_wires, const uint64_t* d_s
     // oracle o from values (or coefficients); a salted one hashes the four columns that already sit behind its polynomials' in leaf order
     auto commit = [&](int o, const uint64_t* d_in, int from_coeffs) -> int {
         if (!lay.n_salt[o])
-            return sipp_commit_batch_ex(ctx, d_in, from_coeffs, co[o], lde[o], tree[o], ncols[o], log_n, fp->rate_bits, fp->cap_height, nullptr, 0,
-                                        cap_of(o));
-        const int rc = commit_batch(ctx, CommitParams{fp->rate_bits, fp->cap_height, nullptr, lay.n_salt[o], true}, d_in, from_coeffs != 0, co[o],
+            return sipp_commit_batch_h(ctx, d_in, from_coeffs, co[o], lde[o], tree[o], ncols[o], log_n, fp->rate_bits, fp->cap_height, nullptr, 0,
+                                       ex.hasher, cap_of(o));
+        const int rc = commit_batch(ctx, CommitParams{fp->rate_bits, fp->cap_height, nullptr, lay.n_salt[o], true, ex.hasher}, d_in, from_coeffs != 0, co[o],
                                     lde[o], tree[o], ncols[o], log_n, cap_of(o));
         if (rc != SIPP_OK) (void)hipStreamSynchronize(ctx->stream);
         return rc;
@@ -684,15 +686,15 @@ int plonk_prove_impl(sipp_ctx* ctx, const uint64_t* d_wires, const uint64_t* d_s
     sipp_challenger cs{};
     ch.store(&cs);
     size_t op_len = 0;
-    SIPP_TRY(sipp_fri_prove_openings(ctx, oracles, 4, batches, 2, log_n, fp, &cs, proof_out + head, proof_cap - head - tail, &op_len));
+    SIPP_TRY(sipp_fri_prove_openings_h(ctx, oracles, 4, batches, 2, log_n, fp, ex.hasher, &cs, proof_out + head, proof_cap - head - tail, &op_len));
     if (ex.lookup || zk) {      // "SIPPPLK5": header[12] = 1, the description words all zero without lookups
         uint64_t h[24] = {zk ? 0x354b4c5050504953ULL /* "SIPPPLK5" */ : 0x344b4c5050504953ULL /* "SIPPPLK4" */, log_n, R, D, C, head + op_len + tail,
-                          Wn, K, ex.circ->num_selectors, ex.circ->num_gates, num_gate_constraints(ex.circ), tail, zk ? 1u : 0u, 0, 0, 0};
+                          Wn, K, ex.circ->num_selectors, ex.circ->num_gates, num_gate_constraints(ex.circ), tail, zk ? 1u : 0u, ex.hasher, 0, 0};
         for (int q = 0; q < 8; q++) h[16 + q] = ex.lookup ? plonk_desc::lookup_word(*ex.lookup, q) : 0;
         memcpy(proof_out, h, sizeof h);
     } else if (ex.circ) {
         const uint64_t h[16] = {0x334b4c5050504953ULL /* "SIPPPLK3" */, log_n, R, D, C, head + op_len + tail, Wn, K, ex.circ->num_selectors,
-                                ex.circ->num_gates, num_gate_constraints(ex.circ), tail, 0, 0, 0, 0};
+                                ex.circ->num_gates, num_gate_constraints(ex.circ), tail, 0, ex.hasher, 0, 0};
         memcpy(proof_out, h, sizeof h);
     } else {
         const uint64_t h[8] = {ex.v2 ? 0x324b4c5050504953ULL /* "SIPPPLK2" */ : 0x314b4c5050504953ULL /* "SIPPPLK1" */, log_n, R, D, C,
@@ -734,8 +736,8 @@ size_t sipp_plonk_gates_lookup_proof_size(uint32_t log_n, const sipp_plonk_param
 static int prove_gates_any(sipp_ctx* ctx, const uint64_t* d_wires, const uint64_t* d_constants_sigmas, const sipp_oracle* wires_oracle,
                            const uint64_t* wires_cap, const sipp_oracle* constants_sigmas_oracle, uint32_t log_n, const sipp_plonk_params* p,
                            const sipp_fri_params* fp, const sipp_plonk_circuit* c, const uint64_t circuit_digest[4], const uint64_t* public_inputs,
-                           uint32_t n_public_inputs, const uint32_t* lookup, const sipp_blinding* blind, bool zk_entry, uint64_t* proof_out,
-                           size_t proof_cap, size_t* proof_len);
+                           uint32_t n_public_inputs, const uint32_t* lookup, const sipp_blinding* blind, bool zk_entry, uint32_t hasher,
+                           uint64_t* proof_out, size_t proof_cap, size_t* proof_len);
 
 int sipp_plonk_prove_gates(sipp_ctx* ctx, const uint64_t* d_wires, const uint64_t* d_constants_sigmas, const sipp_oracle* wires_oracle,
                            const uint64_t* wires_cap, const sipp_oracle* constants_sigmas_oracle, uint32_t log_n, const sipp_plonk_params* p,
@@ -753,7 +755,7 @@ int sipp_plonk_prove_gates_lookup(sipp_ctx* ctx, const uint64_t* d_wires, const 
                                   const uint32_t* lookup, uint64_t* proof_out, size_t proof_cap, size_t* proof_len) {
     // (a hiding fp reaches plonk_prove_impl without a seed and is refused there, SIPP_E_UNSUPPORTED as before)
     return prove_gates_any(ctx, d_wires, d_constants_sigmas, wires_oracle, wires_cap, constants_sigmas_oracle, log_n, p, fp, c, circuit_digest,
-                           public_inputs, n_public_inputs, lookup, nullptr, false, proof_out, proof_cap, proof_len);
+                           public_inputs, n_public_inputs, lookup, nullptr, false, SIPP_HASH_POSEIDON, proof_out, proof_cap, proof_len);
 }
 
 size_t sipp_plonk_gates_zk_proof_size(uint32_t log_n, const sipp_plonk_params* p, const sipp_fri_params* fp, const sipp_plonk_circuit* c,
@@ -772,15 +774,29 @@ int sipp_plonk_prove_gates_zk(sipp_ctx* ctx, const uint64_t* d_wires, const uint
     const BlindArg arg(blind_words);
     const sipp_blinding* blind = arg.p;
     return prove_gates_any(ctx, d_wires, d_constants_sigmas, wires_oracle, wires_cap, constants_sigmas_oracle, log_n, p, fp, c, circuit_digest,
-                           public_inputs, n_public_inputs, lookup, blind, true, proof_out, proof_cap, proof_len);
+                           public_inputs, n_public_inputs, lookup, blind, true, SIPP_HASH_POSEIDON, proof_out, proof_cap, proof_len);
+}
+
+// sipp_plonk_prove_gates_zk with the tree hasher; a NULL lookup is the empty description
+int sipp_plonk_prove_gates_h(sipp_ctx* ctx, const uint64_t* d_wires, const uint64_t* d_constants_sigmas, const sipp_oracle* wires_oracle,
+                             const uint64_t* wires_cap, const sipp_oracle* constants_sigmas_oracle, uint32_t log_n, const sipp_plonk_params* p,
+                             const sipp_fri_params* fp, const sipp_plonk_circuit* c, const uint64_t circuit_digest[4],
+                             const uint64_t* public_inputs, uint32_t n_public_inputs, const uint32_t* lookup, const uint64_t* blind_words,
+                             uint32_t hasher, uint64_t* proof_out, size_t proof_cap, size_t* proof_len) {
+    static const uint32_t none[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (!ctx) return SIPP_E_BADARG;
+    SIPP_TRY(sipp_hasher_check(ctx, hasher));
+    const BlindArg arg(blind_words);
+    return prove_gates_any(ctx, d_wires, d_constants_sigmas, wires_oracle, wires_cap, constants_sigmas_oracle, log_n, p, fp, c, circuit_digest,
+                           public_inputs, n_public_inputs, lookup ? lookup : none, arg.p, true, hasher, proof_out, proof_cap, proof_len);
 }
 
 // the two entries above: `zk_entry` answers a hiding fp without a seed itself (SIPP_E_BADARG), the lookup entry leaves it to plonk_prove_impl
 static int prove_gates_any(sipp_ctx* ctx, const uint64_t* d_wires, const uint64_t* d_constants_sigmas, const sipp_oracle* wires_oracle,
                            const uint64_t* wires_cap, const sipp_oracle* constants_sigmas_oracle, uint32_t log_n, const sipp_plonk_params* p,
                            const sipp_fri_params* fp, const sipp_plonk_circuit* c, const uint64_t circuit_digest[4], const uint64_t* public_inputs,
-                           uint32_t n_public_inputs, const uint32_t* lookup, const sipp_blinding* blind, bool zk_entry, uint64_t* proof_out,
-                           size_t proof_cap, size_t* proof_len) {
+                           uint32_t n_public_inputs, const uint32_t* lookup, const sipp_blinding* blind, bool zk_entry, uint32_t hasher,
+                           uint64_t* proof_out, size_t proof_cap, size_t* proof_len) {
     if (!ctx || !lookup || !d_wires || !d_constants_sigmas || !fp || !p || !c || !circuit_digest || !proof_out || !proof_len ||
         (n_public_inputs && !public_inputs) || (wires_oracle != nullptr) != (wires_cap != nullptr) || n_public_inputs > (1u << 24))
         return SIPP_E_BADARG;
@@ -805,5 +821,6 @@ static int prove_gates_any(sipp_ctx* ctx, const uint64_t* d_wires, const uint64_
     ex.sigmas_oracle = constants_sigmas_oracle; ex.wires_oracle = wires_oracle; ex.wires_cap = wires_cap; ex.circ = c;
     ex.lookup = l.empty() ? nullptr : &l;      // an empty description: "SIPPPLK3", word for word
     ex.blind = blind;
+    ex.hasher = hasher;
     return plonk_prove_impl(ctx, d_wires, d_constants_sigmas, log_n, p, fp, circuit_digest, pih, ex, proof_out, proof_cap, proof_len);
 }

@@ -169,6 +169,7 @@ inline uint32_t sipp_fri_const_arity_rounds(uint32_t degree_bits, uint32_t rate_
 struct FriParamsDev {
     uint32_t rate_bits = 1, cap_height = 4, pow_bits = 16, num_queries = 84, pow_rule = 0;
     std::vector<uint32_t> arity_bits;   // FriParams::reduction_arity_bits
+    uint32_t hasher = SIPP_HASH_POSEIDON;   // of the layer trees (the oracles' trees are the caller's); the challenger is Poseidon either way
     // the generic ABI's parameters (n_rounds beyond SIPP_FRI_MAX_ROUNDS is refused by the callers' checks, cut here)
     explicit FriParamsDev(const sipp_fri_params& p)
         : rate_bits(p.rate_bits), cap_height(p.cap_height), pow_bits(p.pow_bits), num_queries(p.num_queries), pow_rule(p.pow_rule),

@@ -23,6 +23,7 @@
 #include "air_tables.h"
 #include "gl.hpp"
 #include "host_challenger.hpp"
+#include "host_tree_hash.hpp"
 #include "plonk_desc.hpp"
 
 const air_spec_t* sipp_air_get(int kind, uint32_t log_n);   // trace.hip: the AIR of an API kind at a trace length
@@ -333,6 +334,7 @@ struct Reader {
 struct FriShape {
     uint32_t rate_bits, cap_height, pow_bits, num_queries, pow_rule;
     std::vector<uint32_t> arity_bits;
+    uint32_t hasher = SIPP_HASH_POSEIDON;   // of every Merkle tree the proof opens; the challenger and the proof of work are Poseidon either way
 };
 // FriReductionStrategy::ConstantArityBits(arity_bits, final_poly_bits)
 FriShape fri_shape(const sipp_stark_config& c, unsigned degree_bits) {
@@ -346,15 +348,24 @@ FriShape fri_shape(const sipp_stark_config& c, unsigned degree_bits) {
     return p;
 }
 
+using host::tree_hash_or_noop;      // host_tree_hash.hpp: the tree hasher's two functions
+using host::tree_two_to_one;
+// every word of `count` Keccak digests inside its range (words 0 - 2 below 2^56, word 3 below 2^32): the repacking into 25 bytes would
+// drop the bits above, and two different proofs would verify alike
+bool digests_in_range(const uint64_t* d, size_t count) {
+    for (size_t i = 0; i < 4 * count; i++)
+        if (!keccak::word_in_range(d[i], (int)(i & 3))) return false;
+    return true;
+}
+
 // hash_or_noop(leaf) climbed to the cap entry the index points at
-bool merkle_ok(const uint64_t* leaf, size_t leaf_len, size_t index, const uint64_t* siblings, size_t n_siblings, const uint64_t* cap) {
-    uint64_t cur[4] = {0, 0, 0, 0};
-    if (leaf_len <= 4) memcpy(cur, leaf, leaf_len * 8);
-    else host::Challenger::hash_no_pad(leaf, leaf_len, cur);
+bool merkle_ok(uint32_t hasher, const uint64_t* leaf, size_t leaf_len, size_t index, const uint64_t* siblings, size_t n_siblings, const uint64_t* cap) {
+    uint64_t cur[4];
+    tree_hash_or_noop(hasher, leaf, leaf_len, cur);
     for (size_t l = 0; l < n_siblings; l++) {
         uint64_t nxt[4];
-        if ((index >> l) & 1) host::Challenger::two_to_one(siblings + 4 * l, cur, nxt);
-        else host::Challenger::two_to_one(cur, siblings + 4 * l, nxt);
+        if ((index >> l) & 1) tree_two_to_one(hasher, siblings + 4 * l, cur, nxt);
+        else tree_two_to_one(hasher, cur, siblings + 4 * l, nxt);
         memcpy(cur, nxt, 32);
     }
     return memcmp(cur, cap + 4 * (index >> n_siblings), 32) == 0;
@@ -530,12 +541,17 @@ int fri_verify(Reader& rb, const uint64_t* const* caps, const uint32_t* ncols, c
     const size_t m = (size_t)1 << log_m, n = (size_t)1 << log_n;
     const size_t cap_n = (size_t)1 << fp.cap_height;
     if (fp.cap_height > log_m) return 120;
+    const bool kk = fp.hasher == SIPP_HASH_KECCAK25;
+    if (kk)
+        for (size_t o = 0; o < n_oracles; o++)
+            if (!digests_in_range(caps[o], cap_n)) return 141;
     std::vector<const uint64_t*> rcaps(fp.arity_bits.size());
     std::vector<E2> betas(fp.arity_bits.size());
     unsigned sum_ab = 0;
     for (size_t r = 0; r < fp.arity_bits.size(); r++) {
         rcaps[r] = rb.take(cap_n * 4);
         if (rb.bad) return 120;
+        if (kk && !digests_in_range(rcaps[r], cap_n)) return 141;
         ch.observe_many(rcaps[r], cap_n * 4);
         betas[r] = ch.get_ext();
         if (fp.arity_bits[r] < 1 || fp.arity_bits[r] > 4) return 120;
@@ -589,6 +605,24 @@ int fri_verify(Reader& rb, const uint64_t* const* caps, const uint32_t* ncols, c
     std::vector<size_t> xs(fp.num_queries);
     for (uint32_t qi = 0; qi < fp.num_queries; qi++) xs[qi] = (size_t)(ch.get() % m);
     const size_t q_base = rb.pos;
+    if (kk)      // every sibling of every complete query round, before any path is climbed
+        for (uint32_t qi = 0; qi < fp.num_queries; qi++) {
+            size_t at = q_base + (size_t)qi * qwords;
+            if (at > len || qwords > len - at) break;      // (a truncated round is the rounds' own stage 122 / 130)
+            for (size_t o = 0; o < n_oracles; o++) {
+                at += (size_t)ncols[o] + (size_t)n_salt[o];
+                if (!digests_in_range(proof + at, ns0)) return 141;
+                at += (size_t)ns0 * 4;
+            }
+            unsigned lt = log_m;
+            for (size_t r = 0; r < fp.arity_bits.size(); r++) {
+                lt -= fp.arity_bits[r];
+                const size_t ns = lt > fp.cap_height ? lt - fp.cap_height : 0;
+                at += (size_t)2 << fp.arity_bits[r];
+                if (!digests_in_range(proof + at, ns)) return 141;
+                at += ns * 4;
+            }
+        }
     auto query = [&](uint32_t qi) -> int {
         Reader rq{proof, q_base + (size_t)qi * qwords, len};
         if (rq.pos > len) return 122;
@@ -599,7 +633,7 @@ int fri_verify(Reader& rb, const uint64_t* const* caps, const uint32_t* ncols, c
             rows[o] = rq.take(ll);
             const uint64_t* sib = rq.take((size_t)ns0 * 4);
             if (rq.bad) return 122;
-            if (!merkle_ok(rows[o], ll, x, sib, ns0, caps[o])) return 123 + (int)(o < 3 ? o : 3);
+            if (!merkle_ok(fp.hasher, rows[o], ll, x, sib, ns0, caps[o])) return 123 + (int)(o < 3 ? o : 3);
         }
         uint64_t sub_x = gl::mul(gl::GEN, gl::pow(wm, (uint64_t)gl::bitrev((uint32_t)x, log_m)));
         // fri_combine_initial (salt words are never combined)
@@ -651,7 +685,7 @@ int fri_verify(Reader& rb, const uint64_t* const* caps, const uint32_t* ncols, c
             }
             old = acc;
             xi >>= ab;
-            if (!merkle_ok(evw, 2 * arity, xi, sib, ns, rcaps[r])) return 132;
+            if (!merkle_ok(fp.hasher, evw, 2 * arity, xi, sib, ns, rcaps[r])) return 132;
             sub_x = gl::pow(sub_x, (uint64_t)arity);
         }
         E2 fv = e2(0);
@@ -922,7 +956,8 @@ bool fri_params_ok(const sipp_fri_params& p, unsigned log_n) {
 // the section written by PolynomialBatch::prove_openings: header[8], the opened values batch by batch (observed as they are read), then
 // what fri_verify reads.  `sec` / `sec_len`: the section alone (its header carries its own length)
 int fri_openings_verify(const uint64_t* sec, size_t sec_len, const uint64_t* const* caps, const uint32_t* ncols, const uint32_t* n_salt,
-                        size_t n_oracles, const FriBatchV* batches, size_t n_batches, unsigned log_n, const sipp_fri_params& p, host::Challenger& ch) {
+                        size_t n_oracles, const FriBatchV* batches, size_t n_batches, unsigned log_n, const sipp_fri_params& p, uint32_t hasher,
+                        host::Challenger& ch) {
     if (sec_len < 8 || sec[0] != FRI_MAGIC || sec[1] != p.n_rounds || sec[3] != p.num_queries || sec[4] != n_oracles || sec[5] != n_batches ||
         sec[6] != sec_len || sec[7] != log_n)
         return 100;
@@ -953,7 +988,9 @@ int fri_openings_verify(const uint64_t* sec, size_t sec_len, const uint64_t* con
         optr[b] = opened[b].data();
     }
     const E2 alpha = ch.get_ext();
-    const int rc = fri_verify(rb, caps, ncols, n_salt, n_oracles, batches, optr.data(), n_batches, log_n, fri_shape_of(p), alpha, ch);
+    FriShape shape = fri_shape_of(p);
+    shape.hasher = hasher;
+    const int rc = fri_verify(rb, caps, ncols, n_salt, n_oracles, batches, optr.data(), n_batches, log_n, shape, alpha, ch);
     if (rc) return rc;
     return rb.pos == sec_len ? 0 : 140;
 }
@@ -969,7 +1006,7 @@ int fri_openings_verify(const uint64_t* sec, size_t sec_len, const uint64_t* con
 // fp.hiding decides which proof is accepted: 1 = "SIPPPLK5" alone (24 header words, header[12] = 1, the description words zero without
 // `lk`; the wires, zs_partial_products and quotient leaves carry four salt words), 0 = "SIPPPLK3" / "SIPPPLK4" alone.  Else stage 201.
 int plonk_verify(const uint64_t* proof, size_t len, const uint64_t* cs_cap, const sipp_plonk_params& p, const sipp_fri_params& fp,
-                 const sipp_plonk_circuit& c, const uint64_t digest[4], const plonk_desc::Lookup* lk) {
+                 const sipp_plonk_circuit& c, const uint64_t digest[4], const plonk_desc::Lookup* lk, uint32_t hasher) {
     uint32_t log_d, m;
     if (plonk_desc::params_check(&p, 1, plonk_desc::ROUTED, &log_d, &m) != plonk_desc::Params::ok ||
         plonk_desc::circuit_walk(&c, &p) != plonk_desc::Circuit::ok ||
@@ -991,7 +1028,7 @@ int plonk_verify(const uint64_t* proof, size_t len, const uint64_t* cs_cap, cons
             if (proof[16 + q] != (lk ? plonk_desc::lookup_word(*lk, q) : 0u)) return 201;
     }
     if (len < hw + 3 * cap_n * 4 || proof[0] != (zk ? PLONK_MAGIC5 : lk ? PLONK_MAGIC4 : PLONK_MAGIC3) || proof[2] != R || proof[3] != D || proof[4] != C || proof[5] != len || proof[6] != W ||
-        proof[7] != K || proof[8] != c.num_selectors || proof[9] != c.num_gates || proof[10] != ngc || proof[12] != (zk ? 1u : 0u) || (proof[13] | proof[14] | proof[15]))
+        proof[7] != K || proof[8] != c.num_selectors || proof[9] != c.num_gates || proof[10] != ngc || proof[12] != (zk ? 1u : 0u) || proof[13] != hasher || (proof[14] | proof[15]))
         return 201;
     const size_t n_pi = (size_t)proof[11];
     if (proof[11] > len - (hw + 3 * cap_n * 4)) return 201;
@@ -1000,6 +1037,8 @@ int plonk_verify(const uint64_t* proof, size_t len, const uint64_t* cs_cap, cons
     // every body word is a field element in canonical form (x + p would hash and compute like x: a second encoding of the same proof)
     for (size_t i = hw; i < len; i++)
         if (proof[i] >= gl::P) return 141;
+    // under Keccak the three caps the proof carries hold digest words in their ranges (the opening section checks its own caps and siblings)
+    if (hasher == SIPP_HASH_KECCAK25 && !digests_in_range(proof + hw, 3 * cap_n)) return 141;
     uint64_t pih[4];
     host::Challenger::hash_no_pad(proof + len - n_pi, n_pi, pih);
     const uint64_t *wcap = proof + hw, *zcap = wcap + cap_n * 4, *qcap = zcap + cap_n * 4, *op = qcap + cap_n * 4;
@@ -1111,7 +1150,7 @@ int plonk_verify(const uint64_t* proof, size_t len, const uint64_t* cs_cap, cons
     const uint32_t ncols[4] = {K + R, W, nzl, C * D}, zs4 = zk ? SIPP_SALT_SIZE : 0, salt[4] = {0, zs4, zs4, zs4};
     const sipp_poly_range r0[4] = {{0, 0, K + R}, {1, 0, W}, {2, 0, nzl}, {3, 0, C * D}}, r1[2] = {{2, 0, C}, {2, nz, nz + C}};
     const FriBatchV batches[2] = {{zeta, 4, r0}, {gl::scale(zeta, gl::root_of_unity(log_n)), lk ? 2u : 1u, r1}};
-    return fri_openings_verify(op, op_len, caps, ncols, salt, 4, batches, 2, log_n, fp, ch);
+    return fri_openings_verify(op, op_len, caps, ncols, salt, 4, batches, 2, log_n, fp, hasher, ch);
 }
 
 }  // namespace
@@ -1119,7 +1158,14 @@ int plonk_verify(const uint64_t* proof, size_t len, const uint64_t* cs_cap, cons
 extern "C" int sipp_fri_verify_openings(const uint64_t* proof, size_t len, const uint64_t* const* caps, const uint32_t* ncols, const uint32_t* n_salt,
                                         size_t n_oracles, const sipp_fri_batch* batches, size_t n_batches, uint32_t log_n, const sipp_fri_params* p,
                                         sipp_challenger* chal, int* reason) {
+    return sipp_fri_verify_openings_h(proof, len, caps, ncols, n_salt, n_oracles, batches, n_batches, log_n, p, SIPP_HASH_POSEIDON, chal, reason);
+}
+
+extern "C" int sipp_fri_verify_openings_h(const uint64_t* proof, size_t len, const uint64_t* const* caps, const uint32_t* ncols, const uint32_t* n_salt,
+                                          size_t n_oracles, const sipp_fri_batch* batches, size_t n_batches, uint32_t log_n, const sipp_fri_params* p,
+                                          uint32_t hasher, sipp_challenger* chal, int* reason) {
     if (reason) *reason = 0;
+    if (hasher > SIPP_HASH_KECCAK25) return SIPP_E_BADARG;
     if (!proof || !caps || !ncols || !batches || !p || !chal || n_oracles == 0 || n_oracles > 64 || n_batches == 0 || n_batches > 64) return SIPP_E_BADARG;
     if (!fri_params_ok(*p, log_n)) return SIPP_E_UNSUPPORTED;
     std::vector<FriBatchV> bv(n_batches);
@@ -1129,7 +1175,7 @@ extern "C" int sipp_fri_verify_openings(const uint64_t* proof, size_t len, const
     host::Challenger ch(*chal);
     int r;
     try {
-        r = fri_openings_verify(proof, len, caps, ncols, n_salt ? n_salt : zero.data(), n_oracles, bv.data(), n_batches, log_n, *p, ch);
+        r = fri_openings_verify(proof, len, caps, ncols, n_salt ? n_salt : zero.data(), n_oracles, bv.data(), n_batches, log_n, *p, hasher, ch);
     } catch (...) {                        // (allocation failure: nothing crosses the C boundary)
         return SIPP_E_NOMEM;
     }
@@ -1144,7 +1190,7 @@ extern "C" int sipp_plonk_verify_gates(const uint64_t* proof, size_t len, const 
     if (!proof || !constants_sigmas_cap || !p || !fp || !c || !circuit_digest) return SIPP_E_BADARG;
     int r;
     try {
-        r = plonk_verify(proof, len, constants_sigmas_cap, *p, *fp, *c, circuit_digest, nullptr);
+        r = plonk_verify(proof, len, constants_sigmas_cap, *p, *fp, *c, circuit_digest, nullptr, SIPP_HASH_POSEIDON);
     } catch (...) {
         return SIPP_E_NOMEM;
     }
@@ -1155,12 +1201,23 @@ extern "C" int sipp_plonk_verify_gates(const uint64_t* proof, size_t len, const 
 extern "C" int sipp_plonk_verify_gates_lookup(const uint64_t* proof, size_t len, const uint64_t* constants_sigmas_cap, const sipp_plonk_params* p,
                                               const sipp_fri_params* fp, const sipp_plonk_circuit* c, const uint64_t circuit_digest[4],
                                               const uint32_t* lookup, int* reason) {
+    if (!lookup) {
+        if (reason) *reason = 0;
+        return SIPP_E_BADARG;
+    }
+    return sipp_plonk_verify_gates_h(proof, len, constants_sigmas_cap, p, fp, c, circuit_digest, lookup, SIPP_HASH_POSEIDON, reason);
+}
+
+extern "C" int sipp_plonk_verify_gates_h(const uint64_t* proof, size_t len, const uint64_t* constants_sigmas_cap, const sipp_plonk_params* p,
+                                         const sipp_fri_params* fp, const sipp_plonk_circuit* c, const uint64_t circuit_digest[4],
+                                         const uint32_t* lookup, uint32_t hasher, int* reason) {
+    static const uint32_t none[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (reason) *reason = 0;
-    if (!proof || !constants_sigmas_cap || !p || !fp || !c || !circuit_digest || !lookup) return SIPP_E_BADARG;
-    const plonk_desc::Lookup l = plonk_desc::lookup_of(lookup);      // an empty description: a "SIPPPLK3" proof
+    if (!proof || !constants_sigmas_cap || !p || !fp || !c || !circuit_digest || hasher > SIPP_HASH_KECCAK25) return SIPP_E_BADARG;
+    const plonk_desc::Lookup l = plonk_desc::lookup_of(lookup ? lookup : none);      // an empty description: a "SIPPPLK3" proof
     int r;
     try {
-        r = plonk_verify(proof, len, constants_sigmas_cap, *p, *fp, *c, circuit_digest, l.empty() ? nullptr : &l);
+        r = plonk_verify(proof, len, constants_sigmas_cap, *p, *fp, *c, circuit_digest, l.empty() ? nullptr : &l, hasher);
     } catch (...) {
         return SIPP_E_NOMEM;
     }

@@ -35,6 +35,9 @@ initial caps || the round caps || the final polynomial.  Witness inputs: the pro
 evaluations, the coset siblings -- every one a word of the flat proof.
 
 Refused at build: mixed arities, salted oracles, empty batches (FriQueryRoundCircuit's refusals), pow_bits > 32, n_in > 7.
+Refused at proving: Keccak Merkle trees (sipp_fri_prove_openings_h with SIPP_HASH_KECCAK25).  The opening section does not name its hasher,
+so the caller does (prove_proof's `hasher`); a whole outer proof handed over in its place is read by its header word 13.  ValueError,
+before anything is launched: the circuit verifies Poseidon trees only.
 
 numpy only; imports nothing from the test oracle."""
 import numpy as np
@@ -342,9 +345,17 @@ class FriProofProver(CircuitProver):
         cells, values = c.input_cells(*inputs)
         return self.data.prove_inputs(cells, values, c.public_inputs(*inputs[:c.n_public_args]))
 
-    def prove_proof(self, proof, caps, points, transcript):
+    def prove_proof(self, proof, caps, points, transcript, hasher="poseidon"):
         """caps: per initial oracle 2^cap_height digests; points: per batch (c0, c1); transcript: (the 12 state words, the n_in pending
-        inputs) the challenger arrives with.  No Python-integer walk of the proof, no host replay of the challenger."""
+        inputs) the challenger arrives with.  No Python-integer walk of the proof, no host replay of the challenger.
+        hasher: the tree hasher the opening proof was made with (the section does not name it); anything but "poseidon" is refused
+        with ValueError, as is a whole outer proof whose header names Keccak."""
+        from . import _lib
+        if _lib.hasher_id(hasher) != _lib.HASH_POSEIDON:
+            raise ValueError("FriProofProver: the circuit verifies Poseidon Merkle trees only, not hasher %r" % (hasher,))
+        head = np.asarray(proof, dtype=np.uint64).reshape(-1)[:1]
+        if len(head) and (int(head[0]) & 0x00ffffffffffffff) == 0x004b4c5050504953:      # "SIPPPLK?": a whole outer proof, not its opening section
+            _lib.refuse_keccak_proof(proof, "FriProofProver")
         if self.data.input_map is not None:
             return self.data.prove_words(*self.circ.words_of_proof(proof, caps, points, transcript))
         return self.data.prove_inputs(*self.circ.proof_inputs(proof, caps, points, transcript))

@@ -35,7 +35,8 @@ A commit-phase tree with exactly 2^cap_height leaves has no swap row: its leaf d
 
 Refused at build: mixed arities (arity_bits given per round with different values); salted (hiding) oracles (n_salt); empty batches;
 and in THIS class the proof of work (pow_bits != 0) and drawing the challenges in circuit (draw_challenges), which
-sipp_amd/fri_proof.py's FriProofCircuit does around the same wiring (query_rounds_into).
+sipp_amd/fri_proof.py's FriProofCircuit does around the same wiring (query_rounds_into).  Merkle paths are climbed with the Poseidon gate:
+trees hashed with Keccak (SIPP_HASH_KECCAK25) are not verified here, and a witness from such a proof satisfies no row.
 
 numpy only; imports nothing from the test oracle."""
 import numpy as np

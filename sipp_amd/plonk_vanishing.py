@@ -35,7 +35,8 @@ g zeta (2) || the departing sponge state (12).  The last 16 are generated cells:
 passes their values (transcript(), by the library's host permutation) as public inputs.
 
 Refused at build: no inner public input, more than 8 challenges, a max_degree that is no power of two, a gate set circuit_ok refuses,
-poseidon_mds without an inner gate of exactly that program, an alpha_chunk below 2.
+poseidon_mds without an inner gate of exactly that program, an alpha_chunk below 2.  Refused at proving (ValueError, nothing launched): an
+inner proof whose header word 13 names Keccak Merkle trees -- its caps are then 25-byte digests the Poseidon-only FRI half cannot check.
 
 numpy only; imports nothing from the test oracle."""
 import numpy as np
@@ -590,6 +591,8 @@ class PlonkVanishingProver(CircuitProver):
         return self.data.prove_inputs(cells, values, c.public_inputs(*inputs))
 
     def prove_proof(self, proof, digest):
+        from ._lib import refuse_keccak_proof
+        refuse_keccak_proof(proof, "PlonkVanishingProver")
         c = self.circ
         proof = np.ascontiguousarray(proof, dtype=np.uint64).reshape(-1)
         if self._layout is None or self._layout[0] != len(proof):
@@ -676,6 +679,8 @@ class PlonkProofVerifier:
 
     def prove_proof(self, inner_proof, constants_sigmas_cap, digest):
         """-> (the vanishing circuit's proof, the FRI circuit's proof)"""
+        from ._lib import refuse_keccak_proof
+        refuse_keccak_proof(inner_proof, "PlonkProofVerifier")
         v = self.vc
         proof = np.ascontiguousarray(inner_proof, dtype=np.uint64).reshape(-1)
         first = self.vanishing.prove_proof(proof, digest)

@@ -27,7 +27,8 @@ That is 16 generators, 17 with poseidon_mds: more than the level kernels' narrow
 
 Refused at build: what either half refuses -- no inner public input, more than 8 challenges, a max_degree that is no power of two, a gate
 set circuit_ok refuses, poseidon_mds without an inner gate of that program, an alpha_chunk below 2; a cap height outside 1 .. 6, mixed
-arities, salted (hiding) oracles, a proof of work of more than 32 bits.
+arities, salted (hiding) oracles, a proof of work of more than 32 bits.  Refused at proving: an inner proof whose header names Keccak Merkle
+trees (header word 13, sipp_plonk_prove_gates_h): the circuit verifies Poseidon trees only -- ValueError before anything is launched.
 
 numpy only; imports nothing from the test oracle."""
 import numpy as np
@@ -272,6 +273,8 @@ class PlonkVerifierProver(CircuitProver):
 
     def prove_proof(self, inner_proof, constants_sigmas_cap, digest):
         """the outer proof of one flat inner proof: the map from its words to the input cells goes to the device once"""
+        from ._lib import refuse_keccak_proof
+        refuse_keccak_proof(inner_proof, "PlonkVerifierProver")
         c = self.circ
         words, extra, pis = c.words_of_proof(inner_proof, constants_sigmas_cap, digest)
         if not self._mapped:
