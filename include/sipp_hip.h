@@ -539,6 +539,31 @@ int sipp_plonk_prove_gates(sipp_ctx *ctx, const uint64_t *d_wires, const uint64_
  *                                                                       row0 + x / n_tab (canonical) if x < T and that row is below N, else 0.
  *                                                                       n_look, n_tab >= 1, look_wire0 + 2 n_look <= num_wires, tab_const0 +
  *                                                                       2 n_tab <= num_constants, base_col + 1 < num_constants
+ *   SIPP_GEN_U32_ARITHMETIC p = n_ops, stride, limbs per half           per op at b = stride k: a, b, c at b .. b+2 (operands by their low 32 bits), a b + c
+ *                                                                       = lo + 2^32 hi: lo at b+3, hi at b+4, the INVERSE CELL inv(2^32 - 1 - hi)
+ *                                                                       at b+5 (0 when hi = 2^32 - 1), then the 2-bit limbs of lo and of hi from
+ *                                                                       b+6.  a b + c <= p - 1, so (lo, hi) is the split of a canonical value,
+ *                                                                       which (inverse (2^32 - 1 - hi) - 1) lo = 0 lets the constraints say.
+ *                                                                       limbs <= 16, stride >= 6 + 2 limbs, n_ops stride <= num_wires
+ *                                                                                                                          (U32ArithmeticGenerator)
+ *   SIPP_GEN_U32_ADD_MANY   p = n_ops, stride, n_addends A, carry limbs C
+ *                                                                       per op at b = stride k: A addends at b .., the carry-in at b+A (all by
+ *                                                                       their low 32 bits), their sum = lo + 2^32 carry-out: lo at b+A+1, the
+ *                                                                       carry-out at b+A+2, the sixteen 2-bit limbs of lo from b+A+3, the C low
+ *                                                                       2-bit limbs of the carry-out from b+A+19.  A 1 .. 32, C <= 16, stride >=
+ *                                                                       A + 19 + C, n_ops stride <= num_wires.  The widest column of an 8 x 8
+ *                                                                       limb product with one more addend is A = 16: carry-out <= 16, C = 3
+ *                                                                                                                          (U32AddManyGenerator)
+ *   SIPP_GEN_NONNATIVE      p = op, x0, m0, out0                        x = the eight u32 limbs at x0 .., the modulus m = the eight at m0 .. (least
+ *                                                                       significant first, by their low 32 bits; m is data, copied from Constant
+ *                                                                       rows).  Writes 24 cells from out0: result (8), quotient (8), slack (8) =
+ *                                                                       m - 1 - result.  op 0: result = x mod m, quotient = x / m.  op 1: result
+ *                                                                       = (x mod m)^-1 mod m, quotient = k with x result = k m + 1.  m = 0, or
+ *                                                                       under op 1 an even m, m = 1 or gcd(x, m) != 1: 24 zeros.  op <= 1, the
+ *                                                                       three ranges inside the table, the written 24 cells apart from the 16
+ *                                                                       read ones.  One lane per row: a 256-bit division bit by bit, a binary
+ *                                                                       extended Euclid, a 512 / 256-bit division for k
+ * Only the U32 instantiations of the witness kernels carry the last three kinds; a generator list without them launches what it did before.
  * The five families from SIPP_GEN_ARITHMETIC_EXT to SIPP_GEN_QUOTIENT_EXT take ANY field value in every input cell; W != 0.
  * Defined behaviour outside a gate's range (the constraints, not the generators, refuse such rows): BASE_SPLIT drops the bits of w[0] at
  * and above n_limbs * bits; U32_MUL_ADD takes the low 32 bits of an operand that is not a u32, and with a stride wider than 5 + 2 limbs
@@ -565,6 +590,10 @@ int sipp_plonk_prove_gates(sipp_ctx *ctx, const uint64_t *d_wires, const uint64_
 #define SIPP_GEN_BASE_SUM 15
 #define SIPP_GEN_POSEIDON_MDS 16
 #define SIPP_GEN_LOOKUP 17
+/* 18 = SIPP_GEN_RANDOM (ZERO KNOWLEDGE below) */
+#define SIPP_GEN_U32_ARITHMETIC 19
+#define SIPP_GEN_U32_ADD_MANY 20
+#define SIPP_GEN_NONNATIVE 21
 typedef struct {
     uint32_t kind, selector_index, row;
     uint32_t p[5];

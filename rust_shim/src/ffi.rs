@@ -139,6 +139,11 @@ pub const SIPP_GEN_BASE_SUM: u32 = 15;
 pub const SIPP_GEN_POSEIDON_MDS: u32 = 16;
 /// SIPP_GEN_*: a looking row's y cells from a dense lookup table (p = look_wire0, n_look, tab_const0, n_tab, base_col)
 pub const SIPP_GEN_LOOKUP: u32 = 17;
+/// SIPP_GEN_*: u32 arithmetic with the canonicity cell (p = n_ops, stride, limbs per half), u32 add-many (p = n_ops, stride, addends,
+/// carry limbs) and the nonnative reduce / inverse over eight u32 limbs (p = op, x0, m0, out0)
+pub const SIPP_GEN_U32_ARITHMETIC: u32 = 19;
+pub const SIPP_GEN_U32_ADD_MANY: u32 = 20;
+pub const SIPP_GEN_NONNATIVE: u32 = 21;
 
 /// the seed of a zero-knowledge prover (four canonical words, secret) and the number of the proof under it (include/sipp_hip.h,
 /// "ZERO KNOWLEDGE"); the calls take it as its five words: `&b as *const SippBlinding as *const u64`

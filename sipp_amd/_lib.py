@@ -69,6 +69,10 @@ class PlonkCircuit(C.Structure):
         return c
 
 
+# include/sipp_hip.h SIPP_GEN_*: the u32 and nonnative families (sipp_amd/nonnative.py builds on them)
+GEN_U32_ARITHMETIC, GEN_U32_ADD_MANY, GEN_NONNATIVE = 19, 20, 21
+
+
 class PlonkGenerator(C.Structure):
     """sipp_plonk_generator: one gate family's witness generator with its layout (include/sipp_hip.h, "WITNESS GENERATORS")"""
     _fields_ = [("kind", C.c_uint32), ("selector_index", C.c_uint32), ("row", C.c_uint32), ("p", C.c_uint32 * 5)]

@@ -38,6 +38,7 @@ GEN_BASE_SUM = 15
 GEN_POSEIDON_MDS = 16
 GEN_LOOKUP = 17
 GEN_RANDOM = 18
+GEN_U32_ARITHMETIC, GEN_U32_ADD_MANY, GEN_NONNATIVE = 19, 20, 21
 # program factor kinds
 _W, _K, _PIH = 0, 1, 2
 # upstream's PoseidonGate layout (SIPP_GEN_POSEIDON_SWAP): 135 wires

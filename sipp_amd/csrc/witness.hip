@@ -24,6 +24,9 @@
 // extension elements: a case of run_generator on one lane, wherever the row runs.
 // SIPP_GEN_LOOKUP is the library's own (no upstream gate): a looking row of the lookup argument (lookup.hip) takes its y cells from a dense
 // table in the constant columns, y = f(x) by address, no index; also one lane, wherever the row runs.
+// SIPP's transcript in the outer circuit (recalled plonky2_u32 gates/arithmetic_u32.rs, add_many_u32.rs; sipp_amd/nonnative.py) adds
+// SIPP_GEN_U32_ARITHMETIC, SIPP_GEN_U32_ADD_MANY and SIPP_GEN_NONNATIVE, the reduction and the inverse of eight u32 limbs modulo a modulus
+// that is data: one lane per row, and only in kernel instantiations of their own (run_u32_generator, the U32 template flag).
 // SIPP_GEN_RANDOM (blinding rows) is NOT computed here: its cells depend on no other cell and cost a whole permutation per eight wires, so
 // blind.hip fills them with a kernel of its own that both entry points launch first; in run_generator the kind does nothing.
 #include "ctx.hpp"
@@ -343,6 +346,214 @@ __device__ __forceinline__ void run_generator(uint64_t* wires, const uint64_t* c
     }
 }
 
+// ---- the u32 and nonnative families (SIPP_GEN_U32_ARITHMETIC, _U32_ADD_MANY, _NONNATIVE) -----------------------------------------------------
+// They are not cases of run_generator: only the U32 instantiations of the kernels below carry this code, and the host picks those for
+// a generator list that holds one of the three kinds.  A 256-bit value is eight u32 limbs, least significant first, in an array that is
+// only ever indexed by unrolled loops (registers, no scratch); the loops over bits and over Euclid's steps stay rolled.
+__host__ __device__ __forceinline__ bool is_u32_family(uint32_t kind) { return kind >= SIPP_GEN_U32_ARITHMETIC && kind <= SIPP_GEN_NONNATIVE; }
+
+template <int NL>
+__device__ __forceinline__ bool big_is_zero(const uint32_t (&a)[NL]) {
+    uint32_t acc = 0;
+#pragma unroll
+    for (int k = 0; k < NL; k++) acc |= a[k];
+    return acc == 0;
+}
+__device__ __forceinline__ bool big_is_one(const uint32_t (&a)[8]) {
+    uint32_t acc = a[0] ^ 1u;
+#pragma unroll
+    for (int k = 1; k < 8; k++) acc |= a[k];
+    return acc == 0;
+}
+// d = a - b mod 2^256 -> the borrow
+__device__ __forceinline__ uint32_t big_sub(uint32_t (&d)[8], const uint32_t (&a)[8], const uint32_t (&b)[8]) {
+    uint32_t br = 0;
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        const uint64_t t = (uint64_t)a[k] - b[k] - br;
+        d[k] = (uint32_t)t;
+        br = (uint32_t)(t >> 63);
+    }
+    return br;
+}
+// d = a + b mod 2^256 -> the carry
+__device__ __forceinline__ uint32_t big_add(uint32_t (&d)[8], const uint32_t (&a)[8], const uint32_t (&b)[8]) {
+    uint32_t c = 0;
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        const uint64_t t = (uint64_t)a[k] + b[k] + c;
+        d[k] = (uint32_t)t;
+        c = (uint32_t)(t >> 32);
+    }
+    return c;
+}
+// a = 2 a + in mod 2^(32 NL) -> the bit shifted out
+template <int NL>
+__device__ __forceinline__ uint32_t big_shl1(uint32_t (&a)[NL], uint32_t in) {
+#pragma unroll
+    for (int k = 0; k < NL; k++) {
+        const uint32_t out = a[k] >> 31;
+        a[k] = (a[k] << 1) | in;
+        in = out;
+    }
+    return in;
+}
+// a = (a + 2^256 top) / 2
+__device__ __forceinline__ void big_shr1(uint32_t (&a)[8], uint32_t top) {
+#pragma unroll
+    for (int k = 0; k < 7; k++) a[k] = (a[k] >> 1) | (a[k + 1] << 31);
+    a[7] = (a[7] >> 1) | (top << 31);
+}
+// num (32 NL bits, consumed) = quotient m + rem, rem < m, for m != 0: schoolbook division bit by bit from the top.  q keeps the
+// quotient's low 256 bits (all of it for NL = 8; for NL = 16 the callers' quotients are below 2^256).  rem < m before a step, so
+// 2 rem + bit < 2 m: where the shift carries out of 256 bits the difference still fits them.
+template <int NL>
+__device__ __forceinline__ void big_divmod(uint32_t (&num)[NL], const uint32_t (&m)[8], uint32_t (&q)[8], uint32_t (&rem)[8]) {
+#pragma unroll
+    for (int k = 0; k < 8; k++) q[k] = 0, rem[k] = 0;
+#pragma unroll 1
+    for (uint32_t it = 0; it < 32 * NL; it++) {
+        const uint32_t top = big_shl1<8>(rem, big_shl1<NL>(num, 0));
+        uint32_t d[8];
+        const uint32_t take = top | (big_sub(d, rem, m) ^ 1u);
+#pragma unroll
+        for (int k = 0; k < 8; k++) rem[k] = take ? d[k] : rem[k];
+        (void)big_shl1<8>(q, take);
+    }
+}
+// a^-1 mod m for an odd m > 1 and a < m, by the binary extended Euclid: x1 a = u and x2 a = v (mod m) throughout, v stays odd, and
+// every step halves u -- after subtracting the smaller odd value where u is odd -- so bits(u) + bits(v) falls by one at least: at
+// most 512 steps.  At u = 0, v = gcd(a, m).  -> whether the gcd is 1; inv = x2 then.
+__device__ __forceinline__ bool big_inverse(const uint32_t (&a)[8], const uint32_t (&m)[8], uint32_t (&inv)[8]) {
+    uint32_t u[8], v[8], x1[8], d[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) u[k] = a[k], v[k] = m[k], x1[k] = k == 0, inv[k] = 0;
+#pragma unroll 1
+    while (!big_is_zero<8>(u)) {
+        if (u[0] & 1u) {
+            if (big_sub(d, u, v)) {                          // u < v: the two pairs change places
+#pragma unroll
+                for (int k = 0; k < 8; k++) {
+                    const uint32_t tu = u[k], tx = x1[k];
+                    u[k] = v[k], v[k] = tu, x1[k] = inv[k], inv[k] = tx;
+                }
+            }
+            (void)big_sub(u, u, v);
+            if (big_sub(x1, x1, inv)) (void)big_add(x1, x1, m);
+        }
+        big_shr1(u, 0);
+        uint32_t c = 0;
+        if (x1[0] & 1u) c = big_add(x1, x1, m);              // (x1 + m) / 2 < m
+        big_shr1(x1, c);
+    }
+    return big_is_one(v);
+}
+
+// SIPP_GEN_NONNATIVE on row i: x at x0 and the modulus m at m0, eight u32 limbs each (operands by their low 32 bits); result, quotient
+// and slack = m - 1 - result, eight limbs each, at out0.  op 0: result = x mod m, quotient = x / m.  op 1: result = (x mod m)^-1 mod m,
+// quotient = k with x result = k m + 1.  m = 0, or under op 1 an even m, m = 1 or gcd(x, m) != 1: 24 zeros.
+__device__ __forceinline__ void nonnative_row(uint64_t* wires, uint32_t n, uint32_t i, const sipp_plonk_generator& g) {
+    const uint32_t op = g.p[0], x0 = g.p[1], m0 = g.p[2], out0 = g.p[3];
+    uint32_t x[8], m[8], res[8], quo[8], slack[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        x[k] = (uint32_t)wires[(size_t)(x0 + k) * n + i];
+        m[k] = (uint32_t)wires[(size_t)(m0 + k) * n + i];
+        res[k] = 0, quo[k] = 0, slack[k] = 0;
+    }
+    bool ok = !big_is_zero<8>(m);
+    if (op == 1) ok = ok && (m[0] & 1u) && !big_is_one(m);
+    if (ok) {
+        uint32_t num[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) num[k] = x[k];
+        big_divmod<8>(num, m, quo, res);
+        if (op == 1) {
+            uint32_t inv[8];
+            ok = big_inverse(res, m, inv);
+            if (ok) {
+                // x inv - 1 over sixteen limbs (inv >= 1 and x >= 1 here), then its exact quotient by m
+                uint32_t pr[16];
+#pragma unroll
+                for (int k = 0; k < 16; k++) pr[k] = 0;
+#pragma unroll
+                for (int a = 0; a < 8; a++) {
+                    uint64_t c = 0;
+#pragma unroll
+                    for (int b = 0; b < 8; b++) {
+                        const uint64_t t = (uint64_t)x[a] * inv[b] + pr[a + b] + c;
+                        pr[a + b] = (uint32_t)t;
+                        c = t >> 32;
+                    }
+                    pr[a + 8] = (uint32_t)c;
+                }
+                uint32_t br = 1;
+#pragma unroll
+                for (int k = 0; k < 16; k++) {
+                    const uint32_t t = pr[k] - br;
+                    br = br & (pr[k] == 0);
+                    pr[k] = t;
+                }
+                big_divmod<16>(pr, m, quo, res);
+            }
+#pragma unroll
+            for (int k = 0; k < 8; k++) res[k] = ok ? inv[k] : 0, quo[k] = ok ? quo[k] : 0;
+        }
+    }
+    if (ok) {                                                   // m - 1 - result: result < m
+        uint32_t br = 1;
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            const uint64_t t = (uint64_t)m[k] - res[k] - br;
+            slack[k] = (uint32_t)t;
+            br = (uint32_t)(t >> 63);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        wires[(size_t)(out0 + k) * n + i] = res[k];
+        wires[(size_t)(out0 + 8 + k) * n + i] = quo[k];
+        wires[(size_t)(out0 + 16 + k) * n + i] = slack[k];
+    }
+}
+
+// one generator of the three kinds on one row
+__device__ __forceinline__ void run_u32_generator(uint64_t* wires, uint32_t n, uint32_t i, const sipp_plonk_generator& g) {
+    auto W = [&](uint32_t j) -> uint64_t& { return wires[(size_t)j * n + i]; };
+    constexpr uint64_t M32 = 0xffffffffull;
+    switch (g.kind) {
+    case SIPP_GEN_U32_ARITHMETIC:
+        for (uint32_t op = 0; op < g.p[0]; op++) {
+            const uint32_t b = g.p[1] * op, L = g.p[2];
+            // a b + c <= (2^32 - 1)^2 + 2^32 - 1 = p - 1: (lo, hi) is the one split of a canonical value
+            const uint64_t full = (W(b) & M32) * (W(b + 1) & M32) + (W(b + 2) & M32);
+            const uint64_t half[2] = {full & M32, full >> 32};
+            W(b + 3) = half[0];
+            W(b + 4) = half[1];
+            W(b + 5) = gl::inv(M32 - half[1]);               // inv(0) = 0: hi all ones, where the constraint needs lo = 0
+            for (uint32_t h = 0; h < 2; h++)
+                for (uint32_t l = 0; l < L; l++) W(b + 6 + L * h + l) = (half[h] >> (2 * l)) & 3;
+        }
+        break;
+    case SIPP_GEN_U32_ADD_MANY:
+        for (uint32_t op = 0; op < g.p[0]; op++) {
+            const uint32_t b = g.p[1] * op, A = g.p[2], C = g.p[3];
+            uint64_t sum = W(b + A) & M32;                      // the carry-in
+            for (uint32_t k = 0; k < A; k++) sum += W(b + k) & M32;
+            const uint64_t lo = sum & M32, carry = sum >> 32;
+            W(b + A + 1) = lo;
+            W(b + A + 2) = carry;
+            for (uint32_t l = 0; l < 16; l++) W(b + A + 3 + l) = (lo >> (2 * l)) & 3;
+            for (uint32_t l = 0; l < C; l++) W(b + A + 19 + l) = (carry >> (2 * l)) & 3;
+        }
+        break;
+    case SIPP_GEN_NONNATIVE:
+        nonnative_row(wires, n, i, g);
+        break;
+    default: break;
+    }
+}
+
 // SIPP_GEN_REDUCING / SIPP_GEN_REDUCING_EXT on the sixteen lanes of a row (all lanes of the wave call it; act = the row holds the
 // generator, ext = its coefficients are extension elements): lane l owns the chunk of m = ceil(K / 16) consecutive coefficients from
 // l m as the affine map acc -> acc M + C, (M, C) = (alpha^len, Horner of the chunk from 0).  Under (M1, C1) (M2, C2) = (M1 M2, C1 M2 + C2),
@@ -436,6 +647,14 @@ __global__ void __launch_bounds__(256) plonk_witness_kernel(GenArgs a) {
     run_generator(a.wires, a.consts, n, i, a.g, a.pih);
 }
 
+// the row-local launch of a generator of the u32 and nonnative families
+__global__ void __launch_bounds__(256) plonk_witness_u32_kernel(GenArgs a) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, n = a.n;
+    if (i >= n) return;
+    if (!row_holds(a.consts, n, i, a.g)) return;
+    run_u32_generator(a.wires, n, i, a.g);
+}
+
 // ---- level by level -------------------------------------------------------------------------------------------------------------------
 // A circuit's generators travel by value in the kernel arguments (scalar loads by a wave-uniform index).  Up to NARROW_GENS the struct
 // is the one every circuit had before the ceiling rose; a circuit with more takes the same kernels over the MAX_GENS struct (1104 bytes
@@ -458,7 +677,9 @@ using LevelArgsWide = LevelArgsT<MAX_GENS>;
 
 // one lane per row of the level; the row runs the generator whose selector value it holds (the lanes of a wave may hold different gates:
 // the families are short except Poseidon, whose rows a schedule keeps together)
-template <class Args>
+// U32 (here and in the two kernels below): the circuit has a generator of the u32 and nonnative families, whose code no other
+// instantiation carries; a row of theirs is one lane's work on every path.
+template <bool U32, class Args>
 __global__ void __launch_bounds__(64) plonk_witness_level_kernel(Args a) {
     const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= a.count) return;
@@ -468,7 +689,15 @@ __global__ void __launch_bounds__(64) plonk_witness_level_kernel(Args a) {
         return;
     }
     for (uint32_t q = 0; q < a.n_gens; q++)
-        if (row_holds(a.consts, a.n, i, a.g[q])) run_generator(a.wires, a.consts, a.n, i, a.g[q], a.pih);
+        if (row_holds(a.consts, a.n, i, a.g[q])) {
+            if constexpr (U32) {
+                if (is_u32_family(a.g[q].kind)) {
+                    run_u32_generator(a.wires, a.n, i, a.g[q]);
+                    continue;
+                }
+            }
+            run_generator(a.wires, a.consts, a.n, i, a.g[q], a.pih);
+        }
 }
 
 // THIN levels (a hash chain's link: a few hundred to a few thousand rows) are latency-bound -- one lane walking a whole permutation is
@@ -534,7 +763,7 @@ __device__ __forceinline__ void poseidon_lanes(uint64_t* wires, uint32_t n, uint
 }
 
 // the circuit's one Poseidon generator a.g[pos] (pos = -1: none) on the sixteen lanes, its parameters block-uniform
-template <class Args>
+template <bool U32, class Args>
 __global__ void __launch_bounds__(64) plonk_witness_level_coop_kernel(Args a, int pos) {
     __shared__ uint64_t sh[4][12];
     const CoopRow row = coop_row(a.rows, a.count, a.n, a.err);
@@ -544,7 +773,15 @@ __global__ void __launch_bounds__(64) plonk_witness_level_coop_kernel(Args a, in
         if (pos >= 0) is_pos = row_holds(a.consts, n, i, a.g[pos]);
         if (l == 0)
             for (uint32_t q = 0; q < a.n_gens; q++)
-                if ((int)q != pos && row_holds(a.consts, n, i, a.g[q])) run_generator(a.wires, a.consts, n, i, a.g[q], a.pih);
+                if ((int)q != pos && row_holds(a.consts, n, i, a.g[q])) {
+                    if constexpr (U32) {
+                        if (is_u32_family(a.g[q].kind)) {
+                            run_u32_generator(a.wires, n, i, a.g[q]);
+                            continue;
+                        }
+                    }
+                    run_generator(a.wires, a.consts, n, i, a.g[q], a.pih);
+                }
     }
     if (pos < 0 || !__syncthreads_or(is_pos)) return;        // block-uniform: no Poseidon row among the four
     const uint32_t in = a.g[pos].p[0], out = a.g[pos].p[1], sb = a.g[pos].p[2];
@@ -562,7 +799,7 @@ __global__ void __launch_bounds__(64) plonk_witness_level_coop_kernel(Args a, in
 // a query's longest chain); a row that holds SIPP_GEN_REDUCING or _REDUCING_EXT spreads its coefficients over its sixteen lanes
 // (reducing_lanes) unless reduce_one_lane (SIPP_ROUTE_WITNESS_REDUCE_ONE_LANE).  It implies INTERP's code: an interpolation generator
 // may or may not be there.
-template <bool INTERP, bool REDUCE, class Args>
+template <bool INTERP, bool REDUCE, bool U32, class Args>
 __global__ void __launch_bounds__(64) plonk_witness_level_coop_rows_kernel(Args a, bool one_lane, bool reduce_one_lane) {
     __shared__ uint64_t sh[4][12];
     const CoopRow row = coop_row(a.rows, a.count, a.n, a.err);
@@ -585,8 +822,15 @@ __global__ void __launch_bounds__(64) plonk_witness_level_coop_rows_kernel(Args 
         }
         if (l == 0)
             for (uint32_t q = 0; q < a.n_gens; q++)
-                if ((int)q != pq && (int)q != iq && (int)q != rq && row_holds(a.consts, n, i, a.g[q]))
+                if ((int)q != pq && (int)q != iq && (int)q != rq && row_holds(a.consts, n, i, a.g[q])) {
+                    if constexpr (U32) {
+                        if (is_u32_family(a.g[q].kind)) {
+                            run_u32_generator(a.wires, n, i, a.g[q]);
+                            continue;
+                        }
+                    }
                     run_generator(a.wires, a.consts, n, i, a.g[q], a.pih);
+                }
     }
     if (INTERP && __syncthreads_or(iq >= 0)) interpolation_lanes(a.wires, n, i, l, iq >= 0, is, id, inr);   // block-uniform
     if (REDUCE && __syncthreads_or(rq >= 0)) reducing_lanes(a.wires, n, i, l, rq >= 0, rext, rk, rnr);      // block-uniform
@@ -647,6 +891,15 @@ bool layout_ok(const sipp_plonk_generator& g, uint32_t num_wires, uint32_t num_c
         return g.p[1] >= 1 && g.p[3] >= 1 && (uint64_t)g.p[0] + 2ull * g.p[1] <= nw && (uint64_t)g.p[2] + 2ull * g.p[3] <= num_constants &&
                (uint64_t)g.p[4] + 1 < num_constants;
     case SIPP_GEN_RANDOM: return (uint64_t)g.p[0] + g.p[1] <= nw;
+    case SIPP_GEN_U32_ARITHMETIC: return g.p[2] <= 16 && g.p[1] >= 6 + 2 * g.p[2] && (uint64_t)g.p[0] * g.p[1] <= nw;
+    case SIPP_GEN_U32_ADD_MANY:
+        return g.p[2] >= 1 && g.p[2] <= 32 && g.p[3] <= 16 && g.p[1] >= g.p[2] + 19 + g.p[3] && (uint64_t)g.p[0] * g.p[1] <= nw;
+    case SIPP_GEN_NONNATIVE: {
+        // the 24 written cells must not meet the 16 read ones
+        const uint64_t x0 = g.p[1], m0 = g.p[2], out0 = g.p[3];
+        if (g.p[0] > 1 || x0 + 8 > nw || m0 + 8 > nw || out0 + 24 > nw) return false;
+        return (out0 + 24 <= x0 || x0 + 8 <= out0) && (out0 + 24 <= m0 || m0 + 8 <= out0);
+    }
     case SIPP_GEN_POSEIDON_SWAP: {
         // written cells (out, sbox, delta) must not meet the read cells (in, swap): the two launch paths read and write in different orders
         const uint64_t in = g.p[0], out = g.p[1], sb = g.p[2], sw = g.p[3], dl = g.p[4];
@@ -666,8 +919,9 @@ const char* gen_name(uint32_t kind) {
                                   "witness_random_access", "witness_reducing", "witness_poseidon", "witness_poseidon_swap",
                                   "witness_arithmetic_ext", "witness_exponentiation", "witness_coset_interpolation",
                                   "witness_reducing_ext", "witness_quotient_ext", "witness_base_sum", "witness_poseidon_mds",
-                                  "witness_lookup", "witness_random"};
-    return kind <= SIPP_GEN_RANDOM ? names[kind] : "witness";
+                                  "witness_lookup", "witness_random", "witness_u32_arithmetic", "witness_u32_add_many",
+                                  "witness_nonnative"};
+    return kind <= SIPP_GEN_NONNATIVE ? names[kind] : "witness";
 }
 
 }  // namespace
@@ -732,7 +986,10 @@ extern "C" int sipp_plonk_generate_witness_blind(sipp_ctx* ctx, uint64_t* d_wire
         a.wires = d_wires; a.consts = d_constants; a.n = n; a.g = gens[k];
         for (int l = 0; l < 4; l++) a.pih[l] = public_inputs_hash ? public_inputs_hash[l] : 0;
         ProfScope ps(ctx, gen_name(gens[k].kind));
-        hipLaunchKernelGGL(plonk_witness_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, a);
+        if (is_u32_family(gens[k].kind))
+            hipLaunchKernelGGL(plonk_witness_u32_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, a);
+        else
+            hipLaunchKernelGGL(plonk_witness_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, a);
         SIPP_CHECK_HIP(ctx, hipGetLastError());
     }
     return SIPP_OK;
@@ -760,12 +1017,13 @@ int witness_levels_run(sipp_ctx* ctx, uint64_t* d_wires, const uint64_t* d_const
         d_err = reinterpret_cast<int*>(t);
     }
     int pos_gen = -1, n_pos = 0;
-    bool any_swap = false, any_interp = false, any_initial = false;
+    bool any_swap = false, any_interp = false, any_initial = false, any_u32 = false;
     for (size_t q = 0; q < n_gens; q++) {
         if (is_poseidon(gens[q].kind)) pos_gen = (int)q, n_pos++;
         any_swap |= gens[q].kind == SIPP_GEN_POSEIDON_SWAP;
         any_interp |= gens[q].kind == SIPP_GEN_COSET_INTERPOLATION;
         any_initial |= gens[q].kind == SIPP_GEN_REDUCING_EXT || gens[q].kind == SIPP_GEN_QUOTIENT_EXT;
+        any_u32 |= is_u32_family(gens[q].kind);
     }
     const bool per_row = any_swap || n_pos > 1 || any_interp;     // the lanes go to each row's own Poseidon-family / interpolation generator
     const bool one_lane = any_interp && (ctx->kernel_routes & SIPP_ROUTE_WITNESS_INTERP_ONE_LANE);
@@ -773,10 +1031,16 @@ int witness_levels_run(sipp_ctx* ctx, uint64_t* d_wires, const uint64_t* d_const
     const bool reduce_one_lane = any_initial && (ctx->kernel_routes & SIPP_ROUTE_WITNESS_REDUCE_ONE_LANE);
     // a thin level's per-row kernel at the instantiation the circuit's families need (the one-lane flags are false wherever their code is
     // compiled out); none: the single-generator kernel
-    const auto rows_kernel = any_initial  ? plonk_witness_level_coop_rows_kernel<true, true, Args>
-                             : any_interp ? plonk_witness_level_coop_rows_kernel<true, false, Args>
-                             : per_row    ? plonk_witness_level_coop_rows_kernel<false, false, Args>
+    const auto rows_kernel = any_initial  ? (any_u32 ? plonk_witness_level_coop_rows_kernel<true, true, true, Args>
+                                                     : plonk_witness_level_coop_rows_kernel<true, true, false, Args>)
+                             : any_interp ? (any_u32 ? plonk_witness_level_coop_rows_kernel<true, false, true, Args>
+                                                     : plonk_witness_level_coop_rows_kernel<true, false, false, Args>)
+                             : per_row    ? (any_u32 ? plonk_witness_level_coop_rows_kernel<false, false, true, Args>
+                                                     : plonk_witness_level_coop_rows_kernel<false, false, false, Args>)
                                           : nullptr;
+    // a circuit without the u32 and nonnative families launches the instantiations without their code
+    const auto level_kernel = any_u32 ? plonk_witness_level_kernel<true, Args> : plonk_witness_level_kernel<false, Args>;
+    const auto coop_kernel = any_u32 ? plonk_witness_level_coop_kernel<true, Args> : plonk_witness_level_coop_kernel<false, Args>;
     Args a;          // the same for every level but for rows and count
     a.wires = d_wires; a.consts = d_constants; a.n = n; a.n_gens = (uint32_t)n_gens; a.err = d_err;
     for (int q = 0; q < 4; q++) a.pih[q] = public_inputs_hash ? public_inputs_hash[q] : 0;
@@ -789,11 +1053,11 @@ int witness_levels_run(sipp_ctx* ctx, uint64_t* d_wires, const uint64_t* d_const
                 a.rows = sched->d_rows + r0;
                 a.count = cnt;
                 if (cnt >= COOP_BELOW_ROWS)      // wide level: throughput, one lane per row
-                    hipLaunchKernelGGL(plonk_witness_level_kernel<Args>, dim3((cnt + 63) / 64), dim3(64), 0, ctx->stream, a);
+                    hipLaunchKernelGGL(level_kernel, dim3((cnt + 63) / 64), dim3(64), 0, ctx->stream, a);
                 else if (rows_kernel)            // thin level: latency, sixteen lanes per row
                     hipLaunchKernelGGL(rows_kernel, dim3((cnt + 3) / 4), dim3(64), 0, ctx->stream, a, one_lane, reduce_one_lane);
                 else
-                    hipLaunchKernelGGL(plonk_witness_level_coop_kernel<Args>, dim3((cnt + 3) / 4), dim3(64), 0, ctx->stream, a, pos_gen);
+                    hipLaunchKernelGGL(coop_kernel, dim3((cnt + 3) / 4), dim3(64), 0, ctx->stream, a, pos_gen);
             }
             const uint32_t c0 = sched->copy_offsets[l], cc = sched->copy_offsets[l + 1] - c0;
             if (cc)
