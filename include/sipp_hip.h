@@ -544,6 +544,7 @@ int sipp_plonk_prove_gates(sipp_ctx *ctx, const uint64_t *d_wires, const uint64_
  *                                                                       at b+5 (0 when hi = 2^32 - 1), then the 2-bit limbs of lo and of hi from
  *                                                                       b+6.  a b + c <= p - 1, so (lo, hi) is the split of a canonical value,
  *                                                                       which (inverse (2^32 - 1 - hi) - 1) lo = 0 lets the constraints say.
+ *                                                                       Where lo = 0 no constraint binds the inverse cell: a free cell by design.
  *                                                                       limbs <= 16, stride >= 6 + 2 limbs, n_ops stride <= num_wires
  *                                                                                                                          (U32ArithmeticGenerator)
  *   SIPP_GEN_U32_ADD_MANY   p = n_ops, stride, n_addends A, carry limbs C
