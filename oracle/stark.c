@@ -146,6 +146,95 @@ static void selectors_ext(unsigned log_n, gl2 x, gl2 *lf, gl2 *ll, gl2 *zl) {
     *zl = gl2_sub(x, gl2_from(gi));
 }
 
+/* The permutation products of a trace [n_main + 2 nc][n] (table column 0, checked columns from checked_base, then the permuted inputs
+ * and the permuted tables): zv [2 nc][n], column i nc + j for challenge i and checked column j,
+ *   Z[0] = 1,  Z[r + 1] = Z[r] num[r] / den[r],  num = (col + gamma_i)(tab + beta_i),  den = (pin + gamma_i)(ptab + beta_i).
+ * A vanishing denominator stays OUT of the batch inversion and 1 / 0 = 0, cell by cell (the rule of oracle/plonk.c): the column is zero
+ * from the row after it on and untouched before it.  (No honest transcript produces one; a proof over such a column cannot verify.) */
+void orc_z_columns(const uint64_t *trace, size_t n, int nm, int checked_base, int nc, const uint64_t beta[2], const uint64_t gamma[2],
+                   uint64_t *zv) {
+    const int P = 2 * nc;
+#pragma omp parallel
+    {
+        uint64_t *num = (uint64_t *)malloc(n * sizeof(uint64_t)), *den = (uint64_t *)malloc(n * sizeof(uint64_t));
+        uint64_t *pre = (uint64_t *)malloc(n * sizeof(uint64_t));
+#pragma omp for schedule(dynamic)
+        for (int zi = 0; zi < P; zi++) {
+            int i = zi / nc, j = zi % nc;
+            const uint64_t *col = trace + (size_t)(checked_base + j) * n, *tab = trace;
+            const uint64_t *pin = trace + (size_t)(nm + j) * n, *ptab = trace + (size_t)(nm + nc + j) * n;
+            for (size_t r = 0; r < n; r++) {
+                num[r] = gl_mul(gl_add(col[r], gamma[i]), gl_add(tab[r], beta[i]));
+                den[r] = gl_mul(gl_add(pin[r], gamma[i]), gl_add(ptab[r], beta[i]));
+            }
+            /* batch inversion of the non-zero denominators */
+            uint64_t acc = 1;
+            for (size_t r = 0; r < n; r++) { pre[r] = acc; if (den[r]) acc = gl_mul(acc, den[r]); }
+            uint64_t inv = gl_inv(acc);
+            for (size_t r = n; r-- > 0;) {
+                uint64_t d = den[r];
+                if (!d) continue;
+                den[r] = gl_mul(inv, pre[r]);
+                inv = gl_mul(inv, d);
+            }
+            uint64_t z = 1;
+            uint64_t *out = zv + (size_t)zi * n;
+            for (size_t r = 0; r < n; r++) { out[r] = z; z = gl_mul(z, gl_mul(num[r], den[r])); }
+        }
+        free(num); free(den); free(pre);
+    }
+}
+
+/* The quotient's values at chosen points of the coset 7 <w_2N>, from tables laid out as the device's (tests/_stark_quotient_cases.py):
+ * lde [W][stride], zlde [2 nc][stride], aux [n_aux][2N], all in leaf order; pos [npos] leaf positions j < 2N;
+ * out [2][npos] = orc_eval_base(cells at j, cells at the next row's leaf, ...) / Z_H(x_j).  Whatever the cells hold is evaluated.
+ * slot (or NULL): the tables hold only SOME leaf positions (a gather from a table too large for the host); slot[j] is where position j
+ * lies in them, for every position in pos and every next-row position of one. */
+void orc_quotient_points(const air_spec_t *a, unsigned log_n, const uint64_t *lde, const uint64_t *zlde, size_t stride, const uint64_t *aux_lde,
+                         const uint64_t alpha[2], const uint64_t beta[2], const uint64_t gamma[2], const uint32_t *pos, size_t npos,
+                         const uint32_t *slot, uint64_t *out) {
+    const unsigned log_mq = log_n + 1;
+    const size_t n = (size_t)1 << log_n, mq = (size_t)1 << log_mq;
+    const int W = orc_air_width(a), P = 2 * a->n_checked, n_vper = orc_air_n_vper(a), n_per = orc_air_n_per(a);
+    const size_t R2 = (size_t)2 << a->log_rows;
+    uint64_t *vper_tab = (uint64_t *)malloc((size_t)(n_vper ? n_vper : 1) * R2 * sizeof(uint64_t));
+    const uint64_t shift = gl_pow(GL_GEN, (uint64_t)1 << (log_n - (unsigned)a->log_rows));
+#pragma omp parallel for schedule(dynamic)
+    for (int k = 0; k < n_vper; k++) {
+        uint64_t *co = (uint64_t *)malloc((R2 / 2) * sizeof(uint64_t));
+        orc_vper_coeffs(a, k, co);
+        orc_coset_lde(co, (unsigned)a->log_rows, 1, shift, vper_tab + (size_t)k * R2);
+        free(co);
+    }
+    const uint64_t wm = gl_root_of_unity(log_mq), sN = gl_pow(GL_GEN, n);
+    const uint64_t zh_inv[2] = {gl_inv(gl_sub(sN, 1)), gl_inv(gl_sub(gl_neg(sN), 1))};
+#pragma omp parallel
+    {
+        uint64_t *cells = (uint64_t *)malloc(sizeof(uint64_t) * (size_t)(2 * W + 2 * P + (a->n_aux ? a->n_aux : 1) + n_per));
+        uint64_t *local = cells, *next = local + W, *zl = next + W, *zn = zl + P, *aux = zn + P, *per = aux + (a->n_aux ? a->n_aux : 1);
+#pragma omp for schedule(dynamic, 16)
+        for (size_t q = 0; q < npos; q++) {
+            const size_t j0 = pos[q], i = bitrev32((uint32_t)j0, log_mq), jn0 = bitrev32((uint32_t)((i + 2) & (mq - 1)), log_mq);
+            const size_t j = slot ? slot[j0] : j0, jn = slot ? slot[jn0] : jn0;
+            const uint64_t x = gl_mul(GL_GEN, gl_pow(wm, i));
+            uint64_t lf, ll, zlast, o[2];
+            for (int c = 0; c < W; c++) { local[c] = lde[(size_t)c * stride + j]; next[c] = lde[(size_t)c * stride + jn]; }
+            for (int c = 0; c < P; c++) { zl[c] = zlde[(size_t)c * stride + j]; zn[c] = zlde[(size_t)c * stride + jn]; }
+            for (int ai = 0; ai < a->n_aux; ai++) aux[ai] = aux_lde[(size_t)ai * (slot ? stride : mq) + j];
+            for (int k = 0; k < AIR_N_PERIODIC; k++) per[k] = orc_periodic_base(log_n, k, x);
+            for (int k = 0; k < n_vper; k++) per[AIR_N_PERIODIC + k] = vper_tab[(size_t)k * R2 + (i & (R2 - 1))];
+            selectors_base(log_n, x, &lf, &ll, &zlast);
+            orc_eval_base(a, local, next, aux, per, zl, zn, lf, ll, zlast, alpha, beta, gamma, o);
+            out[q] = gl_mul(o[0], zh_inv[i & 1]);
+            out[npos + q] = gl_mul(o[1], zh_inv[i & 1]);
+        }
+        free(cells);
+    }
+    free(vper_tab);
+}
+
+const air_spec_t *orc_air_by_index(int i) { return i >= 0 && (size_t)i < sizeof(AIR_AIRS) / sizeof(AIR_AIRS[0]) ? &AIR_AIRS[i] : NULL; }
+
 /* ---------------- test hook: one-shot tampering with a committed oracle the caller cannot reach ----------------
  * stage 1: Z column values (before their commitment), stage 2: quotient chunk coefficients.  tests/test_oracle_soundness.py */
 static struct { int stage, col; size_t row; uint64_t delta; } g_tamper;
@@ -209,30 +298,7 @@ int orc_stark_prove_trace(const orc_trace *t, const orc_config *cfg, uint64_t **
         if (cfg->lookup_rule) beta[i] = gamma[i];   /* shared challenge: Z' (pin + g)(ptab + g) = Z (col + g)(tab + g) */
     }
     uint64_t *zv = (uint64_t *)malloc((size_t)P * n * sizeof(uint64_t));
-#pragma omp parallel
-    {
-        uint64_t *num = (uint64_t *)malloc(n * sizeof(uint64_t)), *den = (uint64_t *)malloc(n * sizeof(uint64_t));
-        uint64_t *pre = (uint64_t *)malloc(n * sizeof(uint64_t));
-#pragma omp for schedule(dynamic)
-        for (int zi = 0; zi < P; zi++) {
-            int i = zi / nc, j = zi % nc;
-            const uint64_t *col = t->trace + (size_t)(a->checked_base + j) * n, *tab = t->trace;
-            const uint64_t *pin = t->trace + (size_t)(nm + j) * n, *ptab = t->trace + (size_t)(nm + nc + j) * n;
-            for (size_t r = 0; r < n; r++) {
-                num[r] = gl_mul(gl_add(col[r], gamma[i]), gl_add(tab[r], beta[i]));
-                den[r] = gl_mul(gl_add(pin[r], gamma[i]), gl_add(ptab[r], beta[i]));
-            }
-            /* batch inversion of den */
-            uint64_t acc = 1;
-            for (size_t r = 0; r < n; r++) { pre[r] = acc; acc = gl_mul(acc, den[r]); }
-            uint64_t inv = gl_inv(acc);
-            for (size_t r = n; r-- > 0;) { uint64_t d = den[r]; den[r] = gl_mul(inv, pre[r]); inv = gl_mul(inv, d); }
-            uint64_t z = 1;
-            uint64_t *out = zv + (size_t)zi * n;
-            for (size_t r = 0; r < n; r++) { out[r] = z; z = gl_mul(z, gl_mul(num[r], den[r])); }
-        }
-        free(num); free(den); free(pre);
-    }
+    orc_z_columns(t->trace, n, nm, a->checked_base, nc, beta, gamma, zv);
     apply_tamper(1, zv, n);
     orc_batch *bz = orc_batch_from_values(zv, (size_t)P, log_n, cfg->rate_bits, cfg->cap_height);
     free(zv);

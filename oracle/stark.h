@@ -23,6 +23,14 @@ int orc_stark_prove(int kind, const uint32_t *ios, size_t num_io, const orc_conf
                     size_t *proof_len);
 /* the same from a filled (possibly tampered) trace; the trace stays the caller's */
 int orc_stark_prove_trace(const orc_trace *t, const orc_config *cfg, uint64_t **proof_out, size_t *proof_len);
+/* the prover's stages on the caller's cells (tests/_stark_quotient_cases.py): the permutation products of a trace (a vanishing
+ * denominator: 1 / 0 = 0, cell by cell), the quotient's values at chosen leaf positions of device-layout tables, AIR_AIRS[i] */
+void orc_z_columns(const uint64_t *trace, size_t n, int nm, int checked_base, int nc, const uint64_t beta[2], const uint64_t gamma[2],
+                   uint64_t *zv);
+void orc_quotient_points(const air_spec_t *a, unsigned log_n, const uint64_t *lde, const uint64_t *zlde, size_t stride, const uint64_t *aux_lde,
+                         const uint64_t alpha[2], const uint64_t beta[2], const uint64_t gamma[2], const uint32_t *pos, size_t npos,
+                         const uint32_t *slot, uint64_t *out);
+const air_spec_t *orc_air_by_index(int i);
 /* test hook (one shot): add `delta` to cell (col, row) of the Z values (stage 1) or the quotient chunk coefficients (stage 2)
  * inside the next orc_stark_prove_trace */
 void orc_test_tamper(int stage, int col, size_t row, uint64_t delta);

@@ -130,7 +130,46 @@ __global__ void __launch_bounds__(256) z_phase_a(const uint64_t* __restrict__ tr
     }
 }
 
-__global__ void __launch_bounds__(256) z_phase_b(uint64_t* __restrict__ totals, int nblk) {
+// A column with a VANISHING denominator (T = 0: no honest transcript produces one, and a proof over such a column cannot verify -- the
+// running-product constraint is false at that row).  The prefix x suffix / T form has no value for it: 1 / T = inv(0) = 0 would zero the
+// whole column, row 0 included.  The rule is the wire permutation's (plonk.hip, oracle/plonk.c): a zero denominator stays out of any
+// batch trick and 1 / 0 = 0 cell by cell, Z[r + 1] = Z[r] num[r] inv0(den[r]) -- the column is untouched up to that row and zero after it.
+// Phase B's block of the column recomputes it from its four source columns, one inversion per row (n / 256 consecutive rows per lane,
+// the factors parked in the column itself), and leaves 1 in the block totals so that phase C passes it through.
+struct ZSource {
+    const uint64_t* trace;
+    uint64_t* zv;
+    size_t n;
+    int nm, nc, cbase;
+    uint64_t gamma[2], beta[2];
+};
+__device__ __noinline__ void z_column_by_rows(const ZSource a, int zi, uint64_t* s) {
+    const int i = zi / a.nc, j = zi % a.nc;
+    const uint64_t g = i ? a.gamma[1] : a.gamma[0], b = i ? a.beta[1] : a.beta[0];
+    const size_t n = a.n, per = n / 256, r0 = (size_t)threadIdx.x * per;      // n is a multiple of 1024 (sipp_k_z_columns)
+    const uint64_t* col = a.trace + (size_t)(a.cbase + j) * n;
+    const uint64_t* tab = a.trace;
+    const uint64_t* pin = a.trace + (size_t)(a.nm + j) * n;
+    const uint64_t* ptab = a.trace + (size_t)(a.nm + a.nc + j) * n;
+    uint64_t* z = a.zv + (size_t)zi * n;
+    uint64_t prod = 1;
+    for (size_t r = r0; r < r0 + per; r++) {
+        const uint64_t num = gl::mul(gl::add(col[r], g), gl::add(tab[r], b));
+        const uint64_t den = gl::mul(gl::add(pin[r], g), gl::add(ptab[r], b));
+        const uint64_t f = gl::mul(num, gl::inv(den));                        // gl::inv(0) = 0
+        z[r] = f;
+        prod = gl::mul(prod, f);
+    }
+    (void)block_scan_mul_256<false>(prod, s);
+    uint64_t acc = threadIdx.x ? s[threadIdx.x - 1] : 1;                      // the factors of the lanes before this one
+    for (size_t r = r0; r < r0 + per; r++) {
+        const uint64_t f = z[r];
+        z[r] = acc;
+        acc = gl::mul(acc, f);
+    }
+}
+
+__global__ void __launch_bounds__(256) z_phase_b(uint64_t* __restrict__ totals, int nblk, ZSource src) {
     // per Z column (nblk <= 2^15 blocks, chunked by 256): tn[blk] <- (numerators of the blocks before blk) (denominators of the blocks
     // after it) / T, T = all denominators
     __shared__ uint64_t s[256];
@@ -161,6 +200,11 @@ __global__ void __launch_bounds__(256) z_phase_b(uint64_t* __restrict__ totals, 
         if (idx < nblk) td[idx] = excl;
         carry = gl::mul(carry, all);
         __syncthreads();
+    }
+    if (carry == 0) {      // block-uniform: every lane holds the same T
+        z_column_by_rows(src, (int)blockIdx.x, s);
+        for (int idx = threadIdx.x; idx < nblk; idx += 256) tn[idx] = 1;
+        return;
     }
     const uint64_t tinv = gl::inv(carry);
     for (int idx = threadIdx.x; idx < nblk; idx += 256) tn[idx] = gl::mul(gl::mul(tn[idx], td[idx]), tinv);
@@ -1186,7 +1230,8 @@ int sipp_k_z_columns(sipp_ctx* ctx, const air_spec_t* a, const uint64_t* d_trace
     }
     {
         ProfScope ps(ctx, "z_phase_bc");
-        hipLaunchKernelGGL(z_phase_b, dim3(P), dim3(256), 0, ctx->stream, totals, (int)nblk);
+        const ZSource src{d_trace, d_zv, n, a->n_main, a->n_checked, a->checked_base, {gamma[0], gamma[1]}, {beta[0], beta[1]}};
+        hipLaunchKernelGGL(z_phase_b, dim3(P), dim3(256), 0, ctx->stream, totals, (int)nblk, src);
         if (zr == 8)
             hipLaunchKernelGGL(z_phase_c<8>, dim3(nblk, P), dim3(256), 0, ctx->stream, d_zv, n, totals);
         else
@@ -1200,7 +1245,8 @@ int sipp_k_z_columns(sipp_ctx* ctx, const air_spec_t* a, const uint64_t* d_trace
 // monomials with gl::add / gl::sub directly on raw operands (no product in between to canonicalise them): gl::sub(a, b) with b >= p
 // would be off by 2^32 - 1.  Every producer keeps this: the tree sweeps (ntt_tree.hip) and lde_column canonicalise at their last store
 // (gl::canon in the forward sweeps' store phase), the aux LDEs come from the same transforms.  A lazy store there would corrupt the
-// quotient and show only as a proof mismatch.
+// quotient and show only as a proof mismatch.  What the kernels do on canonical cells at the EDGES of that range (p - 1, 2^32 - 1, the
+// q * p carry, both routes of quotient_rest, alpha = 0 refused) is pinned cell by cell in tests/test_gpu_stark_quotient_cases.py.
 int sipp_k_quotient(sipp_ctx* ctx, const air_spec_t* a, uint32_t log_n, const uint64_t* d_lde, const uint64_t* d_zlde,
                     size_t lde_stride, const uint64_t* d_aux, const uint64_t alpha[2], const uint64_t beta[2],
                     const uint64_t gamma[2], uint64_t* d_out) {

@@ -276,6 +276,44 @@ def stark_verify(proof, cfg=None):
     return L.orc_stark_verify(proof, len(proof), C.byref(cfg))
 
 
+# ---------------- the STARK prover's stages on the caller's cells (oracle/stark.c; tests/_stark_quotient_cases.py) ----------------
+def _pair(v):
+    return np.asarray([int(x) for x in v], dtype=np.uint64)
+
+
+def z_columns(trace, n_main, checked_base, n_checked, beta, gamma):
+    """orc_z_columns: trace [n_main + 2 nc][N] -> the permutation products [2 nc][N]"""
+    L = load()
+    L.orc_z_columns.restype = None
+    L.orc_z_columns.argtypes = [u64p, C.c_size_t, C.c_int, C.c_int, C.c_int, u64p, u64p, u64p]
+    trace = np.ascontiguousarray(trace, dtype=np.uint64)
+    assert trace.shape[0] == n_main + 2 * n_checked
+    zv = np.zeros((2 * n_checked, trace.shape[1]), dtype=np.uint64)
+    L.orc_z_columns(trace.reshape(-1), trace.shape[1], n_main, checked_base, n_checked, _pair(beta), _pair(gamma), zv.reshape(-1))
+    return zv
+
+
+def quotient_points(air_index, log_n, lde, zlde, aux, alpha, beta, gamma, pos, slot=None):
+    """orc_quotient_points: orc_eval_base / Z_H at the leaf positions `pos` of device-layout tables (columns `lde.shape[1]` apart; with
+    `slot` the tables hold only the gathered positions slot maps to) -> [2][len(pos)]"""
+    L = load()
+    L.orc_air_by_index.restype = C.c_void_p
+    L.orc_air_by_index.argtypes = [C.c_int]
+    L.orc_quotient_points.restype = None
+    L.orc_quotient_points.argtypes = [C.c_void_p, C.c_uint, u64p, u64p, C.c_size_t, u64p, u64p, u64p, u64p, u32p, C.c_size_t, C.c_void_p, u64p]
+    air = L.orc_air_by_index(air_index)
+    assert air
+    lde, zlde = np.ascontiguousarray(lde, dtype=np.uint64), np.ascontiguousarray(zlde, dtype=np.uint64)
+    aux = np.ascontiguousarray(aux, dtype=np.uint64)
+    assert zlde.shape[1] == lde.shape[1] and (slot is not None or lde.shape[1] == aux.shape[1] == 2 << log_n)
+    pos = np.ascontiguousarray(pos, dtype=np.uint32)
+    slot = None if slot is None else np.ascontiguousarray(slot, dtype=np.uint32)
+    out = np.zeros((2, len(pos)), dtype=np.uint64)
+    L.orc_quotient_points(air, log_n, lde.reshape(-1), zlde.reshape(-1), lde.shape[1], aux.reshape(-1) if aux.size else np.zeros(1, dtype=np.uint64),
+                          _pair(alpha), _pair(beta), _pair(gamma), pos, len(pos), None if slot is None else slot.ctypes.data, out.reshape(-1))
+    return out
+
+
 # ---------------- generic opening proofs (oracle/fri.c) ----------------
 class OrcFriParams(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("rate_bits", "cap_height", "pow_bits", "num_queries", "pow_rule", "hiding", "n_rounds")] + \
