@@ -200,6 +200,26 @@ int sipp_instance_prove(sipp_ctx *const ctxs[3], const uint32_t *const ios[3], c
 int sipp_instances_prove(sipp_ctx *const *ctxs, size_t in_flight, size_t count, const uint32_t *const *ios,
                          const size_t *num_io, uint64_t *const *proof_out, const size_t *proof_cap, size_t *proof_len,
                          int *status);
+/* From the points to the three proofs: sipp_prove_native_ex(native_ctx, A, B, n) -- native_proof, statement, accepted as there, each
+ * may be NULL -- then sipp_instance_prove(ctxs) on the obligation lists it produced (n - 1, n - 1 and 2 log2 n records; n = 1 has none
+ * and yields three empty proofs).  native_ctx may be one of the three ctxs (the native stage has ended before the proofs start); its
+ * workspace is sipp_prove_native_ex's.  A refusal of the native stage is returned and no proof is attempted (proof_len 0). */
+int sipp_flow_prove(sipp_ctx *native_ctx, sipp_ctx *const ctxs[3], const uint32_t *A, const uint32_t *B, size_t n,
+                    uint32_t *native_proof, uint32_t *statement, uint64_t *const proof_out[3], const size_t proof_cap[3],
+                    size_t proof_len[3], int *accepted);
+/* sipp_instances_prove with a producer in front: `count` instances of n pairs each.  One host thread runs sipp_prove_native_ex for
+ * instance 0, 1, ... on native_ctx; the `in_flight` slots (ctxs[3 * slot + kind], as in sipp_instances_prove) take instance i as soon as
+ * its lists exist, so the latency-bound native stage of the next instance runs beside the hash-bound proofs of the current ones.
+ * A[i], B[i]: the points; native_proof[i], statement[i], accepted[i], status[i]: per instance, the ARRAYS native_proof / statement /
+ * accepted / status and the entries of the first two may be NULL; proof_out / proof_cap / proof_len [3 i + kind].
+ * native_ctx equal to a slot ctx, duplicate slot ctxs, a NULL A[i] / B[i] (or proof_out entry, n > 1): SIPP_E_BADARG before anything
+ * starts.  An instance whose native stage is refused gets that code in status[i] and proof_len 0 and no proof is attempted for it;
+ * every other instance is still proved.  Returns the first failing status BY INSTANCE INDEX.  count = 0 is SIPP_OK.  The lists of the
+ * instances the producer is ahead by are held on the host (160 (n - 1) + 2368 log2 n u32 each). */
+int sipp_flows_prove(sipp_ctx *native_ctx, sipp_ctx *const *ctxs, size_t in_flight, size_t count, size_t n,
+                     const uint32_t *const *A, const uint32_t *const *B, uint32_t *const *native_proof,
+                     uint32_t *const *statement, uint64_t *const *proof_out, const size_t *proof_cap, size_t *proof_len,
+                     int *accepted, int *status);
 /* IO-sharded sub-proofs (level L-D): the obligation list of one kind is cut into
  * `world` contiguous, balanced ranges and every rank proves ITS range as a STARK of its own -- on the reference side one
  * g1_exp_circuit / g2_exp_circuit / fq12_exp_circuit call per range instead of one per list (src/verifier_circuit.rs:133-135
@@ -303,6 +323,22 @@ size_t sipp_native_proof_words(size_t n);
 int sipp_prove_native(sipp_ctx *ctx, const uint32_t *A, const uint32_t *B, size_t n, uint32_t *proof);
 int sipp_verify_native(sipp_ctx *ctx, const uint32_t *A, const uint32_t *B, size_t n, const uint32_t *proof,
                        uint32_t *statement, uint32_t *g1_ios, uint32_t *g2_ios, uint32_t *fq12_ios, int *accepted);
+/* Both in ONE pass: the prover's loop, with the verifier's outputs taken on the way instead of folded a second time.
+ *   proof                       sipp_prove_native(A, B)'s, word for word;
+ *   statement, the three lists  what sipp_verify_native(A, B, that proof) returns, word for word (layouts above), and so is
+ *   *accepted                   (pairing(final_A, final_B) == final_Z; that pairing is launched only when the pointer is not NULL).
+ * ANY output pointer may be NULL.  The G1 / G2 lists are the records every round's fold leaves complete; the Fq12 list is one pass over
+ * the 2 log2 n powers Z_L^x, Z_R^(1/x) after the last challenge, with the running product on the host as in sipp_verify_native.  With
+ * statement, fq12_ios and accepted all NULL nothing is launched that sipp_prove_native does not launch (g1_ios / g2_ios cost two host
+ * copies per round).  n = 1 has no round: the lists are empty, final_A / final_B are the inputs and final_Z = Z.
+ * Workspace: the widest fold, sipp_workspace_bytes(SIPP_G2_EXP, n / 2), as for sipp_prove_native; and, when statement, fq12_ios or
+ * accepted is asked for, the Fq12 trace of the powers, sipp_workspace_bytes(SIPP_FQ12_EXP, 2 log2 n) -- one after the other, so the
+ * larger of the two.  Refusals are sipp_prove_native's: SIPP_E_BADARG (n no power of two, a NULL ctx / A / B), SIPP_E_WITNESS (infinity,
+ * a point off its curve, a fold through infinity), and SIPP_E_NOMEM, also for a workspace that holds the fold but not the Fq12 trace
+ * (returned after the folds; the outputs written until then are to be ignored).  After any refusal no fold is in flight, the workspace
+ * is handed back and the ctx works as before. */
+int sipp_prove_native_ex(sipp_ctx *ctx, const uint32_t *A, const uint32_t *B, size_t n, uint32_t *proof,
+                         uint32_t *statement, uint32_t *g1_ios, uint32_t *g2_ios, uint32_t *fq12_ios, int *accepted);
 
 /* ---- next row (SURVEY.md section 8f, rank 2 -- the generic half of the outer plonky2 prover) ---------------------------
  * PolynomialBatch commitments and FRI opening proofs for ARBITRARY FriParams: what reference src/verifier_circuit.rs:225

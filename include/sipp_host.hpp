@@ -582,6 +582,40 @@ class Prover {
         std::memcpy(&v.statement.final_Z, s + 144, sizeof(Fq12));
         return v;
     }
+    // both in one pass (::sipp_prove_native_ex): the prover's loop, the verifier's outputs taken on the way instead of folded twice
+    struct NativeProofAndVerification {
+        std::vector<Fq12> proof;
+        NativeVerification verification;
+    };
+    NativeProofAndVerification sipp_prove_native_ex(const std::vector<G1Affine>& A, const std::vector<G2Affine>& B) {
+        const size_t n = A.size();
+        if (n != B.size() || sipp_native_proof_words(n) == 0) throw Error(SIPP_E_BADARG, "sipp_prove_native_ex: |A| = |B| = 2^k");
+        size_t lg = 0;
+        while (((size_t)1 << lg) < n) lg++;
+        NativeProofAndVerification r;
+        r.proof.resize(2 * lg + 1);
+        NativeVerification& v = r.verification;
+        v.g1_obligations.resize(n - 1);
+        v.g2_obligations.resize(n - 1);
+        v.fq12_obligations.resize(2 * lg);
+        std::vector<uint32_t> st(48 * n + 240);
+        int ok = 0;
+        const int rc = ::sipp_prove_native_ex(ctx_[SIPP_G2_EXP], reinterpret_cast<const uint32_t*>(A.data()),
+                                              reinterpret_cast<const uint32_t*>(B.data()), n, reinterpret_cast<uint32_t*>(r.proof.data()),
+                                              st.data(), reinterpret_cast<uint32_t*>(v.g1_obligations.data()),
+                                              reinterpret_cast<uint32_t*>(v.g2_obligations.data()),
+                                              reinterpret_cast<uint32_t*>(v.fq12_obligations.data()), &ok);
+        if (rc != SIPP_OK) throw Error(rc, std::string("sipp_prove_native_ex: ") + sipp_last_error(ctx_[SIPP_G2_EXP]));
+        if (!ok) throw Error(SIPP_E_WITNESS, "Verification failed");
+        v.statement.A = A;
+        v.statement.B = B;
+        const uint32_t* s = st.data() + 48 * n;
+        std::memcpy(&v.statement.Z, s, sizeof(Fq12));
+        std::memcpy(&v.statement.final_A, s + 96, sizeof(G1Affine));
+        std::memcpy(&v.statement.final_B, s + 112, sizeof(G2Affine));
+        std::memcpy(&v.statement.final_Z, s + 144, sizeof(Fq12));
+        return r;
+    }
 
     sipp_ctx* ctx(int kind) { return ctx_[kind]; }
 

@@ -228,6 +228,15 @@ extern "C" {
     pub fn sipp_instances_prove(ctxs: *const *mut SippCtxOpaque, in_flight: usize, count: usize, ios: *const *const u32,
                                 num_io: *const usize, proof_out: *const *mut u64, proof_cap: *const usize, proof_len: *mut usize,
                                 status: *mut c_int) -> c_int;
+    /// the points of one instance -> its three proofs (sipp_prove_native_ex, then sipp_instance_prove)
+    pub fn sipp_flow_prove(native_ctx: *mut SippCtxOpaque, ctxs: *const *mut SippCtxOpaque, A: *const u32, B: *const u32, n: usize,
+                           native_proof: *mut u32, statement: *mut u32, proof_out: *const *mut u64, proof_cap: *const usize,
+                           proof_len: *mut usize, accepted: *mut c_int) -> c_int;
+    /// a queue of such flows: one producer thread for the native chains, `in_flight` slots of three ctxs for the proofs
+    pub fn sipp_flows_prove(native_ctx: *mut SippCtxOpaque, ctxs: *const *mut SippCtxOpaque, in_flight: usize, count: usize, n: usize,
+                            A: *const *const u32, B: *const *const u32, native_proof: *const *mut u32, statement: *const *mut u32,
+                            proof_out: *const *mut u64, proof_cap: *const usize, proof_len: *mut usize, accepted: *mut c_int,
+                            status: *mut c_int) -> c_int;
     /// range of an obligation list that GPU `rank` of `world` proves as a STARK of its own (level L-D)
     pub fn sipp_io_shard(num_io: usize, world: u32, rank: u32, first: *mut usize, count: *mut usize) -> c_int;
     pub fn sipp_exp_outputs(ctx: *mut SippCtxOpaque, kind: c_int, ios: *mut u32, num_io: usize) -> c_int;
@@ -275,6 +284,9 @@ extern "C" {
     pub fn sipp_prove_native(ctx: *mut SippCtxOpaque, A: *const u32, B: *const u32, n: usize, proof: *mut u32) -> c_int;
     pub fn sipp_verify_native(ctx: *mut SippCtxOpaque, A: *const u32, B: *const u32, n: usize, proof: *const u32, statement: *mut u32,
                               g1_ios: *mut u32, g2_ios: *mut u32, fq12_ios: *mut u32, accepted: *mut c_int) -> c_int;
+    /// prove and verify in one pass: the proof of sipp_prove_native, the statement / lists / accepted of sipp_verify_native
+    pub fn sipp_prove_native_ex(ctx: *mut SippCtxOpaque, A: *const u32, B: *const u32, n: usize, proof: *mut u32, statement: *mut u32,
+                                g1_ios: *mut u32, g2_ios: *mut u32, fq12_ios: *mut u32, accepted: *mut c_int) -> c_int;
     pub fn sipp_fri_const_arity(p: *mut SippFriParams, arity_bits: u32, final_poly_bits: u32, degree_bits: u32);
     pub fn sipp_commit_batch_ex(ctx: *mut SippCtxOpaque, d_in: *const u64, from_coeffs: c_int, d_coeffs: *mut u64, d_lde: *mut u64,
                                 d_tree: *mut u64, ncols: usize, log_n: u32, rate_bits: u32, cap_height: u32, d_salt: *const u64,

@@ -1,5 +1,6 @@
 """End to end on one GPU: points A, B -> sipp_prove_native -> sipp_verify_native (statement + obligation lists) ->
-sipp_instance_prove (three STARK proofs).  The flow of the reference's test_sipp_circuit without the outer plonky2 proof."""
+sipp_instance_prove (three STARK proofs), and beside it the same road as ONE call (sipp_flow_prove: the one-pass native chain
+sipp_prove_native_ex, then the proofs).  The flow of the reference's test_sipp_circuit without the outer plonky2 proof."""
 import os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -18,4 +19,9 @@ for it in range(3):
     t3 = time.perf_counter()
     print("n=%d pass %d: prove_native %.1f ms, verify_native %.1f ms, three STARK proofs %.1f ms, total %.1f ms (accepted %s, %d proof words)"
           % (n, it, 1e3 * (t1 - t0), 1e3 * (t2 - t1), 1e3 * (t3 - t2), 1e3 * (t3 - t0), ok, sum(len(p) for p in proofs)))
+    staged = [p.copy() for p in proofs]
+    t4 = time.perf_counter(); proofs, nproof, stm2, ok2 = inst.flow(nctx, A, B)
+    t5 = time.perf_counter()
+    same = (nproof == proof).all() and (stm2 == stm).all() and all(len(a) == len(b) and (a == b).all() for a, b in zip(proofs, staged))
+    print("n=%d pass %d: flow (one call) %.1f ms (accepted %s, the stage-by-stage words: %s)" % (n, it, 1e3 * (t5 - t4), ok2, same))
 inst.close()

@@ -167,6 +167,12 @@ SIGNATURES = {
     "sipp_native_proof_words": (C.c_size_t, [C.c_size_t]),
     "sipp_prove_native": (C.c_int, [vp, vp, vp, C.c_size_t, vp]),
     "sipp_verify_native": (C.c_int, [vp, vp, vp, C.c_size_t, vp, vp, vp, vp, vp, C.POINTER(C.c_int)]),
+    "sipp_prove_native_ex": (C.c_int, [vp, vp, vp, C.c_size_t, vp, vp, vp, vp, vp, C.POINTER(C.c_int)]),
+    "sipp_flow_prove": (C.c_int, [vp, C.POINTER(vp), vp, vp, C.c_size_t, vp, vp, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
+                                  C.POINTER(C.c_int)]),
+    "sipp_flows_prove": (C.c_int, [vp, C.POINTER(vp), C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
+                                   C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_int),
+                                   C.POINTER(C.c_int)]),
     "sipp_stark_verify": (C.c_int, [u64p, C.c_size_t, C.POINTER(StarkConfig), C.POINTER(C.c_int)]),
     "sipp_fri_verify_openings": (C.c_int, [u64p, C.c_size_t, C.POINTER(u64p), u32p, u32p, C.c_size_t, C.POINTER(FriBatch), C.c_size_t, C.c_uint32,
                                            C.POINTER(FriParams), C.POINTER(Challenger), C.POINTER(C.c_int)]),
@@ -426,6 +432,36 @@ def to_device(arr):
 
 def to_host(t):
     return t.detach().cpu().numpy().view(np.uint64)
+
+
+def native_points(A, B, what="native"):
+    """the points of one SIPP instance as the native chain takes them: A [n, 16], B [n, 32] uint32 limbs, n a power of two ->
+    (A, B, n, log2 n); SippError(SIPP_E_BADARG) for anything else, before any call into the library"""
+    A = np.ascontiguousarray(A, dtype=np.uint32)
+    B = np.ascontiguousarray(B, dtype=np.uint32)
+    if A.size == 0 or A.size % 16 or B.size % 32:
+        raise SippError(-1, "%s: A must be [n, 16] and B [n, 32] uint32 limbs" % what)
+    A, B = A.reshape(-1, 16), B.reshape(-1, 32)
+    n = A.shape[0]
+    if B.shape[0] != n or n & (n - 1):
+        raise SippError(-1, "%s: |A| = |B| = n must be a power of two" % what)
+    return A, B, n, n.bit_length() - 1
+
+
+def native_output_shapes(n):
+    """shapes of what the native chain returns for n pairs (include/sipp_hip.h): proof, statement, the three obligation lists"""
+    lg = n.bit_length() - 1
+    return {"proof": (2 * lg + 1, 96), "statement": (48 * n + 240,), "g1": (n - 1, 56), "g2": (n - 1, 104), "fq12": (2 * lg, 296)}
+
+
+def _native_out(out, key, shape, what):
+    """the caller's array for output `key` (C-contiguous uint32 of exactly `shape`) or a fresh zeroed one"""
+    if out is None or key not in out:
+        return np.zeros(shape, dtype=np.uint32)
+    a = out[key]
+    if not isinstance(a, np.ndarray) or a.dtype != np.uint32 or a.shape != tuple(shape) or not a.flags.c_contiguous or not a.flags.writeable:
+        raise SippError(-1, "%s: out[%r] must be a writeable C-contiguous uint32 array of shape %r" % (what, key, tuple(shape)))
+    return a
 
 
 class Ctx:
@@ -844,6 +880,24 @@ class Ctx:
                  "verify_native")
         return bool(ok.value), st, ios
 
+    def prove_native_ex(self, A, B, lists=True, check=True, statement=True, out=None):
+        """sipp_prove_native_ex: prove_native and verify_native in one pass -> (proof, accepted, statement, [g1_ios, g2_ios, fq12_ios]).
+        lists=False / statement=False / check=False pass NULL for the three lists / the statement / `accepted` and return None in
+        their place (all three off: what prove_native launches and nothing more).  out: optional dict of caller arrays keyed "proof",
+        "statement", "g1", "g2", "fq12" (native_output_shapes(n)); an output that is asked for is written into the caller's array,
+        one that is not asked for is never handed to the library."""
+        A, B, n, _ = native_points(A, B, "prove_native_ex")
+        shp = native_output_shapes(n)
+        proof = _native_out(out, "proof", shp["proof"], "prove_native_ex")
+        st = _native_out(out, "statement", shp["statement"], "prove_native_ex") if statement else None
+        ios = [_native_out(out, k, shp[k], "prove_native_ex") for k in ("g1", "g2", "fq12")] if lists else None
+        ok = C.c_int(0)
+        ptr = lambda a: None if a is None else a.ctypes.data
+        self._ck(self.L.sipp_prove_native_ex(self.h, A.ctypes.data, B.ctypes.data, n, proof.ctypes.data, ptr(st),
+                                             ptr(ios and ios[0]), ptr(ios and ios[1]), ptr(ios and ios[2]),
+                                             C.byref(ok) if check else None), "prove_native_ex")
+        return proof, (bool(ok.value) if check else None), st, ios
+
     def prove_async(self, kind, ios):
         """start one sub-proof on the ctx's worker thread (sipp_prove_async); collect it with wait()"""
         ios = np.ascontiguousarray(ios, dtype=np.uint32)
@@ -956,6 +1010,26 @@ class Instance:
             raise SippError(rc, "instance_prove: " + msgs)
         return [self.out[k][: pl[k]] for k in range(3)]
 
+    def flow(self, native_ctx, A, B):
+        """sipp_flow_prove: the points A [n, 16], B [n, 32] -> (three flat proofs, native proof, statement, accepted).  native_ctx:
+        the Ctx of the native chain (it may be one of this object's); this object's num_io must be (n - 1, n - 1, 2 log2 n)."""
+        A, B, n, lg = native_points(A, B, "flow")
+        if self.num_io != (n - 1, n - 1, 2 * lg):
+            raise SippError(-1, "flow: this Instance was sized for num_io = %r, n = %d needs %r" % (self.num_io, n, (n - 1, n - 1, 2 * lg)))
+        shp = native_output_shapes(n)
+        nproof, st = np.zeros(shp["proof"], dtype=np.uint32), np.zeros(shp["statement"], dtype=np.uint32)
+        h = (vp * 3)(*[c.h for c in self.ctxs])
+        po = (vp * 3)(*[o.ctypes.data for o in self.out])
+        pc = (C.c_size_t * 3)(*self.caps)
+        pl = (C.c_size_t * 3)()
+        ok = C.c_int(0)
+        rc = self.L.sipp_flow_prove(native_ctx.h, h, A.ctypes.data, B.ctypes.data, n, nproof.ctypes.data, st.ctypes.data, po, pc, pl,
+                                    C.byref(ok))
+        if rc != 0:
+            msgs = "; ".join(self.L.sipp_last_error(c.h).decode() for c in [native_ctx] + self.distinct_ctxs())
+            raise SippError(rc, "flow_prove: " + msgs)
+        return [self.out[k][: pl[k]] for k in range(3)], nproof, st, bool(ok.value)
+
     def distinct_ctxs(self):
         return self.ctxs[:1] if getattr(self, "single_ctx", False) else list(self.ctxs)
 
@@ -1012,6 +1086,47 @@ class InstanceQueue:
             msgs = "; ".join(self.L.sipp_last_error(c.h).decode() for s in self.slots for c in s.ctxs)
             raise SippError(rc, "instances_prove: " + msgs)
         return [[outs[i][k][: pl[3 * i + k]] for k in range(3)] for i in range(count)]
+
+    def flows(self, native_ctx, instances, raise_on_error=True):
+        """sipp_flows_prove: instances = list of (A [n, 16], B [n, 32]), all of one n with (n - 1, n - 1, 2 log2 n) = this queue's num_io.
+        The native chain of every instance runs on native_ctx (a Ctx that is none of the slots') beside the proofs of the instances
+        before it.  Returns a list of (three flat proofs, native proof, statement, accepted), copies.  raise_on_error=False returns
+        (rc, status list, that list) instead of raising; an instance that failed has empty proofs."""
+        count, F = len(instances), len(self.slots)
+        n = None
+        keep = []
+        for A, B in instances:
+            A, B, ni, lg = native_points(A, B, "flows")
+            if n is None:
+                n = ni
+            if ni != n or self.num_io != (ni - 1, ni - 1, 2 * lg):
+                raise SippError(-1, "flows: every instance must have the n this queue was sized for (num_io = %r)" % (self.num_io,))
+            keep.append((A, B))
+        if n is None:                              # an empty queue: n follows from num_io
+            n = self.num_io[0] + 1
+        shp = native_output_shapes(n)
+        caps = self.slots[0].caps
+        outs = [[np.zeros(max(c, 1), dtype=np.uint64) for c in caps] for _ in range(count)]
+        nproofs = [np.zeros(shp["proof"], dtype=np.uint32) for _ in range(count)]
+        sts = [np.zeros(shp["statement"], dtype=np.uint32) for _ in range(count)]
+        h = (vp * (3 * F))(*[c.h for s in self.slots for c in s.ctxs])
+        pa = (vp * count)(*[a.ctypes.data for a, _ in keep])
+        pb = (vp * count)(*[b.ctypes.data for _, b in keep])
+        pn = (vp * count)(*[a.ctypes.data for a in nproofs])
+        ps = (vp * count)(*[a.ctypes.data for a in sts])
+        po = (vp * (3 * count))(*[o.ctypes.data for inst in outs for o in inst])
+        pc = (C.c_size_t * (3 * count))(*[c for _ in range(count) for c in caps])
+        pl = (C.c_size_t * (3 * count))()
+        acc = (C.c_int * count)()
+        st = (C.c_int * count)()
+        rc = self.L.sipp_flows_prove(native_ctx.h, h, F, count, n, pa, pb, pn, ps, po, pc, pl, acc, st)
+        res = [([outs[i][k][: pl[3 * i + k]] for k in range(3)], nproofs[i], sts[i], bool(acc[i])) for i in range(count)]
+        if not raise_on_error:
+            return rc, list(st), res
+        if rc != 0:
+            msgs = "; ".join(self.L.sipp_last_error(c.h).decode() for c in [native_ctx] + [c for s in self.slots for c in s.ctxs])
+            raise SippError(rc, "flows_prove: " + msgs)
+        return res
 
     def close(self):
         for s in self.slots:

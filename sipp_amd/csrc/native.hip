@@ -265,20 +265,77 @@ int cross_products(sipp_ctx* ctx, const std::vector<uint32_t>& A, const std::vec
     return SIPP_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-size_t sipp_native_proof_words(size_t n) {
-    if (!is_pow2(n)) return 0;
-    size_t lg = 0;
-    while (((size_t)1 << lg) < n) lg++;
-    return (2 * lg + 1) * F12W;
+// The Fq12 obligation list of `rounds` rounds: all 2 log2 n powers Z_L^x, Z_R^(1/x) in ONE pass through the Fq12 chain kernel
+// (offset 1), and the running product Z <- Z Z_L^x Z_R^(1/x) on the host.  The obligations are {x: Z_L, offset: Z, exp_val: x} and
+// {x: Z_R, offset: Z Z_L^x, exp_val: 1/x} (verifier_circuit.rs:111-124).  zls / zrs: the messages of round r; xs / ixs: 8 u32 per
+// round; Z: the product <A, B> on entry, final_Z on return; f12rec: 2 rounds complete records.  What the verifier and the one-pass
+// prover share.
+int fq12_obligations(sipp_ctx* ctx, size_t rounds, const std::vector<const uint32_t*>& zls, const std::vector<const uint32_t*>& zrs,
+                     const std::vector<uint32_t>& xs, const std::vector<uint32_t>& ixs, uint32_t Z[96], std::vector<uint32_t>& f12rec) {
+    f12rec.assign(2 * rounds * SIPP_FQ12_IO_WORDS, 0);
+    if (!rounds) return SIPP_OK;
+    std::vector<uint32_t> pw(2 * rounds * SIPP_FQ12_IO_WORDS, 0);
+    for (size_t r = 0; r < rounds; r++)
+        for (int h = 0; h < 2; h++) {
+            uint32_t* p = &pw[(2 * r + h) * SIPP_FQ12_IO_WORDS];
+            memcpy(p, h ? zrs[r] : zls[r], 96 * 4);
+            p[96] = 1;  // offset = 1
+            memcpy(p + 192, h ? &ixs[r * 8] : &xs[r * 8], 32);
+        }
+    SIPP_TRY(sipp_exp_outputs(ctx, SIPP_FQ12_EXP, pw.data(), 2 * rounds));
+    for (size_t r = 0; r < rounds; r++)
+        for (int h = 0; h < 2; h++) {
+            uint32_t* rec = &f12rec[(2 * r + h) * SIPP_FQ12_IO_WORDS];
+            const uint32_t* p = &pw[(2 * r + h) * SIPP_FQ12_IO_WORDS];
+            memcpy(rec, p, 96 * 4);
+            memcpy(rec + 96, Z, 96 * 4);
+            memcpy(rec + 192, p + 192, 32);
+            f12_mul_host(Z, p + 200, rec + 200);
+            memcpy(Z, rec + 200, 96 * 4);
+        }
+    return SIPP_OK;
 }
 
-int sipp_prove_native(sipp_ctx* ctx, const uint32_t* A_in, const uint32_t* B_in, size_t n, uint32_t* proof) {
-    if (!ctx || !A_in || !B_in || !proof) return SIPP_E_BADARG;
-    if (!is_pow2(n)) return sipp_fail(ctx, SIPP_E_BADARG, "prove_native: n must be a power of two");
+// A | B | Z | final_A | final_B | final_Z (statements.rs:24-39)
+void write_statement(uint32_t* s, const uint32_t* A_in, const uint32_t* B_in, size_t n0, const uint32_t* orig_Z, const uint32_t* final_A,
+                     const uint32_t* final_B, const uint32_t* final_Z) {
+    memcpy(s, A_in, n0 * G1W * 4);
+    s += n0 * G1W;
+    memcpy(s, B_in, n0 * G2W * 4);
+    s += n0 * G2W;
+    memcpy(s, orig_Z, 96 * 4);
+    s += 96;
+    memcpy(s, final_A, G1W * 4);
+    s += G1W;
+    memcpy(s, final_B, G2W * 4);
+    s += G2W;
+    memcpy(s, final_Z, 96 * 4);
+}
+
+// verifier_native.rs:80-84: pairing(final_A, final_B) == final_Z
+int final_check(sipp_ctx* ctx, const uint32_t* final_A, const uint32_t* final_B, const uint32_t* final_Z, int* accepted) {
+    uint32_t e[96];
+    SIPP_TRY(sipp_inner_product(ctx, final_A, final_B, 1, e));
+    *accepted = memcmp(e, final_Z, sizeof e) == 0;
+    return SIPP_OK;
+}
+
+// The prover's loop with the verifier's outputs taken on the way (sipp_prove_native_ex; sipp_prove_native is the call with every
+// second-half pointer NULL, which launches nothing the loop does not need): the G1 / G2 obligations of a round are the rec1 / rec2
+// that sipp_fold_finish leaves complete, the Fq12 list is one pass over the 2 log2 n powers after the last challenge.
+int prove_native_impl(sipp_ctx* ctx, const char* who, const uint32_t* A_in, const uint32_t* B_in, size_t n, uint32_t* proof,
+                      uint32_t* statement, uint32_t* g1_ios, uint32_t* g2_ios, uint32_t* fq12_ios, int* accepted) {
+    if (!is_pow2(n)) {
+        char msg[64];
+        snprintf(msg, sizeof msg, "%s: n must be a power of two", who);
+        return sipp_fail(ctx, SIPP_E_BADARG, msg);
+    }
+    const size_t n0 = n;
+    size_t rounds = 0;
+    while (((size_t)1 << rounds) < n) rounds++;
+    const bool want_z = statement || fq12_ios || accepted;  // final_Z comes from the Fq12 chain
+    std::vector<uint32_t> xs, ixs;                          // the challenges and their inverses, 8 u32 per round
+    size_t o1 = 0, o2 = 0;
     std::vector<uint32_t> A(A_in, A_in + n * G1W), B(B_in, B_in + n * G2W);
     Transcript t;
     for (size_t i = 0; i < n; i++) {  // register A and B (prover_native.rs:35-39)
@@ -286,6 +343,7 @@ int sipp_prove_native(sipp_ctx* ctx, const uint32_t* A_in, const uint32_t* B_in,
         t.append(&B[i * G2W], G2W);
     }
     std::vector<uint32_t> msgs;  // in sending order; reversed at the end (prover_native.rs:78)
+    msgs.reserve((2 * rounds + 1) * 96);
     uint32_t z[96], zl[96], zr[96];
     bool have_first = false, fold_started = false;
     std::vector<uint32_t> rec1, rec2;
@@ -352,12 +410,57 @@ int sipp_prove_native(sipp_ctx* ctx, const uint32_t* A_in, const uint32_t* B_in,
         fold_records(A, B, n, xw, ixw, rec1, rec2);
         fold_started = false;
         SIPP_TRY(sipp_fold_finish(ctx, rec1.data(), n / 2, rec2.data(), n / 2));
+        if (g1_ios) memcpy(g1_ios + o1, rec1.data(), rec1.size() * 4);  // round-major, as the verifier writes them
+        if (g2_ios) memcpy(g2_ios + o2, rec2.data(), rec2.size() * 4);
+        o1 += rec1.size();
+        o2 += rec2.size();
+        if (want_z) {
+            xs.insert(xs.end(), xw, xw + 8);
+            ixs.insert(ixs.end(), ixw, ixw + 8);
+        }
         take_outputs(rec1, rec2, n / 2, A, B);
         n /= 2;
     }
     const size_t cnt = msgs.size() / 96;
-    for (size_t i = 0; i < cnt; i++) memcpy(proof + i * 96, &msgs[(cnt - 1 - i) * 96], 96 * 4);
+    if (proof)
+        for (size_t i = 0; i < cnt; i++) memcpy(proof + i * 96, &msgs[(cnt - 1 - i) * 96], 96 * 4);
+    if (!want_z) return SIPP_OK;
+    // no fold is in flight here: a refusal of the Fq12 pass (SIPP_E_NOMEM for a workspace that holds the fold only) leaves the ctx clean
+    uint32_t Z[96];
+    memcpy(Z, &msgs[0], 96 * 4);
+    std::vector<const uint32_t*> zls(rounds), zrs(rounds);
+    for (size_t r = 0; r < rounds; r++) {
+        zls[r] = &msgs[(1 + 2 * r) * 96];
+        zrs[r] = &msgs[(2 + 2 * r) * 96];
+    }
+    std::vector<uint32_t> f12rec;
+    SIPP_TRY(fq12_obligations(ctx, rounds, zls, zrs, xs, ixs, Z, f12rec));
+    if (fq12_ios && !f12rec.empty()) memcpy(fq12_ios, f12rec.data(), f12rec.size() * 4);
+    if (statement) write_statement(statement, A_in, B_in, n0, &msgs[0], A.data(), B.data(), Z);
+    if (accepted) SIPP_TRY(final_check(ctx, A.data(), B.data(), Z, accepted));
     return SIPP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t sipp_native_proof_words(size_t n) {
+    if (!is_pow2(n)) return 0;
+    size_t lg = 0;
+    while (((size_t)1 << lg) < n) lg++;
+    return (2 * lg + 1) * F12W;
+}
+
+int sipp_prove_native(sipp_ctx* ctx, const uint32_t* A_in, const uint32_t* B_in, size_t n, uint32_t* proof) {
+    if (!ctx || !A_in || !B_in || !proof) return SIPP_E_BADARG;
+    return prove_native_impl(ctx, "prove_native", A_in, B_in, n, proof, nullptr, nullptr, nullptr, nullptr, nullptr);
+}
+
+int sipp_prove_native_ex(sipp_ctx* ctx, const uint32_t* A_in, const uint32_t* B_in, size_t n, uint32_t* proof, uint32_t* statement,
+                         uint32_t* g1_ios, uint32_t* g2_ios, uint32_t* fq12_ios, int* accepted) {
+    if (!ctx || !A_in || !B_in) return SIPP_E_BADARG;
+    return prove_native_impl(ctx, "prove_native_ex", A_in, B_in, n, proof, statement, g1_ios, g2_ios, fq12_ios, accepted);
 }
 
 int sipp_verify_native(sipp_ctx* ctx, const uint32_t* A_in, const uint32_t* B_in, size_t n0, const uint32_t* proof,
@@ -390,10 +493,8 @@ int sipp_verify_native(sipp_ctx* ctx, const uint32_t* A_in, const uint32_t* B_in
         to_u32(x, &xs[r * 8]);
         to_u32(inv_mod_r(x), &ixs[r * 8]);
     }
-    // ... then all 2 log2 n powers Z_L^x, Z_R^(1/x) in ONE pass through the Fq12 chain kernel (offset 1), and the running
-    // product Z <- Z Z_L^x Z_R^(1/x) on the host.  The obligations are {x: Z_L, offset: Z, exp_val: x} and
-    // {x: Z_R, offset: Z Z_L^x, exp_val: 1/x} (verifier_circuit.rs:111-124).
-    std::vector<uint32_t> f12rec(2 * rounds * SIPP_FQ12_IO_WORDS, 0);
+    // ... then the Fq12 list and the running product Z in one pass (fq12_obligations)
+    std::vector<uint32_t> f12rec;
     // the first round's doubling chains (side streams) run beside the Fq12 powers (main stream)
     std::vector<uint32_t> rec1_0, rec2_0;
     bool fold0 = false;
@@ -401,31 +502,11 @@ int sipp_verify_native(sipp_ctx* ctx, const uint32_t* A_in, const uint32_t* B_in
         fold_records(A, B, n, &xs[0], &ixs[0], rec1_0, rec2_0);
         SIPP_TRY(sipp_fold_begin(ctx, rec1_0.data(), n / 2, rec2_0.data(), n / 2));
         fold0 = true;
-        std::vector<uint32_t> pw(2 * rounds * SIPP_FQ12_IO_WORDS, 0);
-        for (size_t r = 0; r < rounds; r++)
-            for (int h = 0; h < 2; h++) {
-                uint32_t* p = &pw[(2 * r + h) * SIPP_FQ12_IO_WORDS];
-                memcpy(p, h ? zrs[r] : zls[r], 96 * 4);
-                p[96] = 1;  // offset = 1
-                memcpy(p + 192, h ? &ixs[r * 8] : &xs[r * 8], 32);
-            }
-        {
-            const int rc = sipp_exp_outputs(ctx, SIPP_FQ12_EXP, pw.data(), 2 * rounds);
-            if (rc != SIPP_OK) {
-                (void)sipp_fold_finish(ctx, rec1_0.data(), n / 2, rec2_0.data(), n / 2);
-                return rc;
-            }
+        const int rc = fq12_obligations(ctx, rounds, zls, zrs, xs, ixs, Z, f12rec);
+        if (rc != SIPP_OK) {
+            (void)sipp_fold_finish(ctx, rec1_0.data(), n / 2, rec2_0.data(), n / 2);
+            return rc;
         }
-        for (size_t r = 0; r < rounds; r++)
-            for (int h = 0; h < 2; h++) {
-                uint32_t* rec = &f12rec[(2 * r + h) * SIPP_FQ12_IO_WORDS];
-                const uint32_t* p = &pw[(2 * r + h) * SIPP_FQ12_IO_WORDS];
-                memcpy(rec, p, 96 * 4);
-                memcpy(rec + 96, Z, 96 * 4);
-                memcpy(rec + 192, p + 192, 32);
-                f12_mul_host(Z, p + 200, rec + 200);
-                memcpy(Z, rec + 200, 96 * 4);
-            }
         if (fq12_ios) memcpy(fq12_ios, f12rec.data(), f12rec.size() * 4);
     }
     size_t o1 = 0, o2 = 0;
@@ -445,25 +526,8 @@ int sipp_verify_native(sipp_ctx* ctx, const uint32_t* A_in, const uint32_t* B_in
         take_outputs(rec1, rec2, n / 2, A, B);
         n /= 2;
     }
-    if (statement) {  // A | B | Z | final_A | final_B | final_Z (statements.rs:24-39)
-        uint32_t* s = statement;
-        memcpy(s, A_in, n0 * G1W * 4);
-        s += n0 * G1W;
-        memcpy(s, B_in, n0 * G2W * 4);
-        s += n0 * G2W;
-        memcpy(s, orig_Z, 96 * 4);
-        s += 96;
-        memcpy(s, A.data(), G1W * 4);
-        s += G1W;
-        memcpy(s, B.data(), G2W * 4);
-        s += G2W;
-        memcpy(s, Z, 96 * 4);
-    }
-    if (accepted) {  // verifier_native.rs:80-84: pairing(final_A, final_B) == final_Z
-        uint32_t e[96];
-        SIPP_TRY(sipp_inner_product(ctx, A.data(), B.data(), 1, e));
-        *accepted = memcmp(e, Z, sizeof e) == 0;
-    }
+    if (statement) write_statement(statement, A_in, B_in, n0, orig_Z, A.data(), B.data(), Z);
+    if (accepted) SIPP_TRY(final_check(ctx, A.data(), B.data(), Z, accepted));
     return SIPP_OK;
 }
 
