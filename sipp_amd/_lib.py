@@ -78,6 +78,11 @@ class PlonkGenerator(C.Structure):
     _fields_ = [("kind", C.c_uint32), ("selector_index", C.c_uint32), ("row", C.c_uint32), ("p", C.c_uint32 * 5)]
 
 
+def _gen_array(gens):
+    """gens = [(kind, selector_index, row, p0 .. p4)] as the array the C calls take (one unused element for an empty list)"""
+    return (PlonkGenerator * max(1, len(gens)))(*[PlonkGenerator(int(g[0]), int(g[1]), int(g[2]), (C.c_uint32 * 5)(*[int(x) for x in g[3:8]])) for g in gens])
+
+
 class PlonkSchedule(C.Structure):
     """sipp_plonk_schedule: rows sorted by level + the copies each level's outputs feed (include/sipp_hip.h)"""
     _fields_ = [("n_levels", C.c_uint32), ("d_rows", C.c_void_p), ("level_offsets", C.POINTER(C.c_uint32)), ("d_copy_src", C.c_void_p),
@@ -344,17 +349,22 @@ def host_merkle_hash(hasher, elements, right=None):
     return out
 
 
-def plonk_verify_gates_h(proof, constants_sigmas_cap, p, fp, circuit, digest, lookup, hasher):
-    """sipp_plonk_verify_gates_h: plonk_verify_gates_lookup (lookup may be None) with the tree hasher.  Returns 0 or the refusing stage."""
+def _verify_gates(name, proof, constants_sigmas_cap, p, fp, circuit, digest, extra):
+    """what plonk_verify_gates_lookup / _h share: the call `name` with `extra` between the digest and the reason -> 0 or the refusing stage"""
     pf = np.ascontiguousarray(proof, dtype=np.uint64)
     cap = np.ascontiguousarray(constants_sigmas_cap, dtype=np.uint64).reshape(-1)
     reason = C.c_int(0)
-    rc = lib().sipp_plonk_verify_gates_h(pf.ctypes.data_as(u64p), len(pf), cap.ctypes.data_as(u64p), C.byref(p), C.byref(fp), C.byref(circuit),
-                                         (C.c_uint64 * 4)(*[int(x) for x in digest]), None if lookup is None else Ctx._lookup_words(lookup),
-                                         hasher_id(hasher), C.byref(reason))
+    rc = getattr(lib(), name)(pf.ctypes.data_as(u64p), len(pf), cap.ctypes.data_as(u64p), C.byref(p), C.byref(fp), C.byref(circuit),
+                              (C.c_uint64 * 4)(*[int(x) for x in digest]), *extra, C.byref(reason))
     if rc not in (0, SIPP_E_VERIFY):
-        raise SippError(rc, "sipp_plonk_verify_gates_h")
+        raise SippError(rc, name)
     return reason.value
+
+
+def plonk_verify_gates_h(proof, constants_sigmas_cap, p, fp, circuit, digest, lookup, hasher):
+    """sipp_plonk_verify_gates_h: plonk_verify_gates_lookup (lookup may be None) with the tree hasher.  Returns 0 or the refusing stage."""
+    return _verify_gates("sipp_plonk_verify_gates_h", proof, constants_sigmas_cap, p, fp, circuit, digest,
+                         [None if lookup is None else Ctx._lookup_words(lookup), hasher_id(hasher)])
 
 
 def fri_verify_openings_h(proof, caps, ncols, n_salt, batches, log_n, params, challenger, hasher):
@@ -377,14 +387,7 @@ def plonk_verify_gates_lookup(proof, constants_sigmas_cap, p, fp, circuit, diges
     """sipp_plonk_verify_gates_lookup: the library's own check of a "SIPPPLK4" proof (host code; no ctx, no GPU) against the caller's
     lookup description (eight words; an empty one: a "SIPPPLK3" proof).  Under fp.hiding = 1 it accepts a "SIPPPLK5" proof alone, under
     hiding = 0 none.  Returns 0 for an accepted proof, else the refusing stage."""
-    pf = np.ascontiguousarray(proof, dtype=np.uint64)
-    cap = np.ascontiguousarray(constants_sigmas_cap, dtype=np.uint64).reshape(-1)
-    reason = C.c_int(0)
-    rc = lib().sipp_plonk_verify_gates_lookup(pf.ctypes.data_as(u64p), len(pf), cap.ctypes.data_as(u64p), C.byref(p), C.byref(fp), C.byref(circuit),
-                                              (C.c_uint64 * 4)(*[int(x) for x in digest]), Ctx._lookup_words(lookup), C.byref(reason))
-    if rc not in (0, SIPP_E_VERIFY):
-        raise SippError(rc, "sipp_plonk_verify_gates_lookup")
-    return reason.value
+    return _verify_gates("sipp_plonk_verify_gates_lookup", proof, constants_sigmas_cap, p, fp, circuit, digest, [Ctx._lookup_words(lookup)])
 
 
 def stark_verify(proof, cfg=None):
@@ -711,30 +714,34 @@ class Ctx:
         return self._plonk_prove("plonk_prove_ex", "sipp_plonk_perm_proof_size", cap and cap + len(pis), wires, sigmas, wires_oracle, wires_cap,
                                  sigmas_oracle, log_n, p, fp, None, digest, pis, extra)
 
+    def _prove_gates(self, fn, size_fn, size_extra, call_extra, wires, constants_sigmas, log_n, p, fp, circuit, digest, public_inputs,
+                     wires_oracle, wires_cap, cs_oracle):
+        """the four gates-as-data calls: sipp_<size_fn>(.., n_public_inputs, *size_extra) sizes the buffer of sipp_<fn>(.., *call_extra, buffer)"""
+        pis = [int(x) for x in public_inputs]
+        cap = getattr(self.L, "sipp_" + size_fn)(log_n, C.byref(p), C.byref(fp), C.byref(circuit), len(pis), *size_extra)
+        return self._plonk_prove(fn, "sipp_" + size_fn, cap, wires, constants_sigmas, wires_oracle, wires_cap, cs_oracle, log_n, p, fp, circuit,
+                                 digest, pis, call_extra)
+
     def plonk_prove_gates(self, wires, constants_sigmas, log_n, p, fp, circuit, digest, public_inputs, wires_oracle=None, wires_cap=None,
                           cs_oracle=None):
         """sipp_plonk_prove_gates: wires [num_wires][N], constants_sigmas [num_constants + num_routed][N] device tensors (values);
         circuit = PlonkCircuit; the gate constraints are interpreted inside the quotient kernel.  Returns the flat "SIPPPLK3" proof."""
-        pis = [int(x) for x in public_inputs]
-        cap = self.L.sipp_plonk_gates_proof_size(log_n, C.byref(p), C.byref(fp), C.byref(circuit), len(pis))
-        return self._plonk_prove("plonk_prove_gates", "sipp_plonk_gates_proof_size", cap, wires, constants_sigmas, wires_oracle, wires_cap,
-                                 cs_oracle, log_n, p, fp, circuit, digest, pis, [])
+        return self._prove_gates("plonk_prove_gates", "plonk_gates_proof_size", [], [], wires, constants_sigmas, log_n, p, fp, circuit, digest,
+                                 public_inputs, wires_oracle, wires_cap, cs_oracle)
 
     def plonk_prove_gates_lookup(self, wires, constants_sigmas, log_n, p, fp, circuit, digest, public_inputs, lookup, wires_oracle=None,
                                  wires_cap=None, cs_oracle=None):
         """sipp_plonk_prove_gates_lookup: plonk_prove_gates with a lookup description (eight words); the wire table holds the
         multiplicities already.  Returns the flat "SIPPPLK4" proof -- "SIPPPLK3", word for word plonk_prove_gates', for an empty one."""
-        pis = [int(x) for x in public_inputs]
         words = self._lookup_words(lookup)
-        cap = self.L.sipp_plonk_gates_lookup_proof_size(log_n, C.byref(p), C.byref(fp), C.byref(circuit), len(pis), words)
-        return self._plonk_prove("plonk_prove_gates_lookup", "sipp_plonk_gates_lookup_proof_size", cap, wires, constants_sigmas, wires_oracle,
-                                 wires_cap, cs_oracle, log_n, p, fp, circuit, digest, pis, [words])
+        return self._prove_gates("plonk_prove_gates_lookup", "plonk_gates_lookup_proof_size", [words], [words], wires, constants_sigmas, log_n, p,
+                                 fp, circuit, digest, public_inputs, wires_oracle, wires_cap, cs_oracle)
 
     def plonk_generate_witness(self, wires, constants, log_n, gens, pih=None, blind=None):
         """sipp_plonk_generate_witness: the gates' witness generators, in place on the device wire table [num_wires][N]; constants
         [>= num_constants][N] device tensor (the front of constants_sigmas); gens = [(kind, selector_index, row, p0 .. p4)];
         blind = Blinding (sipp_plonk_generate_witness_blind: what a SIPP_GEN_RANDOM generator needs) or None"""
-        arr = (PlonkGenerator * len(gens))(*[PlonkGenerator(int(g[0]), int(g[1]), int(g[2]), (C.c_uint32 * 5)(*[int(x) for x in g[3:8]])) for g in gens])
+        arr = _gen_array(gens)
         args = [self.h, wires.data_ptr(), constants.data_ptr(), log_n, wires.shape[0], constants.shape[0], arr, len(gens),
                 None if pih is None else self._u64([int(x) for x in pih])]
         if blind is None:
@@ -745,7 +752,7 @@ class Ctx:
     def plonk_generate_witness_levels(self, wires, constants, log_n, gens, pih, sched, blind=None):
         """sipp_plonk_generate_witness_levels: the generators level by level with the copies between levels (sched = PlonkSchedule);
         synchronises the ctx stream (the schedule's bounds are checked on the device).  blind: as in plonk_generate_witness"""
-        arr = (PlonkGenerator * len(gens))(*[PlonkGenerator(int(g[0]), int(g[1]), int(g[2]), (C.c_uint32 * 5)(*[int(x) for x in g[3:8]])) for g in gens])
+        arr = _gen_array(gens)
         args = [self.h, wires.data_ptr(), constants.data_ptr(), log_n, wires.shape[0], constants.shape[0], arr, len(gens),
                 None if pih is None else self._u64([int(x) for x in pih]), C.byref(sched)]
         if blind is None:
@@ -757,22 +764,18 @@ class Ctx:
                              wires_cap=None, cs_oracle=None):
         """sipp_plonk_prove_gates_zk: plonk_prove_gates_lookup with blind = Blinding (fp.hiding = 1: salted wires, Z / partial-products
         and quotient oracles, the flat "SIPPPLK5" proof) or None (that call, byte for byte)"""
-        pis = [int(x) for x in public_inputs]
         words = self._lookup_words(lookup)
-        cap = self.L.sipp_plonk_gates_zk_proof_size(log_n, C.byref(p), C.byref(fp), C.byref(circuit), len(pis), words)
-        return self._plonk_prove("plonk_prove_gates_zk", "sipp_plonk_gates_zk_proof_size", cap, wires, constants_sigmas, wires_oracle, wires_cap,
-                                 cs_oracle, log_n, p, fp, circuit, digest, pis, [words, None if blind is None else C.byref(blind)])
+        return self._prove_gates("plonk_prove_gates_zk", "plonk_gates_zk_proof_size", [words], [words, None if blind is None else C.byref(blind)],
+                                 wires, constants_sigmas, log_n, p, fp, circuit, digest, public_inputs, wires_oracle, wires_cap, cs_oracle)
 
     def plonk_prove_gates_h(self, wires, constants_sigmas, log_n, p, fp, circuit, digest, public_inputs, lookup, blind, hasher, wires_oracle=None,
                             wires_cap=None, cs_oracle=None):
         """sipp_plonk_prove_gates_h: plonk_prove_gates_zk (lookup and blind may each be None) with the tree hasher 'poseidon' / 'keccak';
         pre-committed oracles must have been committed with the same one.  The proof names the hasher in header word 13."""
-        pis = [int(x) for x in public_inputs]
         words = self._lookup_words(lookup if lookup is not None else (0,) * 8)
-        cap = self.L.sipp_plonk_gates_zk_proof_size(log_n, C.byref(p), C.byref(fp), C.byref(circuit), len(pis), words)
-        return self._plonk_prove("plonk_prove_gates_h", "sipp_plonk_gates_zk_proof_size", cap, wires, constants_sigmas, wires_oracle, wires_cap,
-                                 cs_oracle, log_n, p, fp, circuit, digest, pis,
-                                 [None if lookup is None else words, None if blind is None else C.byref(blind), hasher_id(hasher)])
+        return self._prove_gates("plonk_prove_gates_h", "plonk_gates_zk_proof_size", [words],
+                                 [None if lookup is None else words, None if blind is None else C.byref(blind), hasher_id(hasher)],
+                                 wires, constants_sigmas, log_n, p, fp, circuit, digest, public_inputs, wires_oracle, wires_cap, cs_oracle)
 
     def blind_salt(self, lde, ncols, log_m, blind, stream):
         """sipp_blind_salt: the four salt columns of stream 1 .. 3 behind the ncols polynomial columns of lde [ncols + 4, 2^log_m] (device
@@ -1145,7 +1148,7 @@ class CircuitData:
         self.ctx, self.L = ctx, ctx.L                      # the ctx must outlive this object
         self.circuit, self.params, self.fri = circuit, params, fri
         cs = np.ascontiguousarray(constants_sigmas, dtype=np.uint64)
-        arr = (PlonkGenerator * max(1, len(gens)))(*[PlonkGenerator(int(g[0]), int(g[1]), int(g[2]), (C.c_uint32 * 5)(*[int(x) for x in g[3:8]])) for g in gens])
+        arr = _gen_array(gens)
         self._sched = None if sched is None else PlonkScheduleHost.from_dict(sched)
         h = C.c_void_p()
         head = [ctx.h, log_n, C.byref(params), C.byref(fri), C.byref(circuit), cs.ctypes.data, arr, len(gens),

@@ -2,8 +2,9 @@
 // src/verifier_circuit.rs:225 (`builder.build::<C>()`: constants_sigmas committed once, the generators ordered once), :253 (`data.prove(pw)`)
 // and :254 (`data.verify(proof)`), for a caller that holds no device memory of its own (the Rust shim; include/sipp_host.hpp's CircuitData).
 // Nothing new is computed here: build = sipp_commit_batch_ex over the uploaded constants_sigmas; prove = upload of the wire table with its
-// input cells (or a scatter of the input cells alone into a zeroed table), sipp_plonk_generate_witness[_levels], sipp_plonk_prove_gates; verify = sipp_plonk_verify_gates with the data's own cap / digest.
-// Under a hiding fp (zero knowledge) the same through the _blind witness calls and sipp_plonk_prove_gates_zk, with the data's seed and the number of the proof.
+// input cells (or a scatter of the input cells alone into a zeroed table), sipp_plonk_generate_witness[_levels]_blind, the path behind
+// sipp_plonk_prove_gates* (sipp_prove_gates) with the data's lookup description, seed and number of the proof, and hasher; verify =
+// sipp_plonk_verify_gates_h with the data's own cap / digest.
 // Device memory of a circuit data is its own (hipMalloc at build: the arena of the ctx is the provers' scratch and empties after each proof).
 #include "ctx.hpp"
 #include "host_challenger.hpp"
@@ -206,7 +207,7 @@ extern "C" int sipp_circuit_verifier_data(const sipp_circuit_data* cd, uint64_t*
 }
 
 extern "C" size_t sipp_circuit_proof_size(const sipp_circuit_data* cd, uint32_t n_public_inputs) {
-    return cd ? sipp_plonk_gates_zk_proof_size(cd->log_n, &cd->p, &cd->fp, &cd->circ, n_public_inputs, cd->lookup) : 0;
+    return cd ? sipp_gates_proof_words(cd->log_n, &cd->p, &cd->fp, &cd->circ, n_public_inputs, cd->lookup, cd->fp.hiding != 0) : 0;
 }
 
 namespace {
@@ -240,23 +241,12 @@ int prove_uploaded(sipp_circuit_data* cd, const uint64_t* blind, const uint64_t*
     else
         SIPP_TRY(sipp_plonk_generate_witness_blind(ctx, cd->d_wires, cd->d_cs, cd->log_n, cd->circ.num_wires, cd->circ.num_constants,
                                                    cd->gens.data(), cd->gens.size(), pih, blind));
-    if (cd->hasher != SIPP_HASH_POSEIDON) {      // the one entry that takes a hasher serves all four kinds of proof
-        if (!cd->lk.empty()) SIPP_TRY(sipp_lookup_multiplicities_indexed(ctx, cd->d_wires, cd->d_cs, cd->log_n, cd->lk, cd->d_index, cd->n_index));
-        return sipp_plonk_prove_gates_h(ctx, cd->d_wires, cd->d_cs, nullptr, nullptr, &cd->cs_oracle, cd->log_n, &cd->p, &cd->fp, &cd->circ,
-                                        cd->digest, public_inputs, n_public_inputs, cd->lookup, blind, cd->hasher, proof_out, proof_cap, proof_len);
-    }
-    if (blind) {
-        if (!cd->lk.empty()) SIPP_TRY(sipp_lookup_multiplicities_indexed(ctx, cd->d_wires, cd->d_cs, cd->log_n, cd->lk, cd->d_index, cd->n_index));
-        return sipp_plonk_prove_gates_zk(ctx, cd->d_wires, cd->d_cs, nullptr, nullptr, &cd->cs_oracle, cd->log_n, &cd->p, &cd->fp, &cd->circ,
-                                         cd->digest, public_inputs, n_public_inputs, cd->lookup, blind, proof_out, proof_cap, proof_len);
-    }
-    if (cd->lk.empty())
-        return sipp_plonk_prove_gates(ctx, cd->d_wires, cd->d_cs, nullptr, nullptr, &cd->cs_oracle, cd->log_n, &cd->p, &cd->fp, &cd->circ, cd->digest,
-                                      public_inputs, n_public_inputs, proof_out, proof_cap, proof_len);
     // the multiplicities behind witness generation: the looking wires are the generators' outputs (or the caller's cells)
-    SIPP_TRY(sipp_lookup_multiplicities_indexed(ctx, cd->d_wires, cd->d_cs, cd->log_n, cd->lk, cd->d_index, cd->n_index));
-    return sipp_plonk_prove_gates_lookup(ctx, cd->d_wires, cd->d_cs, nullptr, nullptr, &cd->cs_oracle, cd->log_n, &cd->p, &cd->fp, &cd->circ,
-                                         cd->digest, public_inputs, n_public_inputs, cd->lookup, proof_out, proof_cap, proof_len);
+    if (!cd->lk.empty()) SIPP_TRY(sipp_lookup_multiplicities_indexed(ctx, cd->d_wires, cd->d_cs, cd->log_n, cd->lk, cd->d_index, cd->n_index));
+    const BlindArg arg(blind);      // the one path behind the sibling entries serves every kind of proof
+    const plonk_desc::ProveOptions o{cd->lookup, arg.p, cd->hasher};
+    return sipp_prove_gates(ctx, cd->d_wires, cd->d_cs, nullptr, nullptr, &cd->cs_oracle, cd->log_n, &cd->p, &cd->fp, &cd->circ, cd->digest, public_inputs,
+                            n_public_inputs, o, proof_out, proof_cap, proof_len);
 }
 
 // The input cells of a proof: pair k puts its value at cells[k], one lane per pair, grid-stride.  MAPPED: the value is
@@ -338,7 +328,7 @@ extern "C" int sipp_circuit_set_lookup(sipp_circuit_data* cd, const uint32_t* lo
     SIPP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
     std::vector<uint64_t> index;
     if (!l.empty()) {
-        if (sipp_plonk_gates_lookup_proof_size(cd->log_n, &cd->p, &cd->fp, &cd->circ, 0, lookup) == 0)
+        if (sipp_gates_proof_words(cd->log_n, &cd->p, &cd->fp, &cd->circ, 0, lookup, false) == 0)
             return sipp_fail(ctx, SIPP_E_BADARG, "circuit lookup: the description does not fit the parameters");
         SIPP_TRY(sipp_lookup_index_host(ctx, cd->d_cs, cd->log_n, l, &index));
         SIPP_TRY(replace_block(cd, &cd->d_index, {index.data()}, index.size(), "circuit lookup"));

@@ -269,6 +269,13 @@ int sipp_k_tree_fri_leaves(sipp_ctx* ctx, uint32_t hasher, const uint64_t* d_val
 int sipp_k_tree_levels(sipp_ctx* ctx, uint32_t hasher, uint64_t* d_tree, uint32_t log_leaves, uint32_t cap_height);
 void sipp_witness_graph_release(sipp_ctx* ctx);   // witness.hip
 int sipp_plonk_circuit_check(sipp_ctx* ctx, const sipp_plonk_circuit* c, const sipp_plonk_params* p);   // plonk.hip
+// plonk.hip -- the one path behind sipp_plonk_prove_gates{,_lookup,_zk,_h} and the gates*_proof_size entries (`zk`: salted oracles)
+int sipp_prove_gates(sipp_ctx* ctx, const uint64_t* d_wires, const uint64_t* d_constants_sigmas, const sipp_oracle* wires_oracle,
+                     const uint64_t* wires_cap, const sipp_oracle* constants_sigmas_oracle, uint32_t log_n, const sipp_plonk_params* p,
+                     const sipp_fri_params* fp, const sipp_plonk_circuit* c, const uint64_t circuit_digest[4], const uint64_t* public_inputs,
+                     uint32_t n_public_inputs, const plonk_desc::ProveOptions& o, uint64_t* proof_out, size_t proof_cap, size_t* proof_len);
+size_t sipp_gates_proof_words(uint32_t log_n, const sipp_plonk_params* p, const sipp_fri_params* fp, const sipp_plonk_circuit* c,
+                              uint32_t n_public_inputs, const uint32_t* lookup, bool zk);
 // lookup.hip -- a lookup description is the eight words of include/sipp_hip.h, read ONCE into plonk_desc::Lookup.  _check: that reading
 // and its refusals (an empty one passes); _index_host: the sorted index of the table's distinct pairs (kx | ky | cell | kt, a quarter of
 // the vector each), built once per circuit; _multiplicities_indexed: sipp_plonk_lookup_multiplicities over an index the caller keeps on

@@ -285,12 +285,6 @@ int sipp_plonk_zs_partial_products(sipp_ctx* ctx, const uint64_t* d_wires, const
     return sipp_sync(ctx);   // the scratch goes back with the scope
 }
 
-int sipp_plonk_quotient_chunks(sipp_ctx* ctx, const uint64_t* d_wires_lde, const uint64_t* d_sigmas_lde, const uint64_t* d_zs_lde, uint32_t log_n,
-                               uint32_t rate_bits, const sipp_plonk_params* p, const uint64_t* betas, const uint64_t* gammas,
-                               const uint64_t* alphas, uint64_t* d_chunks) {
-    return sipp_plonk_quotient_chunks_ex(ctx, d_wires_lde, d_sigmas_lde, d_zs_lde, log_n, rate_bits, p, betas, gammas, alphas, nullptr, 0, d_chunks);
-}
-
 namespace {
 // the gate set on the device: the constant columns' LDE, the circuit (host description, validated by the caller) and the hash of the public inputs
 struct GateSet {
@@ -304,19 +298,7 @@ struct LookupSet {
     const uint64_t *etas, *thetas;
     const uint64_t* d_sums_lde;
 };
-int quotient_chunks_impl(sipp_ctx* ctx, const uint64_t* d_wires_lde, const uint64_t* d_sigmas_lde, const uint64_t* d_zs_lde, uint32_t log_n,
-                         uint32_t rate_bits, const sipp_plonk_params* p, const uint64_t* betas, const uint64_t* gammas, const uint64_t* alphas,
-                         const uint64_t* d_gate_terms, uint32_t num_gate_terms, const GateSet* gs, const LookupSet* ls, uint64_t* d_chunks);
-}  // namespace
 
-int sipp_plonk_quotient_chunks_ex(sipp_ctx* ctx, const uint64_t* d_wires_lde, const uint64_t* d_sigmas_lde, const uint64_t* d_zs_lde, uint32_t log_n,
-                                  uint32_t rate_bits, const sipp_plonk_params* p, const uint64_t* betas, const uint64_t* gammas,
-                                  const uint64_t* alphas, const uint64_t* d_gate_terms, uint32_t num_gate_terms, uint64_t* d_chunks) {
-    return quotient_chunks_impl(ctx, d_wires_lde, d_sigmas_lde, d_zs_lde, log_n, rate_bits, p, betas, gammas, alphas, d_gate_terms, num_gate_terms,
-                                nullptr, nullptr, d_chunks);
-}
-
-namespace {
 // The gate programs compiled for one proof.  A gate's constraints are sums of monomials over the row's wires / constants / public-inputs
 // hash, and the prover needs only  sum_j alpha^(n0 + j) constraint_j  per challenge: exchanging the sums, every DISTINCT monomial of a gate
 // is evaluated once per point and weighted by B = sum over its occurrences (constraint j, coefficient) of alpha^(n0 + j) coefficient.
@@ -479,6 +461,19 @@ int quotient_chunks_impl(sipp_ctx* ctx, const uint64_t* d_wires_lde, const uint6
 }
 }  // namespace
 
+int sipp_plonk_quotient_chunks_ex(sipp_ctx* ctx, const uint64_t* d_wires_lde, const uint64_t* d_sigmas_lde, const uint64_t* d_zs_lde, uint32_t log_n,
+                                  uint32_t rate_bits, const sipp_plonk_params* p, const uint64_t* betas, const uint64_t* gammas,
+                                  const uint64_t* alphas, const uint64_t* d_gate_terms, uint32_t num_gate_terms, uint64_t* d_chunks) {
+    return quotient_chunks_impl(ctx, d_wires_lde, d_sigmas_lde, d_zs_lde, log_n, rate_bits, p, betas, gammas, alphas, d_gate_terms, num_gate_terms,
+                                nullptr, nullptr, d_chunks);
+}
+
+int sipp_plonk_quotient_chunks(sipp_ctx* ctx, const uint64_t* d_wires_lde, const uint64_t* d_sigmas_lde, const uint64_t* d_zs_lde, uint32_t log_n,
+                               uint32_t rate_bits, const sipp_plonk_params* p, const uint64_t* betas, const uint64_t* gammas,
+                               const uint64_t* alphas, uint64_t* d_chunks) {
+    return sipp_plonk_quotient_chunks_ex(ctx, d_wires_lde, d_sigmas_lde, d_zs_lde, log_n, rate_bits, p, betas, gammas, alphas, nullptr, 0, d_chunks);
+}
+
 // circuit_data.hip refuses a malformed gate set at build time
 int sipp_plonk_circuit_check(sipp_ctx* ctx, const sipp_plonk_circuit* c, const sipp_plonk_params* p) { return circuit_check(ctx, c, p); }
 
@@ -507,9 +502,6 @@ struct PlonkExtra {
     // the tree hasher of every oracle and FRI layer (with circ): recorded in header word 13, which is zero under Poseidon
     uint32_t hasher = SIPP_HASH_POSEIDON;
 };
-int plonk_prove_impl(sipp_ctx* ctx, const uint64_t* d_wires, const uint64_t* d_sigmas, uint32_t log_n, const sipp_plonk_params* p,
-                     const sipp_fri_params* fp, const uint64_t circuit_digest[4], const uint64_t public_inputs_hash[4], const PlonkExtra& ex,
-                     uint64_t* proof_out, size_t proof_cap, size_t* proof_len);
 
 // The opening set of a plonk proof, for the prover and the two size functions: four oracles -- constants_sigmas (the sigmas alone
 // without a circuit) | wires | zs_partial_products | quotient chunks -- all opened at zeta, the C running products Z again at g zeta.
@@ -560,36 +552,24 @@ size_t plonk_proof_words(uint32_t log_n, const sipp_plonk_params* p, const sipp_
     const size_t op = lay.opening_words(log_n, fp);
     return op ? lay.head_words(log_n, fp) + op + n_public_inputs : 0;
 }
-}  // namespace
 
-int sipp_plonk_perm_prove(sipp_ctx* ctx, const uint64_t* d_wires, const uint64_t* d_sigmas, uint32_t log_n, const sipp_plonk_params* p,
-                          const sipp_fri_params* fp, const uint64_t circuit_digest[4], const uint64_t public_inputs_hash[4],
-                          uint64_t* proof_out, size_t proof_cap, size_t* proof_len) {
-    if (!ctx || !d_wires || !d_sigmas || !fp || !circuit_digest || !public_inputs_hash || !proof_out || !proof_len) return SIPP_E_BADARG;
-    return plonk_prove_impl(ctx, d_wires, d_sigmas, log_n, p, fp, circuit_digest, public_inputs_hash, PlonkExtra{}, proof_out, proof_cap, proof_len);
+// a pre-committed oracle (nullptr: none) is whole and holds what the prover would have committed itself
+bool oracle_ok(const sipp_oracle* o, uint32_t n_polys, uint32_t n_salt) {
+    return !o || (o->n_polys == n_polys && o->n_salt == n_salt && o->d_coeffs && o->d_lde && o->d_tree);
 }
 
-int sipp_plonk_prove_ex(sipp_ctx* ctx, const uint64_t* d_wires, const uint64_t* d_sigmas, const sipp_oracle* wires_oracle, const uint64_t* wires_cap,
-                        const sipp_oracle* sigmas_oracle, uint32_t log_n, const sipp_plonk_params* p, const sipp_fri_params* fp,
-                        const uint64_t circuit_digest[4], const uint64_t* public_inputs, uint32_t n_public_inputs, const uint64_t* d_gate_terms,
-                        uint32_t num_gate_terms, uint64_t* proof_out, size_t proof_cap, size_t* proof_len) {
-    if (!ctx || !d_wires || !d_sigmas || !fp || !p || !circuit_digest || !proof_out || !proof_len || (n_public_inputs && !public_inputs) ||
-        (num_gate_terms != 0) != (d_gate_terms != nullptr) || (wires_oracle != nullptr) != (wires_cap != nullptr) || n_public_inputs > (1u << 24))
-        return SIPP_E_BADARG;
-    if ((wires_oracle && (wires_oracle->n_polys != p->num_routed_wires || wires_oracle->n_salt || !wires_oracle->d_coeffs || !wires_oracle->d_lde ||
-                          !wires_oracle->d_tree)) ||
-        (sigmas_oracle && (sigmas_oracle->n_polys != p->num_routed_wires || sigmas_oracle->n_salt || !sigmas_oracle->d_coeffs ||
-                           !sigmas_oracle->d_lde || !sigmas_oracle->d_tree)))
-        return sipp_fail(ctx, SIPP_E_BADARG, "plonk: a pre-committed oracle must hold num_routed_wires unsalted polynomials");
-    uint64_t pih[4];
-    host::Challenger::hash_no_pad(public_inputs, n_public_inputs, pih);      // plonk/prover.rs: hash_n_to_hash_no_pad(public_inputs)
-    PlonkExtra ex;
-    ex.d_gate_terms = d_gate_terms; ex.n_gate_terms = num_gate_terms; ex.public_inputs = public_inputs; ex.n_public_inputs = n_public_inputs;
-    ex.v2 = true; ex.sigmas_oracle = sigmas_oracle; ex.wires_oracle = wires_oracle; ex.wires_cap = wires_cap;
-    return plonk_prove_impl(ctx, d_wires, d_sigmas, log_n, p, fp, circuit_digest, pih, ex, proof_out, proof_cap, proof_len);
+// header[0 .. lay.header_words) of a flat proof of `total` words: the words every kind carries, then the kind's own, zero where it says nothing
+void write_header(uint64_t* out, uint64_t magic, const PlonkLayout& lay, uint32_t log_n, const sipp_plonk_params* p, size_t total, uint64_t tail,
+                  const PlonkExtra& ex) {
+    uint64_t h[24] = {magic, log_n, p->num_routed_wires, p->max_degree, p->num_challenges, total, ex.v2 ? ex.n_gate_terms : 0, tail};
+    if (const sipp_plonk_circuit* c = ex.circ) {      // header[12] = 1 under blinding, [13] the hasher, [16 .. 24) the lookup description
+        const uint64_t own[8] = {c->num_wires, c->num_constants, c->num_selectors, c->num_gates, num_gate_constraints(c), tail, ex.blind ? 1u : 0u, ex.hasher};
+        std::copy(own, own + 8, h + 6);
+        for (int q = 0; q < 8 && ex.lookup; q++) h[16 + q] = plonk_desc::lookup_word(*ex.lookup, q);
+    }
+    memcpy(out, h, lay.header_words * 8);
 }
 
-namespace {
 int plonk_prove_impl(sipp_ctx* ctx, const uint64_t* d_wires, const uint64_t* d_sigmas, uint32_t log_n, const sipp_plonk_params* p,
                      const sipp_fri_params* fp, const uint64_t circuit_digest[4], const uint64_t public_inputs_hash[4], const PlonkExtra& ex,
                      uint64_t* proof_out, size_t proof_cap, size_t* proof_len) {
@@ -599,9 +579,9 @@ int plonk_prove_impl(sipp_ctx* ctx, const uint64_t* d_wires, const uint64_t* d_s
         return sipp_fail(ctx, SIPP_E_UNSUPPORTED, "plonk: blowup 2^rate_bits >= quotient degree factor, <= 8, unsalted oracles");
     SIPP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
     ArenaScope scope(ctx);
-    const uint32_t R = p->num_routed_wires, D = p->max_degree, C = p->num_challenges, nz = C * m;
+    const uint32_t C = p->num_challenges, nz = C * m;
     const size_t n = (size_t)1 << log_n, M = n << fp->rate_bits, cap_n = (size_t)1 << std::min(fp->cap_height, log_n + fp->rate_bits);
-    const uint32_t K = ex.circ ? ex.circ->num_constants : 0, Wn = ex.circ ? ex.circ->num_wires : R;
+    const uint32_t K = ex.circ ? ex.circ->num_constants : 0;
     const bool zk = ex.blind != nullptr;
     const PlonkLayout lay(p, m, ex.circ, ex.lookup, zk);
     const uint32_t* ncols = lay.ncols;             // (ncols[2] = nz + the S / U columns of a lookup description)
@@ -687,20 +667,9 @@ int plonk_prove_impl(sipp_ctx* ctx, const uint64_t* d_wires, const uint64_t* d_s
     ch.store(&cs);
     size_t op_len = 0;
     SIPP_TRY(sipp_fri_prove_openings_h(ctx, oracles, 4, batches, 2, log_n, fp, ex.hasher, &cs, proof_out + head, proof_cap - head - tail, &op_len));
-    if (ex.lookup || zk) {      // "SIPPPLK5": header[12] = 1, the description words all zero without lookups
-        uint64_t h[24] = {zk ? 0x354b4c5050504953ULL /* "SIPPPLK5" */ : 0x344b4c5050504953ULL /* "SIPPPLK4" */, log_n, R, D, C, head + op_len + tail,
-                          Wn, K, ex.circ->num_selectors, ex.circ->num_gates, num_gate_constraints(ex.circ), tail, zk ? 1u : 0u, ex.hasher, 0, 0};
-        for (int q = 0; q < 8; q++) h[16 + q] = ex.lookup ? plonk_desc::lookup_word(*ex.lookup, q) : 0;
-        memcpy(proof_out, h, sizeof h);
-    } else if (ex.circ) {
-        const uint64_t h[16] = {0x334b4c5050504953ULL /* "SIPPPLK3" */, log_n, R, D, C, head + op_len + tail, Wn, K, ex.circ->num_selectors,
-                                ex.circ->num_gates, num_gate_constraints(ex.circ), tail, 0, ex.hasher, 0, 0};
-        memcpy(proof_out, h, sizeof h);
-    } else {
-        const uint64_t h[8] = {ex.v2 ? 0x324b4c5050504953ULL /* "SIPPPLK2" */ : 0x314b4c5050504953ULL /* "SIPPPLK1" */, log_n, R, D, C,
-                               head + op_len + tail, ex.v2 ? ex.n_gate_terms : 0, tail};
-        memcpy(proof_out, h, sizeof h);
-    }
+    // "SIPPPLK1" .. "SIPPPLK5": the permutation argument alone | with gate terms and public inputs | gates as data | lookups | salted oracles
+    const int kind = zk ? 5 : ex.lookup ? 4 : ex.circ ? 3 : ex.v2 ? 2 : 1;
+    write_header(proof_out, 0x304b4c5050504953ULL + ((uint64_t)kind << 56), lay, log_n, p, head + op_len + tail, tail, ex);
     if (tail) memcpy(proof_out + head + op_len, ex.public_inputs, tail * 8);
     memcpy(proof_out + hw, cap_of(1), cap_n * 32);
     memcpy(proof_out + hw + cap_n * 4, cap_of(2), cap_n * 32);
@@ -708,36 +677,108 @@ int plonk_prove_impl(sipp_ctx* ctx, const uint64_t* d_wires, const uint64_t* d_s
     *proof_len = head + op_len + tail;
     return SIPP_OK;
 }
-}  // namespace
 
-size_t sipp_plonk_perm_proof_size(uint32_t log_n, const sipp_plonk_params* p, const sipp_fri_params* fp) {
-    return plonk_proof_words(log_n, p, fp, nullptr, 0);
-}
-
-namespace {
 // (the circuit's own bounds: circuit_check)
 bool sizes_ok(const sipp_plonk_circuit* c, const sipp_plonk_params* p) {
     return c && p && c->num_wires >= p->num_routed_wires && plonk_desc::sizes_within_caps(c->num_wires, c->num_constants);
 }
 }  // namespace
 
+int sipp_plonk_perm_prove(sipp_ctx* ctx, const uint64_t* d_wires, const uint64_t* d_sigmas, uint32_t log_n, const sipp_plonk_params* p,
+                          const sipp_fri_params* fp, const uint64_t circuit_digest[4], const uint64_t public_inputs_hash[4],
+                          uint64_t* proof_out, size_t proof_cap, size_t* proof_len) {
+    if (!ctx || !d_wires || !d_sigmas || !fp || !circuit_digest || !public_inputs_hash || !proof_out || !proof_len) return SIPP_E_BADARG;
+    return plonk_prove_impl(ctx, d_wires, d_sigmas, log_n, p, fp, circuit_digest, public_inputs_hash, PlonkExtra{}, proof_out, proof_cap, proof_len);
+}
+
+int sipp_plonk_prove_ex(sipp_ctx* ctx, const uint64_t* d_wires, const uint64_t* d_sigmas, const sipp_oracle* wires_oracle, const uint64_t* wires_cap,
+                        const sipp_oracle* sigmas_oracle, uint32_t log_n, const sipp_plonk_params* p, const sipp_fri_params* fp,
+                        const uint64_t circuit_digest[4], const uint64_t* public_inputs, uint32_t n_public_inputs, const uint64_t* d_gate_terms,
+                        uint32_t num_gate_terms, uint64_t* proof_out, size_t proof_cap, size_t* proof_len) {
+    if (!ctx || !d_wires || !d_sigmas || !fp || !p || !circuit_digest || !proof_out || !proof_len || (n_public_inputs && !public_inputs) ||
+        (num_gate_terms != 0) != (d_gate_terms != nullptr) || (wires_oracle != nullptr) != (wires_cap != nullptr) || n_public_inputs > (1u << 24))
+        return SIPP_E_BADARG;
+    if (!oracle_ok(wires_oracle, p->num_routed_wires, 0) || !oracle_ok(sigmas_oracle, p->num_routed_wires, 0))
+        return sipp_fail(ctx, SIPP_E_BADARG, "plonk: a pre-committed oracle must hold num_routed_wires unsalted polynomials");
+    uint64_t pih[4];
+    host::Challenger::hash_no_pad(public_inputs, n_public_inputs, pih);      // plonk/prover.rs: hash_n_to_hash_no_pad(public_inputs)
+    PlonkExtra ex;
+    ex.d_gate_terms = d_gate_terms; ex.n_gate_terms = num_gate_terms; ex.public_inputs = public_inputs; ex.n_public_inputs = n_public_inputs;
+    ex.v2 = true; ex.sigmas_oracle = sigmas_oracle; ex.wires_oracle = wires_oracle; ex.wires_cap = wires_cap;
+    return plonk_prove_impl(ctx, d_wires, d_sigmas, log_n, p, fp, circuit_digest, pih, ex, proof_out, proof_cap, proof_len);
+}
+
+size_t sipp_plonk_perm_proof_size(uint32_t log_n, const sipp_plonk_params* p, const sipp_fri_params* fp) {
+    return plonk_proof_words(log_n, p, fp, nullptr, 0);
+}
+
+// ---- gates as data: ONE path behind the sibling entries (ctx.hpp; circuit_data.hip enters here as well) --------------------------------
+// words of a proof of the circuit under a lookup description (eight words; nullptr: the empty one) with (zk) or without salted oracles;
+// 0 for anything the prover would refuse
+size_t sipp_gates_proof_words(uint32_t log_n, const sipp_plonk_params* p, const sipp_fri_params* fp, const sipp_plonk_circuit* c,
+                              uint32_t n_public_inputs, const uint32_t* lookup, bool zk) {
+    Lookup l{};
+    if (!sizes_ok(c, p) || (lookup && sipp_lookup_check(nullptr, lookup, c->num_wires, c->num_constants, c->num_selectors, &l) != SIPP_OK)) return 0;
+    return plonk_proof_words(log_n, p, fp, c, n_public_inputs, l.empty() ? nullptr : &l, zk);
+}
+
+int sipp_prove_gates(sipp_ctx* ctx, const uint64_t* d_wires, const uint64_t* d_constants_sigmas, const sipp_oracle* wires_oracle,
+                     const uint64_t* wires_cap, const sipp_oracle* constants_sigmas_oracle, uint32_t log_n, const sipp_plonk_params* p,
+                     const sipp_fri_params* fp, const sipp_plonk_circuit* c, const uint64_t circuit_digest[4], const uint64_t* public_inputs,
+                     uint32_t n_public_inputs, const plonk_desc::ProveOptions& o, uint64_t* proof_out, size_t proof_cap, size_t* proof_len) {
+    if (!ctx || !d_wires || !d_constants_sigmas || !fp || !p || !c || !circuit_digest || !proof_out || !proof_len ||
+        (n_public_inputs && !public_inputs) || (wires_oracle != nullptr) != (wires_cap != nullptr) || n_public_inputs > (1u << 24))
+        return SIPP_E_BADARG;
+    SIPP_TRY(circuit_check(ctx, c, p));
+    Lookup l{};
+    if (o.lookup) SIPP_TRY(sipp_lookup_check(ctx, o.lookup, c->num_wires, c->num_constants, c->num_selectors, &l));
+    if (fp->hiding && !o.blind && !o.missing_seed_left_to_prover)
+        return sipp_fail(ctx, SIPP_E_BADARG, "plonk: FRI parameters with hiding = 1 need a blinding seed");
+    if (o.blind) {
+        if (!fp->hiding) return sipp_fail(ctx, SIPP_E_BADARG, "plonk: a blinding seed needs FRI parameters with hiding = 1");
+        SIPP_TRY(sipp_blind_check(ctx, o.blind));
+    }
+    if (!oracle_ok(wires_oracle, c->num_wires, o.blind ? SIPP_SALT_SIZE : 0u) ||
+        !oracle_ok(constants_sigmas_oracle, c->num_constants + p->num_routed_wires, 0))
+        return sipp_fail(ctx, SIPP_E_BADARG, "plonk: a pre-committed oracle must hold every column of its batch, the wires salted under blinding alone");
+    uint64_t pih[4];
+    host::Challenger::hash_no_pad(public_inputs, n_public_inputs, pih);
+    PlonkExtra ex;
+    ex.public_inputs = public_inputs; ex.n_public_inputs = n_public_inputs; ex.v2 = true;
+    ex.sigmas_oracle = constants_sigmas_oracle; ex.wires_oracle = wires_oracle; ex.wires_cap = wires_cap; ex.circ = c;
+    ex.lookup = l.empty() ? nullptr : &l;      // an empty description: "SIPPPLK3", word for word
+    ex.blind = o.blind;
+    ex.hasher = o.hasher;
+    return plonk_prove_impl(ctx, d_wires, d_constants_sigmas, log_n, p, fp, circuit_digest, pih, ex, proof_out, proof_cap, proof_len);
+}
+
+// ---- the entries of include/sipp_hip.h: each fills the options, makes the checks that are its own and enters above ---------------------
 size_t sipp_plonk_gates_proof_size(uint32_t log_n, const sipp_plonk_params* p, const sipp_fri_params* fp, const sipp_plonk_circuit* c,
                                    uint32_t n_public_inputs) {
-    return sizes_ok(c, p) ? plonk_proof_words(log_n, p, fp, c, n_public_inputs) : 0;
+    return sipp_gates_proof_words(log_n, p, fp, c, n_public_inputs, nullptr, false);
 }
 
 size_t sipp_plonk_gates_lookup_proof_size(uint32_t log_n, const sipp_plonk_params* p, const sipp_fri_params* fp, const sipp_plonk_circuit* c,
                                           uint32_t n_public_inputs, const uint32_t* lookup) {
-    Lookup l;
-    if (!sizes_ok(c, p) || sipp_lookup_check(nullptr, lookup, c->num_wires, c->num_constants, c->num_selectors, &l) != SIPP_OK) return 0;
-    return plonk_proof_words(log_n, p, fp, c, n_public_inputs, l.empty() ? nullptr : &l);
+    return lookup ? sipp_gates_proof_words(log_n, p, fp, c, n_public_inputs, lookup, false) : 0;
 }
 
-static int prove_gates_any(sipp_ctx* ctx, const uint64_t* d_wires, const uint64_t* d_constants_sigmas, const sipp_oracle* wires_oracle,
-                           const uint64_t* wires_cap, const sipp_oracle* constants_sigmas_oracle, uint32_t log_n, const sipp_plonk_params* p,
-                           const sipp_fri_params* fp, const sipp_plonk_circuit* c, const uint64_t circuit_digest[4], const uint64_t* public_inputs,
-                           uint32_t n_public_inputs, const uint32_t* lookup, const sipp_blinding* blind, bool zk_entry, uint32_t hasher,
-                           uint64_t* proof_out, size_t proof_cap, size_t* proof_len);
+size_t sipp_plonk_gates_zk_proof_size(uint32_t log_n, const sipp_plonk_params* p, const sipp_fri_params* fp, const sipp_plonk_circuit* c,
+                                      uint32_t n_public_inputs, const uint32_t* lookup) {
+    return lookup ? sipp_gates_proof_words(log_n, p, fp, c, n_public_inputs, lookup, fp && fp->hiding) : 0;
+}
+
+// these two take no seed: the one place where a hiding fp is left to plonk_prove_impl (SIPP_E_UNSUPPORTED, their answer since before blinding)
+int sipp_plonk_prove_gates_lookup(sipp_ctx* ctx, const uint64_t* d_wires, const uint64_t* d_constants_sigmas, const sipp_oracle* wires_oracle,
+                                  const uint64_t* wires_cap, const sipp_oracle* constants_sigmas_oracle, uint32_t log_n,
+                                  const sipp_plonk_params* p, const sipp_fri_params* fp, const sipp_plonk_circuit* c,
+                                  const uint64_t circuit_digest[4], const uint64_t* public_inputs, uint32_t n_public_inputs,
+                                  const uint32_t* lookup, uint64_t* proof_out, size_t proof_cap, size_t* proof_len) {
+    if (!lookup) return SIPP_E_BADARG;
+    const plonk_desc::ProveOptions o{lookup, nullptr, SIPP_HASH_POSEIDON, /* missing_seed_left_to_prover */ true};
+    return sipp_prove_gates(ctx, d_wires, d_constants_sigmas, wires_oracle, wires_cap, constants_sigmas_oracle, log_n, p, fp, c, circuit_digest,
+                            public_inputs, n_public_inputs, o, proof_out, proof_cap, proof_len);
+}
 
 int sipp_plonk_prove_gates(sipp_ctx* ctx, const uint64_t* d_wires, const uint64_t* d_constants_sigmas, const sipp_oracle* wires_oracle,
                            const uint64_t* wires_cap, const sipp_oracle* constants_sigmas_oracle, uint32_t log_n, const sipp_plonk_params* p,
@@ -748,33 +789,16 @@ int sipp_plonk_prove_gates(sipp_ctx* ctx, const uint64_t* d_wires, const uint64_
                                          circuit_digest, public_inputs, n_public_inputs, none, proof_out, proof_cap, proof_len);
 }
 
-int sipp_plonk_prove_gates_lookup(sipp_ctx* ctx, const uint64_t* d_wires, const uint64_t* d_constants_sigmas, const sipp_oracle* wires_oracle,
-                                  const uint64_t* wires_cap, const sipp_oracle* constants_sigmas_oracle, uint32_t log_n,
-                                  const sipp_plonk_params* p, const sipp_fri_params* fp, const sipp_plonk_circuit* c,
-                                  const uint64_t circuit_digest[4], const uint64_t* public_inputs, uint32_t n_public_inputs,
-                                  const uint32_t* lookup, uint64_t* proof_out, size_t proof_cap, size_t* proof_len) {
-    // (a hiding fp reaches plonk_prove_impl without a seed and is refused there, SIPP_E_UNSUPPORTED as before)
-    return prove_gates_any(ctx, d_wires, d_constants_sigmas, wires_oracle, wires_cap, constants_sigmas_oracle, log_n, p, fp, c, circuit_digest,
-                           public_inputs, n_public_inputs, lookup, nullptr, false, SIPP_HASH_POSEIDON, proof_out, proof_cap, proof_len);
-}
-
-size_t sipp_plonk_gates_zk_proof_size(uint32_t log_n, const sipp_plonk_params* p, const sipp_fri_params* fp, const sipp_plonk_circuit* c,
-                                      uint32_t n_public_inputs, const uint32_t* lookup) {
-    if (!fp || !fp->hiding) return sipp_plonk_gates_lookup_proof_size(log_n, p, fp, c, n_public_inputs, lookup);
-    Lookup l;
-    if (!sizes_ok(c, p) || sipp_lookup_check(nullptr, lookup, c->num_wires, c->num_constants, c->num_selectors, &l) != SIPP_OK) return 0;
-    return plonk_proof_words(log_n, p, fp, c, n_public_inputs, l.empty() ? nullptr : &l, true);
-}
-
 int sipp_plonk_prove_gates_zk(sipp_ctx* ctx, const uint64_t* d_wires, const uint64_t* d_constants_sigmas, const sipp_oracle* wires_oracle,
                               const uint64_t* wires_cap, const sipp_oracle* constants_sigmas_oracle, uint32_t log_n, const sipp_plonk_params* p,
                               const sipp_fri_params* fp, const sipp_plonk_circuit* c, const uint64_t circuit_digest[4],
                               const uint64_t* public_inputs, uint32_t n_public_inputs, const uint32_t* lookup, const uint64_t* blind_words,
                               uint64_t* proof_out, size_t proof_cap, size_t* proof_len) {
+    if (!lookup) return SIPP_E_BADARG;
     const BlindArg arg(blind_words);
-    const sipp_blinding* blind = arg.p;
-    return prove_gates_any(ctx, d_wires, d_constants_sigmas, wires_oracle, wires_cap, constants_sigmas_oracle, log_n, p, fp, c, circuit_digest,
-                           public_inputs, n_public_inputs, lookup, blind, true, SIPP_HASH_POSEIDON, proof_out, proof_cap, proof_len);
+    const plonk_desc::ProveOptions o{lookup, arg.p, SIPP_HASH_POSEIDON};
+    return sipp_prove_gates(ctx, d_wires, d_constants_sigmas, wires_oracle, wires_cap, constants_sigmas_oracle, log_n, p, fp, c, circuit_digest,
+                            public_inputs, n_public_inputs, o, proof_out, proof_cap, proof_len);
 }
 
 // sipp_plonk_prove_gates_zk with the tree hasher; a NULL lookup is the empty description
@@ -783,44 +807,10 @@ int sipp_plonk_prove_gates_h(sipp_ctx* ctx, const uint64_t* d_wires, const uint6
                              const sipp_fri_params* fp, const sipp_plonk_circuit* c, const uint64_t circuit_digest[4],
                              const uint64_t* public_inputs, uint32_t n_public_inputs, const uint32_t* lookup, const uint64_t* blind_words,
                              uint32_t hasher, uint64_t* proof_out, size_t proof_cap, size_t* proof_len) {
-    static const uint32_t none[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (!ctx) return SIPP_E_BADARG;
     SIPP_TRY(sipp_hasher_check(ctx, hasher));
     const BlindArg arg(blind_words);
-    return prove_gates_any(ctx, d_wires, d_constants_sigmas, wires_oracle, wires_cap, constants_sigmas_oracle, log_n, p, fp, c, circuit_digest,
-                           public_inputs, n_public_inputs, lookup ? lookup : none, arg.p, true, hasher, proof_out, proof_cap, proof_len);
-}
-
-// the two entries above: `zk_entry` answers a hiding fp without a seed itself (SIPP_E_BADARG), the lookup entry leaves it to plonk_prove_impl
-static int prove_gates_any(sipp_ctx* ctx, const uint64_t* d_wires, const uint64_t* d_constants_sigmas, const sipp_oracle* wires_oracle,
-                           const uint64_t* wires_cap, const sipp_oracle* constants_sigmas_oracle, uint32_t log_n, const sipp_plonk_params* p,
-                           const sipp_fri_params* fp, const sipp_plonk_circuit* c, const uint64_t circuit_digest[4], const uint64_t* public_inputs,
-                           uint32_t n_public_inputs, const uint32_t* lookup, const sipp_blinding* blind, bool zk_entry, uint32_t hasher,
-                           uint64_t* proof_out, size_t proof_cap, size_t* proof_len) {
-    if (!ctx || !lookup || !d_wires || !d_constants_sigmas || !fp || !p || !c || !circuit_digest || !proof_out || !proof_len ||
-        (n_public_inputs && !public_inputs) || (wires_oracle != nullptr) != (wires_cap != nullptr) || n_public_inputs > (1u << 24))
-        return SIPP_E_BADARG;
-    SIPP_TRY(circuit_check(ctx, c, p));
-    Lookup l;
-    SIPP_TRY(sipp_lookup_check(ctx, lookup, c->num_wires, c->num_constants, c->num_selectors, &l));
-    if (zk_entry && fp->hiding && !blind) return sipp_fail(ctx, SIPP_E_BADARG, "plonk: FRI parameters with hiding = 1 need a blinding seed");
-    if (blind) {
-        if (!fp->hiding) return sipp_fail(ctx, SIPP_E_BADARG, "plonk: a blinding seed needs FRI parameters with hiding = 1");
-        SIPP_TRY(sipp_blind_check(ctx, blind));
-    }
-    if ((wires_oracle && (wires_oracle->n_polys != c->num_wires || wires_oracle->n_salt != (blind ? SIPP_SALT_SIZE : 0u) || !wires_oracle->d_coeffs ||
-                          !wires_oracle->d_lde || !wires_oracle->d_tree)) ||
-        (constants_sigmas_oracle &&
-         (constants_sigmas_oracle->n_polys != c->num_constants + p->num_routed_wires || constants_sigmas_oracle->n_salt ||
-          !constants_sigmas_oracle->d_coeffs || !constants_sigmas_oracle->d_lde || !constants_sigmas_oracle->d_tree)))
-        return sipp_fail(ctx, SIPP_E_BADARG, "plonk: a pre-committed oracle must hold every column of its batch, the wires salted under blinding alone");
-    uint64_t pih[4];
-    host::Challenger::hash_no_pad(public_inputs, n_public_inputs, pih);
-    PlonkExtra ex;
-    ex.public_inputs = public_inputs; ex.n_public_inputs = n_public_inputs; ex.v2 = true;
-    ex.sigmas_oracle = constants_sigmas_oracle; ex.wires_oracle = wires_oracle; ex.wires_cap = wires_cap; ex.circ = c;
-    ex.lookup = l.empty() ? nullptr : &l;      // an empty description: "SIPPPLK3", word for word
-    ex.blind = blind;
-    ex.hasher = hasher;
-    return plonk_prove_impl(ctx, d_wires, d_constants_sigmas, log_n, p, fp, circuit_digest, pih, ex, proof_out, proof_cap, proof_len);
+    const plonk_desc::ProveOptions o{lookup, arg.p, hasher};
+    return sipp_prove_gates(ctx, d_wires, d_constants_sigmas, wires_oracle, wires_cap, constants_sigmas_oracle, log_n, p, fp, c, circuit_digest,
+                            public_inputs, n_public_inputs, o, proof_out, proof_cap, proof_len);
 }

@@ -70,6 +70,18 @@ inline LookupReason lookup_check(const Lookup& l, uint32_t num_wires, uint32_t n
     return LookupReason::ok;
 }
 
+// ---- the options of a gates-as-data proof ----------------------------------------------------------------------------------------------
+// What the sibling entries sipp_plonk_prove_gates{,_lookup,_zk,_h} differ in, as the ONE value behind them (plonk.hip sipp_prove_gates;
+// internal, not part of the ABI).  The defaults are every option off.
+struct ProveOptions {
+    const uint32_t* lookup = nullptr;           // the eight words of a lookup description; nullptr: the empty one
+    const sipp_blinding* blind = nullptr;       // the seed and counter of a zero-knowledge proof; nullptr: none
+    uint32_t hasher = SIPP_HASH_POSEIDON;
+    // a hiding fp and no seed is refused at the options (SIPP_E_BADARG) unless this is set: the two entries older than blinding, which
+    // take no seed, set it and keep the answer plonk_prove_impl has always given them (SIPP_E_UNSUPPORTED)
+    bool missing_seed_left_to_prover = false;
+};
+
 // ---- the gate set ----------------------------------------------------------------------------------------------------------------------
 enum class Circuit { ok, description, selector_group, past_program_words, program, operand };
 // the STRUCTURE of a gate set handed over as data: every operand in range, every program inside program_words -- an index out of range

@@ -1153,6 +1153,29 @@ int plonk_verify(const uint64_t* proof, size_t len, const uint64_t* cs_cap, cons
     return fri_openings_verify(op, op_len, caps, ncols, salt, 4, batches, 2, log_n, fp, hasher, ch);
 }
 
+// The frame every verify entry ends in: `check` gives the refusing stage (0: accepted), which goes to *reason; whatever it throws (an
+// allocation failure) stays on this side of the C boundary.  It covers the calling thread only, not fri_verify's worker threads.
+template <typename Check>
+int guarded(int* reason, Check&& check) {
+    int r;
+    try {
+        r = check();
+    } catch (...) {
+        return SIPP_E_NOMEM;
+    }
+    if (reason) *reason = r;
+    return r == 0 ? SIPP_OK : SIPP_E_VERIFY;
+}
+
+// what the three sipp_plonk_verify_gates* entries share; lookup: the eight words, nullptr or all zero for none (a "SIPPPLK3" proof)
+int verify_gates(const uint64_t* proof, size_t len, const uint64_t* cs_cap, const sipp_plonk_params* p, const sipp_fri_params* fp,
+                 const sipp_plonk_circuit* c, const uint64_t digest[4], const uint32_t* lookup, uint32_t hasher, int* reason) {
+    if (reason) *reason = 0;
+    if (!proof || !cs_cap || !p || !fp || !c || !digest || hasher > SIPP_HASH_KECCAK25) return SIPP_E_BADARG;
+    const plonk_desc::Lookup l = lookup ? plonk_desc::lookup_of(lookup) : plonk_desc::Lookup{};
+    return guarded(reason, [&] { return plonk_verify(proof, len, cs_cap, *p, *fp, *c, digest, l.empty() ? nullptr : &l, hasher); });
+}
+
 }  // namespace
 
 extern "C" int sipp_fri_verify_openings(const uint64_t* proof, size_t len, const uint64_t* const* caps, const uint32_t* ncols, const uint32_t* n_salt,
@@ -1173,29 +1196,16 @@ extern "C" int sipp_fri_verify_openings_h(const uint64_t* proof, size_t len, con
     std::vector<uint32_t> zero(n_oracles, 0);
     if (chal->n_in > 8 || chal->n_out > 8) return SIPP_E_BADARG;
     host::Challenger ch(*chal);
-    int r;
-    try {
-        r = fri_openings_verify(proof, len, caps, ncols, n_salt ? n_salt : zero.data(), n_oracles, bv.data(), n_batches, log_n, *p, hasher, ch);
-    } catch (...) {                        // (allocation failure: nothing crosses the C boundary)
-        return SIPP_E_NOMEM;
-    }
-    ch.store(chal);
-    if (reason) *reason = r;
-    return r == 0 ? SIPP_OK : SIPP_E_VERIFY;
+    return guarded(reason, [&] {
+        const int r = fri_openings_verify(proof, len, caps, ncols, n_salt ? n_salt : zero.data(), n_oracles, bv.data(), n_batches, log_n, *p, hasher, ch);
+        ch.store(chal);
+        return r;
+    });
 }
 
 extern "C" int sipp_plonk_verify_gates(const uint64_t* proof, size_t len, const uint64_t* constants_sigmas_cap, const sipp_plonk_params* p,
                                        const sipp_fri_params* fp, const sipp_plonk_circuit* c, const uint64_t circuit_digest[4], int* reason) {
-    if (reason) *reason = 0;
-    if (!proof || !constants_sigmas_cap || !p || !fp || !c || !circuit_digest) return SIPP_E_BADARG;
-    int r;
-    try {
-        r = plonk_verify(proof, len, constants_sigmas_cap, *p, *fp, *c, circuit_digest, nullptr, SIPP_HASH_POSEIDON);
-    } catch (...) {
-        return SIPP_E_NOMEM;
-    }
-    if (reason) *reason = r;
-    return r == 0 ? SIPP_OK : SIPP_E_VERIFY;
+    return verify_gates(proof, len, constants_sigmas_cap, p, fp, c, circuit_digest, nullptr, SIPP_HASH_POSEIDON, reason);
 }
 
 extern "C" int sipp_plonk_verify_gates_lookup(const uint64_t* proof, size_t len, const uint64_t* constants_sigmas_cap, const sipp_plonk_params* p,
@@ -1205,24 +1215,13 @@ extern "C" int sipp_plonk_verify_gates_lookup(const uint64_t* proof, size_t len,
         if (reason) *reason = 0;
         return SIPP_E_BADARG;
     }
-    return sipp_plonk_verify_gates_h(proof, len, constants_sigmas_cap, p, fp, c, circuit_digest, lookup, SIPP_HASH_POSEIDON, reason);
+    return verify_gates(proof, len, constants_sigmas_cap, p, fp, c, circuit_digest, lookup, SIPP_HASH_POSEIDON, reason);
 }
 
 extern "C" int sipp_plonk_verify_gates_h(const uint64_t* proof, size_t len, const uint64_t* constants_sigmas_cap, const sipp_plonk_params* p,
                                          const sipp_fri_params* fp, const sipp_plonk_circuit* c, const uint64_t circuit_digest[4],
                                          const uint32_t* lookup, uint32_t hasher, int* reason) {
-    static const uint32_t none[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (reason) *reason = 0;
-    if (!proof || !constants_sigmas_cap || !p || !fp || !c || !circuit_digest || hasher > SIPP_HASH_KECCAK25) return SIPP_E_BADARG;
-    const plonk_desc::Lookup l = plonk_desc::lookup_of(lookup ? lookup : none);      // an empty description: a "SIPPPLK3" proof
-    int r;
-    try {
-        r = plonk_verify(proof, len, constants_sigmas_cap, *p, *fp, *c, circuit_digest, l.empty() ? nullptr : &l, hasher);
-    } catch (...) {
-        return SIPP_E_NOMEM;
-    }
-    if (reason) *reason = r;
-    return r == 0 ? SIPP_OK : SIPP_E_VERIFY;
+    return verify_gates(proof, len, constants_sigmas_cap, p, fp, c, circuit_digest, lookup, hasher, reason);
 }
 
 extern "C" int sipp_stark_verify(const uint64_t* proof, size_t len, const sipp_stark_config* cfg, int* reason) {
@@ -1232,12 +1231,5 @@ extern "C" int sipp_stark_verify(const uint64_t* proof, size_t len, const sipp_s
     if (cfg) c = *cfg;
     else sipp_default_config(&c);
     if (c.num_challenges != 2) return SIPP_E_UNSUPPORTED;
-    int r;
-    try {
-        r = verify(proof, len, c);
-    } catch (...) {
-        return SIPP_E_NOMEM;
-    }
-    if (reason) *reason = r;
-    return r == 0 ? SIPP_OK : SIPP_E_VERIFY;
+    return guarded(reason, [&] { return verify(proof, len, c); });
 }
